@@ -1,8 +1,12 @@
 #!/usr/bin/env python
 """bench.py — images/sec of the Imagen 64->256 cascade on MI355X (BASELINE.json metric), one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run measures the headline only: it builds the model, gives every lane its stages and graphs (one 2-step sample per lane),
+runs W warm-up batches, times K batches and prints the result line.  `--dump-outputs DIR` writes the images of the last timed batch
+as DIR/images.npy (float32).  `--full` adds the extra legs below (and the `sequential` / `merged_requests` records).
 
 A "step" is ONE full pass of the hot path over one batch: `Imagen.sample()` of the README cascade (unet1 @64^2 ->
 unet2 @256^2), 1000 DDPM steps per stage, classifier-free guidance 3.0, batch 8 PER GPU (weak scaling: each rank
@@ -16,7 +20,7 @@ latency-bound at batch 8, so independent batches fill the idle CUs), `pipeline` 
 Imagen.sample_pipelined) or `sequential` (one sample() call after the other — also measured once after the timed region and
 reported under "sequential").  Every batch runs the full cascade at batch 8; nothing is shared between batches but the weights.
 
-Extra legs (rank 0, N = 1 only):
+Extra legs (--full; rank 0, N = 1 only):
   roofline     — HIP-event timing, on the launch stream, of every implicit-GEMM launch of one denoiser step of each stage, grouped
                  by kernel symbol (tile configuration, taps, epilogue / prologue instantiation) and by bound (algorithmic FLOP/byte vs the 312 FLOP/B ridge).  "roofline" is the dominant
                  group overall, "roofline_other_bound" the dominant group under the other roof: achieved = algorithmic FLOPs
@@ -49,6 +53,21 @@ README_U2 = dict(dim=32, cond_dim=512, dim_mults=(1, 2, 4, 8), num_resnet_blocks
 FLOPS_PER_IMAGE_REFERENCE = 287.3e12   # 2000 * (12.71 + 130.94) GF, as the reference executes the path
 MFMA_PEAK_TFLOPS = 2500.0              # dense fp16/bf16, MI355X_MICROARCH.md
 LANES_DEFAULT = 6
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory: str, **arrays):
+    """--dump-outputs: each array as DIR/<name>.npy in float32; one larger than 64 MB keeps its leading rows (a fixed sample)."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu()
+        if a.numel() * 4 > DUMP_LIMIT_BYTES:
+            a = a[:max(1, DUMP_LIMIT_BYTES // (4 * a[0].numel()))]
+        np.save(os.path.join(directory, name + ".npy"), a.contiguous().numpy())
 
 
 def build_imagen(timesteps: int, device):
@@ -443,7 +462,7 @@ OTHER_CONFIGS = {
 }
 
 
-def other_config_leg(name: str, steps: int, reps: int):
+def other_config_leg(name: str, steps: int, reps: int, dump_dir=None):
     """One of BASELINE.json's other configs on one GPU: `steps` sampling steps timed (graph replays, after a 2-step warm-up that packs the
     weights and captures the graphs), linearly extrapolated to the config's full schedule where `steps` is smaller (said in the record).
     Prints the bench JSON shape with the SURVEY ceiling and the fraction of the dense MFMA peak beside it."""
@@ -480,6 +499,8 @@ def other_config_leg(name: str, steps: int, reps: int):
         torch.cuda.synchronize()
         best = min(best, time.perf_counter() - t0)
     assert torch.isfinite(out).all()
+    if dump_dir:
+        dump_outputs(dump_dir, images=out)
     full = best * (T / steps)          # seconds per batch at the config's full schedule
     value = B / full
     launches = {f"stage{k[0]}": len(st["plan"].ops) for k, st in getattr(model, "_stages", {}).items()}
@@ -508,6 +529,11 @@ def main():
     ap.add_argument("--lanes", type=int, default=int(os.environ.get("IMAGEN_BENCH_LANES", "0")),
                     help="concurrent cascades in --mode lanes; 0 = min(6, --steps): throughput still rises from 3 to 6 lanes (round 3, call C: "
                          "8.90 / 8.00 / 7.50 ms per DDPM step pair at 3 / 4 / 6 lanes on one box); batches are handed out dynamically")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra legs (sequential latency, merged requests, calibration, roofline + PMC passes, CPU baseline); "
+                         "a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write the images of the last timed batch as DIR/images.npy (float32, at most 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-merged", action="store_true", help="skip the informational merged-requests leg (six requests as two merged batches of 24)")
@@ -518,7 +544,7 @@ def main():
     ap.add_argument("--config-steps", type=int, default=50, help="sampling steps timed by the c2 / c5 legs (extrapolated to the full schedule)")
     args = ap.parse_args()
     if args.config != "c3":
-        other_config_leg(args.config, args.config_steps, max(1, args.steps))
+        other_config_leg(args.config, args.config_steps, max(1, args.steps), args.dump_outputs)
         return
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline_leg(None, args.batch)), flush=True)
@@ -601,8 +627,16 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # every lane's stages / graphs are built by the warm-up (a lane only exists once a batch has run on it)
-    n_warm = max(args.warmup, min(args.lanes, args.steps)) if args.mode == "lanes" else args.warmup
+    if args.mode == "lanes":
+        # a lane only exists once a batch has run on it: one short sample per lane (2 DDPM steps per stage) builds every lane's stages,
+        # time tables and graphs, so that neither the warm-up nor the timed batches pay for it, whatever --warmup is.  One lane after the
+        # other: a graph capture must not overlap another lane's device synchronisation
+        for lane in range(1, args.lanes + 1):
+            with imagen.lane(lane):
+                imagen.sample(text_embeds=text_embeds, cond_scale=3.0, use_tqdm=False, seed=1000, sample_offset=rank * B, max_steps=2)
+        fence()
+        log(f"{args.lanes} lanes set up")
+    n_warm = args.warmup
     passes(0, n_warm)
     log(f"{n_warm} warmup passes done ({args.mode})")
     fence()
@@ -616,6 +650,9 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     assert torch.isfinite(out).all() and out.shape == (B * world, 3, 256, 256)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, images=out)
+        log(f"outputs of the last timed batch written to {args.dump_outputs}")
 
     if rank == 0:
         images = B * world * args.steps
@@ -645,7 +682,7 @@ def main():
         if os.path.basename(_abi_mod.LIB_PATH) != "libimagen_hip.so" or knobs:
             rec["config"]["kernel_library"] = os.path.basename(_abi_mod.LIB_PATH)
             rec["config"]["probe_knobs"] = knobs
-        if world == 1 and args.mode != "sequential":
+        if args.full and world == 1 and args.mode != "sequential":
             # the same cascade as ONE request at a time (latency view): three sequential passes outside the timed region, the median reported
             import threading
             dts, under_load = [], {}
@@ -679,7 +716,7 @@ def main():
             except Exception as e:  # noqa: BLE001
                 rec["sequential"]["in_graph_step_error"] = f"{type(e).__name__}: {e}"
             log("sequential passes done")
-        if world == 1 and args.mode == "lanes" and headline and not args.no_merged:
+        if args.full and world == 1 and args.mode == "lanes" and headline and not args.no_merged:
             # the same 48 images in flight as six requests MERGED three by three into two batches of 24 (Imagen.sample_requests: every row keeps its
             # request's noise), one lane each — informational, never the headline: the metric's requests are batch 8, and `value` above runs them as such
             try:
@@ -714,7 +751,7 @@ def main():
                 log("merged-requests leg done")
             except Exception as e:  # noqa: BLE001
                 rec["merged_requests_error"] = f"{type(e).__name__}: {e}"
-        if world == 1:
+        if args.full and world == 1:
             try:
                 rec["calibration"] = calibration_leg(device)
                 ul = (rec.get("sequential") or {}).get("rocm_smi_under_load") or {}
@@ -730,7 +767,7 @@ def main():
                 rec["calibration"] = None
                 rec["calibration_error"] = f"{type(e).__name__}: {e}"
         # the extra legs must never cost the headline line: a failure is reported in the record instead
-        if world == 1 and not args.no_roofline:
+        if args.full and world == 1 and not args.no_roofline:
             try:
                 # the counter passes are evidence beside the headline, never at its expense: skipped when the run is already long
                 spent = time.perf_counter() - t_start
@@ -743,7 +780,7 @@ def main():
                 rec["roofline"] = None
                 rec["roofline_error"] = f"{type(e).__name__}: {e}"
                 log(f"roofline leg failed: {e}")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 rec["cpu_baseline"] = cpu_baseline_leg(imagen, B)
                 log("cpu baseline leg done")

@@ -522,8 +522,99 @@ def make_checkpoint_fixture(ip, path, seed=17, T=2):
     print(f"wrote {path}: {len(model_sd)} model tensors, {len(ema)} ema entries, out std {expected['ema']['output'].std():.4f}")
 
 
+def make_reference_outputs_fixtures(ip, iv):
+    """tests/golden/reference_{unet,unet3d,sampler}.pt for tests/test_oracle_vs_reference.py: the reference's outputs for the weights and
+    inputs of tests/reference_cases.py (the weights loaded strictly into the reference's modules), its state_dict layouts, and the error
+    its constructor raises for `cross_embed_downsample`."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import reference_cases as rc
+    from unet_config_sweep import SWEEP
+
+    def ref_unet(kw, sd):
+        u = ip.Unet(**kw).eval()
+        u.load_state_dict(sd)
+        return u
+
+    def ref_unet3d(kw, sd):
+        u = iv.Unet3D(**kw).eval()
+        u.load_state_dict(sd)
+        return u
+
+    out = {"unet": {}, "unet3d": {}, "sampler": {}}
+    with torch.no_grad():
+        fx = out["unet"]
+        for name, kw in rc.UNET_FORWARD.items():
+            sd, x, t, te, extra = rc.unet_forward_case(kw)
+            u = ref_unet(kw, sd)
+            fx[f"forward/{name}"] = [u(x, t, text_embeds=te, cond_drop_prob=cdp, **extra) for cdp in (0.0, 1.0)]
+        fx["layout"] = [rc.layout(ip.Unet(**kw)) for kw in rc.LAYOUT_CONFIGS]
+        for name in SWEEP:
+            kw, ours, x, t, te, extra = rc.sweep_case(name)
+            u = ref_unet(kw, ours.state_dict())
+            fx[f"sweep_layout/{name}"] = rc.layout(u)
+            fx[f"sweep/{name}"] = [u(x, t, text_embeds=te, cond_drop_prob=cdp, **extra) for cdp in (0.0, 1.0)]
+        try:
+            ip.Unet(dim=8, dim_mults=(1, 2), cross_embed_downsample=True)
+            fx["cross_embed_downsample_error"] = ""
+        except Exception as e:  # noqa: BLE001 — the type is what is recorded
+            fx["cross_embed_downsample_error"] = type(e).__name__
+
+        fx = out["unet3d"]
+        sd, x, t, te = rc.unet3d_readme_case()
+        u = ref_unet3d(rc.UNET3D_README, sd)
+        fx["readme"] = [u(x, t, text_embeds=te, cond_drop_prob=cdp) for cdp in (0.0, 1.0)]
+        for lowres in (False, True):
+            for prompts in ("pre", "post", "both"):
+                kw, sd, x, t, te, extra = rc.unet3d_prompt_case(lowres, prompts)
+                u = ref_unet3d(kw, sd)
+                fx[f"prompt/{prompts}-{lowres}"] = [u(x, t, text_embeds=te, cond_drop_prob=cdp, **extra) for cdp in (0.0, 1.0)]
+        for lowres, prompt in ((False, False), (True, False), (True, True)):
+            kw, ours, x, t, te, extra = rc.unet3d_cond_images_case(lowres, prompt)
+            u = ref_unet3d(kw, ours.state_dict())
+            fx[f"cond_images_layout/{lowres}-{prompt}"] = rc.layout(u)
+            fx[f"cond_images/{lowres}-{prompt}"] = [u(x, t, text_embeds=te, cond_drop_prob=cdp, **extra) for cdp in (0.0, 1.0)]
+
+        fx = out["sampler"]
+        for name, (cond_ch, self_cond, mode) in rc.SAMPLER.items():
+            unets, te, extra = rc.sampler_case(cond_ch, self_cond, mode)
+            im = ip.Imagen(tuple(ip.Unet(**{k: v for k, v in kw.items() if k != "lowres_cond"}) for _, kw in unets), image_sizes=(16, 32),
+                           timesteps=4, text_embed_dim=768, cond_drop_prob=0.1, resize_mode=mode)
+            for u, (sd, _) in zip(im.unets, unets):
+                u.load_state_dict(sd)
+            torch.manual_seed(123)
+            fx[f"cascade/{name}"] = im.sample(text_embeds=te, cond_scale=3., use_tqdm=False, return_all_unet_outputs=True, **extra)
+        calls = rc.schedule_inputs()
+        for ns in ("linear", "cosine"):
+            sch = ip.GaussianDiffusionContinuousTimes(noise_schedule=ns, timesteps=37)
+            for name, (method, args, kw) in calls.items():
+                r = getattr(sch, method)(*args, **kw)
+                fx[f"schedule/{ns}/{name}"] = list(r) if isinstance(r, tuple) else [r]
+            fx[f"schedule/{ns}/timesteps"] = [torch.stack([a, b]) for a, b in sch.get_sampling_timesteps(4, device="cpu")]
+            fx[f"schedule/{ns}/random_times_shape"] = tuple(sch.sample_random_times(5, device="cpu").shape)
+        im = ip.Imagen((ip.Unet(**rc.POSTERIOR_UNET),), image_sizes=(16,), timesteps=10, text_embed_dim=768, cond_drop_prob=0.1)
+        for objective in ("noise", "x_start", "v"):
+            for dyn in (True, False):
+                x, mo, t, tn = rc.posterior_inputs()     # fresh for every case: the reference clamps the model output in place
+                (m, v, lv), s = im.p_mean_variance(im.unets[0], x, t, noise_scheduler=im.noise_schedulers[0], t_next=tn, model_output=mo,
+                                                   pred_objective=objective, dynamic_threshold=dyn)
+                fx[f"posterior/{objective}-{dyn}"] = [m, v, lv, s]
+
+    def contiguous(v):
+        if isinstance(v, torch.Tensor):
+            return v.detach().contiguous().clone()
+        return type(v)(contiguous(x) for x in v) if isinstance(v, (list, tuple)) else v
+
+    for group, fx in out.items():
+        path = os.path.join(GOLDEN, rc.FIXTURES[group])
+        torch.save({k: contiguous(v) for k, v in fx.items()}, path)
+        print(f"wrote {path}: {len(fx)} entries, {os.path.getsize(path) / 1024:.0f} KiB")
+
+
 def main():
     ip = load_reference()
+    if "--reference-outputs" in sys.argv:   # only the fixtures of tests/test_oracle_vs_reference.py
+        make_reference_outputs_fixtures(ip, load_reference("imagen_video"))
+        return
     if "--video" in sys.argv:        # only the video sampling fixture
         make_video_sample_fixture(ip, load_reference("imagen_video"), os.path.join(GOLDEN, "sample_tiny_video.pt"))
         return

@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 O=$GRAFT_REPO_ROOT/gpurun_out/r04_s; mkdir -p $O
 for L in 6 9 12; do
-  timeout 400 python bench.py --lanes $L --steps $L --warmup $L --timesteps 250 --no-cpu-baseline --no-roofline 2>/dev/null | tail -n 1 > $O/lanes_$L.json
+  timeout 400 python bench.py --full --lanes $L --steps $L --warmup $L --timesteps 250 --no-cpu-baseline --no-roofline 2>/dev/null | tail -n 1 > $O/lanes_$L.json
   python - $O/lanes_$L.json $L <<'PY' | tee -a $O/lanes_ab.jsonl
 import json, sys
 d = json.loads(open(sys.argv[1]).read())

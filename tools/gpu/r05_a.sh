@@ -19,7 +19,7 @@ cp $R/gpurun_out/parity_measured.json $OUT/parity.json 2>/dev/null
 echo "=== smoke"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1; tail -n 3 $OUT/smoke.txt
 echo "=== bench (6 lanes) with the new calibration"
-timeout 600 python bench.py --steps 6 --warmup 6 --no-cpu-baseline --no-pmc > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+timeout 600 python bench.py --full --steps 6 --warmup 6 --no-cpu-baseline --no-pmc > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 tail -n 4 $OUT/bench_n1.err; cut -c1-1800 $OUT/bench_n1.json
 cd /tmp && export TMPDIR=/tmp
 echo "=== in-graph per-op profile"

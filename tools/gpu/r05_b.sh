@@ -14,7 +14,7 @@ echo "=== step A/B"
 for rc in 1 0; do IMAGEN_ROWCHAIN=$rc timeout 200 python tools/step_time.py --steps 60 --reps 3 --tag rowchain$rc 2>/dev/null | tail -n 1 | tee -a $OUT/step_ab.jsonl; done
 echo "=== bench: lanes vs staged (12 passes each)"
 for m in lanes staged; do
-  timeout 500 python bench.py --steps 12 --warmup 6 --mode $m --no-cpu-baseline --no-pmc --no-roofline > $OUT/bench_$m.json 2> $OUT/bench_$m.err
+  timeout 500 python bench.py --full --steps 12 --warmup 6 --mode $m --no-cpu-baseline --no-pmc --no-roofline > $OUT/bench_$m.json 2> $OUT/bench_$m.err
   tail -n 3 $OUT/bench_$m.err | cut -c1-200; python -c "
 import json,sys
 r=json.load(open('$OUT/bench_$m.json'))

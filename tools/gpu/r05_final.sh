@@ -16,10 +16,10 @@ cp $R/gpurun_out/parity_bench_shapes.json $OUT/parity_bench_shapes.json 2>/dev/n
 echo "=== smoke"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1; tail -n 2 $OUT/smoke.txt
 echo "=== bench (default: 6 lanes, 1000 steps) with the live PMC passes, calibration and the CPU baseline"
-timeout 1000 python bench.py --steps 6 --warmup 6 > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+timeout 1000 python bench.py --full --steps 6 --warmup 6 > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 tail -n 6 $OUT/bench_n1.err; cut -c1-3000 $OUT/bench_n1.json
 echo "=== the same headline without the small-map family (same box)"
-IMAGEN_CONV_SMALL=0 timeout 600 python bench.py --steps 6 --warmup 6 --no-cpu-baseline --no-roofline > $OUT/bench_n1_conv_small_off.json 2> $OUT/bench_n1_conv_small_off.err
+IMAGEN_CONV_SMALL=0 timeout 600 python bench.py --full --steps 6 --warmup 6 --no-cpu-baseline --no-roofline > $OUT/bench_n1_conv_small_off.json 2> $OUT/bench_n1_conv_small_off.err
 cut -c1-400 $OUT/bench_n1_conv_small_off.json
 cd /tmp && export TMPDIR=/tmp
 echo "=== rocprofv3 kernel stats of the sampling loop (sequential, 60 timesteps)"

@@ -7,7 +7,7 @@ R=$PWD
 OUT=$R/gpurun_out/r05_g
 mkdir -p $OUT
 echo "=== bench (driver-sized: --steps 20 --warmup 6)"
-timeout 1200 python bench.py --steps 20 --warmup 6 > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+timeout 1200 python bench.py --full --steps 20 --warmup 6 > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 tail -n 8 $OUT/bench_n1.err | cut -c1-200; cut -c1-600 $OUT/bench_n1.json
 cd /tmp && export TMPDIR=/tmp
 echo "=== PMC passes joined with the plan"

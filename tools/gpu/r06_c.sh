@@ -13,7 +13,7 @@ timeout 1500 python -m pytest tests -m gpu -q --tb=short -p no:cacheprovider > $
 tail -n 30 $OUT/pytest_gpu.txt | cut -c1-200
 cp $R/gpurun_out/parity_measured.json $OUT/parity.json 2>/dev/null
 echo "=== bench (6 lanes, 1000 steps; no PMC passes, no CPU baseline: the calibration block is what this call is about)"
-timeout 900 python bench.py --steps 6 --warmup 6 --no-cpu-baseline --no-pmc > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+timeout 900 python bench.py --full --steps 6 --warmup 6 --no-cpu-baseline --no-pmc > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 tail -n 4 $OUT/bench_n1.err; python - <<PY
 import json
 r = json.load(open("$OUT/bench_n1.json"))

@@ -18,7 +18,7 @@ for key, st in imagen._stages.items():
         torch.cuda.synchronize(); t0 = time.perf_counter(); eng._tt_plan.run(); torch.cuda.synchronize(); dt = time.perf_counter() - t0
     print(f"stage {key[0]}: time-table pass {dt*1e3:.2f} ms for {st['coef'].shape[0]} steps x {eng.R} rows ({len(eng._tt_plan)} launches)")
 PY
-timeout 600 python bench.py --steps 6 --warmup 6 --no-cpu-baseline --no-roofline > $OUT/bench_tt.json 2>$OUT/bench_tt.err
+timeout 600 python bench.py --full --steps 6 --warmup 6 --no-cpu-baseline --no-roofline > $OUT/bench_tt.json 2>$OUT/bench_tt.err
 python -c "import json;d=json.load(open('$OUT/bench_tt.json'));print('table:',d['value'],d['ms_per_step'],d['sequential']['value'],d['sequential']['ms_per_ddpm_step_pair'])"
-IMAGEN_TIME_TABLE=0 timeout 600 python bench.py --steps 6 --warmup 6 --no-cpu-baseline --no-roofline > $OUT/bench_chain.json 2>$OUT/bench_chain.err
+IMAGEN_TIME_TABLE=0 timeout 600 python bench.py --full --steps 6 --warmup 6 --no-cpu-baseline --no-roofline > $OUT/bench_chain.json 2>$OUT/bench_chain.err
 python -c "import json;d=json.load(open('$OUT/bench_chain.json'));print('chain:',d['value'],d['ms_per_step'],d['sequential']['value'],d['sequential']['ms_per_ddpm_step_pair'])"

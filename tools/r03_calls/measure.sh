@@ -13,7 +13,7 @@ tail -n 14 $OUT/pytest_gpu.txt | cut -c1-250
 cp $R/gpurun_out/parity_measured.json $OUT/parity.json 2>/dev/null
 cp $R/gpurun_out/parity_bench_shapes.json $OUT/parity_bench_shapes.json 2>/dev/null
 echo "=== bench (default: 6 lanes, 1000 steps) with the live PMC passes, calibration and the CPU baseline"
-timeout 900 python bench.py --steps 6 --warmup 6 > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+timeout 900 python bench.py --full --steps 6 --warmup 6 > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 tail -n 14 $OUT/bench_n1.err; cut -c1-2500 $OUT/bench_n1.json
 cd /tmp && export TMPDIR=/tmp
 echo "=== rocprofv3 kernel stats of the sampling loop (sequential, 60 timesteps)"
