@@ -140,9 +140,11 @@ __global__ __launch_bounds__(256) void quantile_final_kernel(const ImagenQuantil
   if (threadIdx.x == 0) {
     const uint32_t hi_key = (cnt_le >= k + 2u || min_gt == 0xFFFFFFFFu) ? nr.prefix : min_gt;
     const float lo = __uint_as_float(nr.prefix), hi = __uint_as_float(hi_key);
-    // torch lerp: w < 0.5 ? a + w*(b-a) : b - (b-a)*(1-w)
+    // torch lerp: w < 0.5 ? a + w*(b-a) : b - (b-a)*(1-w), each branch ONE fused multiply-add as torch's CPU kernel evaluates it
+    // (lerp_vec: fmadd(w or w-1, b-a, a or b)).  Spelt out, not left to fp contraction: an unfused b - (b-a)*(1-w) rounds twice
+    // and can land one ulp away from torch.quantile.
     const float d = hi - lo;
-    p.out[b] = (w < 0.5f) ? (lo + w * d) : (hi - d * (1.0f - w));
+    p.out[b] = (w < 0.5f) ? fmaf(w, d, lo) : fmaf(w - 1.0f, d, hi);
   }
 }
 

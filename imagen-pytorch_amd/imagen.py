@@ -44,6 +44,12 @@ _SAMPLING_DEVICE_TYPES = ('cuda',)   # where plans can be launched; tests/test_s
 TAG_INIT, TAG_LOWRES = 0x7FFF0001, 0x7FFF0002  # RANDN counter tags (step noise uses the step index)
 
 
+def nearest_indices(n_in: int, n_out: int) -> torch.Tensor:
+    """Source indices of F.interpolate(mode='nearest') along one axis: floor(dst * fp32(n_in / n_out)), capped at n_in - 1.  Torch
+    rounds the scale to fp32, so for some ratios (2 -> 82, 14 -> 46) this is not the integer dst * n_in // n_out; taken from torch itself."""
+    return F.interpolate(torch.arange(n_in, dtype=torch.float32).view(1, 1, n_in), n_out, mode='nearest').view(n_out).long()
+
+
 def _cast_tuple(val, length=None):
     if isinstance(val, list):
         val = tuple(val)
@@ -900,9 +906,8 @@ class Imagen(nn.Module):
                     src = img if self.auto_normalize_img else (img + 1) * 0.5                  # kernel normalises [0,1] -> [-1,1]
                     if st.get('video', False) and src.shape[1] != aug.shape[1]:
                         # a stage sampled at a lower frame rate feeds this one: nearest over the frame axis (resize_video_to,
-                        # iv.py:134-156; F.interpolate 'nearest' takes source index floor(dst * F_in / F_out)); once per stage
-                        f_in, f_out = src.shape[1], aug.shape[1]
-                        src = src[:, (torch.arange(f_out, device=src.device) * f_in) // f_out]
+                        # iv.py:134-156); once per stage
+                        src = src[:, nearest_indices(src.shape[1], aug.shape[1]).to(src.device)]
                     if self.resize_mode != 'nearest' and src.shape[-1] != S:
                         # LOWRES_PREP resizes with nearest in-kernel; any other mode is resized here, once per stage, and the kernel's
                         # own resize becomes the identity.  The resize acts on the [0, 1] image as in ip.py:2444-2446 (normalisation after).

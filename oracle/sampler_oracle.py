@@ -3,7 +3,7 @@
 Restates, in fp32 torch on CPU, the continuous-time Gaussian diffusion helpers
 (ip.py:212-318) and the ancestral sampler `Imagen.p_mean_variance / p_sample /
 p_sample_loop / sample` (ip.py:2042-2498) for the options the BASELINE configs use:
-noise-prediction objective, dynamic thresholding, classifier-free guidance, low-res
+the noise / x_start / v objectives, dynamic or static thresholding, classifier-free guidance, low-res
 noise-conditioning augmentation, plus the p_sample_loop options init_images, skip_steps
 and inpainting with resampling (ip.py:2205-2206, 2228-2229, 2237-2286), `cond_images`,
 self-conditioning unets, and for video stages `cond_video_frames` / `post_cond_video_frames`
@@ -77,15 +77,27 @@ def dynamic_threshold(x0: Tensor, percentile: float = 0.95) -> Tensor:
     return x0.clamp(-s, s) / s
 
 
+def predict_x0(x: Tensor, pred: Tensor, alpha: Tensor, sigma: Tensor, pred_objective: str = "noise") -> Tensor:
+    """The model output -> x0 estimate: ip.py:2085-2092 (noise: 314-318, v: 308-312, x_start: the output itself)."""
+    if pred_objective == "noise":
+        return (x - sigma * pred) / alpha.clamp(min=1e-8)
+    if pred_objective == "x_start":
+        return pred
+    if pred_objective == "v":
+        return alpha * x - sigma * pred
+    raise ValueError(f"unknown objective {pred_objective}")
+
+
 def ddpm_step(x: Tensor, pred_noise: Tensor, t: Tensor, t_next: Tensor, noise: Tensor, schedule: str,
-              dynamic_thresholding: bool = True, percentile: float = 0.95):
-    """x_t, eps_hat -> x_{t_next}.  t, t_next: (B,) fp32.  ip.py:314-318, 2094-2109, 252-270, 2160-2164."""
+              dynamic_thresholding: bool = True, percentile: float = 0.95, pred_objective: str = "noise"):
+    """x_t, model output -> x_{t_next}.  t, t_next: (B,) fp32.  `pred_noise` is eps_hat, or x0_hat / v_hat with
+    pred_objective 'x_start' / 'v'.  ip.py:2085-2092, 2094-2109, 252-270, 2160-2164."""
     fn = SCHEDULES[schedule]
     pad = lambda v: v.reshape(-1, *([1] * (x.ndim - 1)))
     log_snr, log_snr_next = pad(fn(t)), pad(fn(t_next))
     alpha, sigma = alpha_sigma(log_snr)
     alpha_next, sigma_next = alpha_sigma(log_snr_next)
-    x0 = (x - sigma * pred_noise) / alpha.clamp(min=1e-8)
+    x0 = predict_x0(x, pred_noise, alpha, sigma, pred_objective)
     x0 = dynamic_threshold(x0, percentile) if dynamic_thresholding else x0.clamp(-1.0, 1.0)
     c = -torch.special.expm1(log_snr - log_snr_next)
     mean = alpha_next * (x * (1 - c) / alpha + c * x0)
@@ -110,8 +122,9 @@ def p_sample_loop(denoise: Callable[[Tensor, Tensor], Tensor], shape, *, schedul
                   noise_fn: Callable, stage: int, dynamic_thresholding: bool = True, percentile: float = 0.95,
                   max_steps: Optional[int] = None, trace: Optional[list] = None, init_images: Optional[Tensor] = None,
                   skip_steps: Optional[int] = None, inpaint_images: Optional[Tensor] = None, inpaint_masks: Optional[Tensor] = None,
-                  inpaint_resample_times: int = 5, self_cond: bool = False, resize_mode: str = "nearest") -> Tensor:
-    """denoise(x_t, log_snr(t)) -> guided eps_hat; with `self_cond` the call is denoise(x_t, log_snr(t), x0_prev) where x0_prev is the
+                  inpaint_resample_times: int = 5, self_cond: bool = False, resize_mode: str = "nearest",
+                  pred_objective: str = "noise") -> Tensor:
+    """denoise(x_t, log_snr(t)) -> guided model output (eps_hat, or x0_hat / v_hat per `pred_objective`); with `self_cond` the call is denoise(x_t, log_snr(t), x0_prev) where x0_prev is the
     thresholded x0 estimate of the previous call (None before the first one; ip.py:2208-2210, 2249-2251).  Returns the un-normalised image in [0, 1] (ip.py:2167-2289).
 
     init_images / inpaint_images arrive NORMALISED to [-1, 1] and at any resolution (resized here, ip.py:2219-2220, 2457);
@@ -148,7 +161,8 @@ def p_sample_loop(denoise: Callable[[Tensor, Tensor], Tensor], shape, *, schedul
                 img = img * ~mask + noised * mask
             pred = denoise(img, fn(t), x_start) if self_cond else denoise(img, fn(t))
             tag = ("step", stage, i, r) if inpainting else ("step", stage, i)
-            img, x_start = ddpm_step(img, pred, t, t_next, noise_fn(tag, shape), schedule, dynamic_thresholding, percentile)
+            img, x_start = ddpm_step(img, pred, t, t_next, noise_fn(tag, shape), schedule, dynamic_thresholding, percentile,
+                                     pred_objective)
             if inpainting and not (r == 0 or last_t):
                 img = q_sample_from_to(img, t_next, t, noise_fn(("renoise", stage, i, r), shape), schedule)   # ip.py:2268-2275
             if trace is not None:
@@ -169,7 +183,7 @@ def imagen_sample(
     noise_schedules="cosine",
     lowres_noise_schedule: str = "linear",
     lowres_sample_noise_level: float = 0.2,
-    dynamic_thresholding: bool = True,
+    dynamic_thresholding=True,                 # bool, or one per unet (ip.py:1958)
     percentile: float = 0.95,
     channels: int = 3,
     text_masks: Optional[Tensor] = None,
@@ -188,6 +202,7 @@ def imagen_sample(
     post_cond_video_frames: Optional[Tensor] = None,   # normalised — after the per-stage temporal resize (ip.py:2417-2434)
     resize_cond_video_frames: bool = True,
     resize_mode: str = "nearest",              # Imagen(resize_mode=...): every image resize of the cascade (ip.py:1924); images only here
+    pred_objective="noise",                    # 'noise' | 'x_start' | 'v', or one per unet (Imagen(pred_objectives=...), ip.py:1877)
 ):
     """ip.py:2291-2498 for text_embeds-conditioned sampling (no self-conditioning)."""
     n = len(unets)
@@ -204,6 +219,7 @@ def imagen_sample(
     as_tuple = lambda v: tuple(v) if isinstance(v, (list, tuple)) else (v,) * n
     init_images = [None if im is None else im * 2 - 1 for im in as_tuple(init_images)]   # normalize_img, ip.py:2391
     skip_steps = as_tuple(skip_steps)
+    objectives, dyn = as_tuple(pred_objective), as_tuple(dynamic_thresholding)
     known = None if inpaint_images is None else inpaint_images * 2 - 1                   # ip.py:2218
     if video and inpaint_masks is not None and inpaint_masks.ndim == 3:                  # ip.py:2376-2377
         inpaint_masks = inpaint_masks[:, None].expand(-1, video_frames, -1, -1)
@@ -241,9 +257,9 @@ def imagen_sample(
 
         shape = (b, channels, video_frames // tds[stage], size, size) if video else (b, channels, size, size)
         img = p_sample_loop(denoise, shape, schedule=sched, num_timesteps=T, noise_fn=noise_fn,
-                            stage=stage, dynamic_thresholding=dynamic_thresholding, percentile=percentile,
+                            stage=stage, dynamic_thresholding=bool(dyn[stage]), percentile=percentile,
                             max_steps=max_steps, init_images=init_images[stage], skip_steps=skip_steps[stage], inpaint_images=known,
                             inpaint_masks=inpaint_masks, inpaint_resample_times=inpaint_resample_times,
-                            self_cond=bool(kw.get("self_cond", False)), resize_mode=resize_mode)
+                            self_cond=bool(kw.get("self_cond", False)), resize_mode=resize_mode, pred_objective=objectives[stage])
         outputs.append(img)
     return outputs if return_all else outputs[-1]

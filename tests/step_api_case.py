@@ -84,3 +84,55 @@ def cond_images_cascade(device, timesteps=3, cond_ch=4, self_cond=False, resize_
         want = so.imagen_sample(sds, (16, 32), te, timesteps=timesteps, cond_scale=3., return_all=True, noise_fn=noise, cond_images=cond,
                                 resize_mode=resize_mode)
     return imagen, te, cond, (lambda tag, shape: noise(tag, shape).to(device)), want, sds
+
+
+# cond_scale per stage of the objectives cascade: each stage runs once with and once without classifier-free guidance
+OBJECTIVE_CFG_RUNS = {"cfg-off-on": (1.0, 3.0), "cfg-on-off": (3.0, 1.0)}
+
+
+def objectives_cascade(g, device, stages=2):
+    """The weights of tests/golden/sample_tiny_cascade.pt in Imagen(pred_objectives=('v', 'x_start'), dynamic_thresholding=(False, True),
+    dynamic_thresholding_percentile=0.9): the v and x_start branches of CFG_X0 (ip.py:2085-2092), the static clamp (no quantile launch)
+    and a quantile at q != 0.95.  Returns the Imagen and the oracle's (state_dict, kwargs) per stage."""
+    from imagen_pytorch_amd import Imagen, Unet
+
+    specs = g["unets"][:stages]
+    unets = [Unet(**spec["kwargs"]).eval() for spec in specs]
+    imagen = Imagen(unets, image_sizes=g["image_sizes"][:stages], timesteps=g["timesteps"], text_embed_dim=32, cond_drop_prob=0.1,
+                    pred_objectives=("v", "x_start")[:stages], dynamic_thresholding=(False, True)[:stages],
+                    dynamic_thresholding_percentile=0.9).to(device)
+    for u, spec in zip(imagen.unets, specs):   # cast_model_parameters may have re-instantiated: (re)load
+        u.load_state_dict(spec["state_dict"])
+    return imagen.eval(), [(spec["state_dict"], spec["kwargs"]) for spec in specs]
+
+
+def memo_noise(seed=5):
+    """A noise_fn(tag, shape) that draws each tag once from a seeded generator and hands the same tensor to every caller; `tags_of()` makes
+    a per-caller view that records which tags that caller asked for."""
+    gen = torch.Generator().manual_seed(seed)
+    draws = {}
+
+    def draw(tag, shape):
+        if tag not in draws:
+            draws[tag] = torch.randn(tuple(shape), generator=gen)
+        assert tuple(draws[tag].shape) == tuple(shape), (tag, draws[tag].shape, shape)
+        return draws[tag]
+
+    def tags_of(device="cpu"):
+        seen = set()
+
+        def fn(tag, shape):
+            seen.add(tag)
+            return draw(tag, shape).to(device)
+        return fn, seen
+    return tags_of
+
+
+def objectives_oracle(sds, g, cond_scale, noise_fn):
+    from oracle import sampler_oracle as so
+
+    n = len(sds)
+    with torch.no_grad():
+        return so.imagen_sample(sds, g["image_sizes"][:n], g["text_embeds"], timesteps=g["timesteps"], cond_scale=cond_scale[:n],
+                                dynamic_thresholding=(False, True)[:n], percentile=0.9, pred_objective=("v", "x_start")[:n],
+                                noise_fn=noise_fn, return_all=True)

@@ -494,3 +494,29 @@ def test_first_small_unet_of_a_process_can_be_recast():
             "assert '_sys' not in u._locals\nImagen([u], image_sizes=(16,), timesteps=4, text_embed_dim=32)\nprint('ok')\n")
     r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
     assert r.returncode == 0 and r.stdout.decode().strip().endswith("ok"), r.stdout.decode()[-1500:]
+
+
+def test_video_frame_resample_matches_interpolate_nearest():
+    """Imagen.sample hands a stage sampled at fewer frames to the next one through a nearest resample of the frame axis (resize_video_to,
+    iv.py:134-156).  Its source frames must be F.interpolate's for every pair of stage frame counts the cascade allows (descending
+    temporal_downsample_factor ending in 1, video_frames divisible by each).  Torch rounds the scale to fp32: for 2 -> 82 frames (factors
+    (41, 1)) the integer dst * f_in // f_out the sampler used before picks a different source frame."""
+    import torch.nn.functional as F
+    from imagen_pytorch_amd.imagen import nearest_indices
+
+    def torch_frames(f_in, f_out):
+        clip = torch.arange(f_in, dtype=torch.float32).view(1, 1, f_in, 1, 1)
+        return F.interpolate(clip, (f_out, 1, 1), mode="nearest").view(f_out).long()
+
+    checked = 0
+    for frames in range(1, 97):
+        factors = [f for f in range(1, frames + 1) if frames % f == 0]
+        for hi in factors:
+            for lo in factors:
+                if lo < hi:
+                    f_in, f_out = frames // hi, frames // lo
+                    assert torch.equal(nearest_indices(f_in, f_out), torch_frames(f_in, f_out)), (frames, hi, lo)
+                    checked += 1
+    assert checked > 1000
+    assert torch.equal(nearest_indices(2, 82), torch_frames(2, 82))
+    assert not torch.equal((torch.arange(82) * 2) // 82, torch_frames(2, 82))

@@ -226,6 +226,34 @@ def test_sample_vs_reference_fixture():
         assert torch.equal(a, b), "hipGraph replay must be bit-identical to eager launches"
 
 
+@pytest.mark.parametrize("run", ["cfg-off-on", "cfg-on-off"])
+def test_objectives_and_thresholding_sample_vs_oracle(run):
+    """Imagen.sample with pred_objectives ('v', 'x_start'), dynamic_thresholding (False, True) at percentile 0.9, each stage once with and
+    once without CFG (rows = B, no null half), against oracle.imagen_sample on the same memoised noise; graph replay == eager launches."""
+    from conftest import record_parity
+    from step_api_case import OBJECTIVE_CFG_RUNS, memo_noise, objectives_cascade, objectives_oracle
+
+    dev = gpu_device()
+    g = _load("sample_tiny_cascade.pt")
+    cs = OBJECTIVE_CFG_RUNS[run]
+    imagen, sds = objectives_cascade(g, dev)
+    tags_of = memo_noise()
+    fn, oracle_tags = tags_of()
+    want = objectives_oracle(sds, g, cs, fn)
+    results = {}
+    for use_graph in (False, True):
+        fn, ours_tags = tags_of(dev)
+        outs = imagen.sample(text_embeds=g["text_embeds"].to(dev), cond_scale=cs, use_tqdm=False, return_all_unet_outputs=True,
+                             noise_fn=fn, use_graph=use_graph)
+        assert ours_tags == oracle_tags
+        errs = [nerr(o, r) for o, r in zip(outs, want)]
+        record_parity(f"objectives_sample[{run}-{'graph' if use_graph else 'eager'}]", stage1=errs[0], stage2=errs[1])
+        assert len(outs) == 2 and max(errs) < 2e-2, errs   # the bar of test_sample_vs_reference_fixture
+        results[use_graph] = outs
+    for a, b in zip(results[False], results[True]):
+        assert torch.equal(a, b), "hipGraph replay must be bit-identical to eager launches"
+
+
 def test_time_table_matches_per_step_chain(monkeypatch):
     """The timestep-only conditioning of the image stages evaluated for all steps in one batched pass per request (engine.enable_time_table:
     a STEP_SLICE copy per step) against the same launches at the head of every step (IMAGEN_TIME_TABLE=0): same kernels on more rows."""

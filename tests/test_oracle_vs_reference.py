@@ -148,6 +148,20 @@ def test_step_level_posterior_math(objective, dyn, ref_sampler):
         assert u.shape == v.shape and torch.allclose(u, v, rtol=0, atol=1e-6)
 
 
+@pytest.mark.parametrize("objective", ["noise", "x_start", "v"])
+@pytest.mark.parametrize("dyn", [True, False])
+def test_oracle_ddpm_step_posterior_math(objective, dyn, ref_sampler):
+    """oracle.ddpm_step on every objective x thresholding (ip.py:2085-2109, 252-270) against the reference's p_mean_variance: with the
+    noise term zeroed the step returns the posterior mean, and its x0 is the thresholded x_start."""
+    x, out, t, tn = rc.posterior_inputs()
+    mean, _, _, x0 = ref_sampler[f"posterior/{objective}-{dyn}"]
+    got, got_x0 = so.ddpm_step(x, out, t, tn, torch.zeros_like(x), "cosine", dyn, 0.95, objective)
+    assert torch.allclose(got_x0, x0, rtol=0, atol=1e-6), (got_x0 - x0).abs().max()
+    assert torch.allclose(got, mean, rtol=0, atol=1e-6), (got - mean).abs().max()
+    if dyn:     # the fixture's thresholds do bite: the test could not pass with the static clamp
+        assert not torch.allclose(x0, so.predict_x0(x, out, *so.alpha_sigma(so.log_snr_cosine(t).view(-1, 1, 1, 1)), objective).clamp(-1, 1))
+
+
 def test_cross_embed_downsample_is_unbuildable_in_the_reference(ref_unet):
     """Why `Unet(cross_embed_downsample=True)` stays a NotImplementedError here: the reference's own constructor fails on it
     (`partial(CrossEmbedLayer, kernel_sizes=...)(dim_in, dim_out)`, ip.py:1315 / 1357 / 1366), so no model with that flag exists."""

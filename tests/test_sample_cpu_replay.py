@@ -465,3 +465,22 @@ def test_video_elucidated_inpainting_driver(cpu_backend):
         if "inpaint_images" in kw:
             m = keep[:, None].expand(-1, 3, -1, -1, -1)
             assert torch.allclose(outs[1][m], known[m], atol=1e-6)
+
+
+@pytest.mark.parametrize("run", ["cfg-off-on", "cfg-on-off"])
+def test_objectives_and_thresholding_sample_driver(cpu_backend, run):
+    """Imagen.sample with pred_objectives ('v', 'x_start'), dynamic_thresholding (False, True) at percentile 0.9, with and without CFG
+    per stage, against oracle.imagen_sample on the same memoised noise (the tags both ask for must agree)."""
+    from step_api_case import OBJECTIVE_CFG_RUNS, memo_noise, objectives_cascade, objectives_oracle
+
+    g = torch.load(os.path.join(GOLDEN, "sample_tiny_cascade.pt"), weights_only=False)
+    cs = OBJECTIVE_CFG_RUNS[run]
+    imagen, sds = objectives_cascade(g, "cpu")
+    tags_of = memo_noise()
+    fn, ours_tags = tags_of()
+    outs = imagen.sample(text_embeds=g["text_embeds"], cond_scale=cs, use_tqdm=False, return_all_unet_outputs=True, noise_fn=fn, device="cpu")
+    fn, oracle_tags = tags_of()
+    want = objectives_oracle(sds, g, cs, fn)
+    assert ours_tags == oracle_tags
+    errs = [nerr(o, r) for o, r in zip(outs, want)]
+    assert len(outs) == 2 and max(errs) < 2e-2, errs
