@@ -2,6 +2,7 @@
 // assembly, embeddings).  All kernels move 16 B per lane (8 fp16) with consecutive lanes on consecutive
 // addresses; reductions over a row use a power-of-two sub-group of the wave64 and __shfl_xor.
 #include <algorithm>
+#include <cstdint>
 #include <cstdlib>
 #include "common.h"
 #include "gca_device.h"
@@ -848,6 +849,11 @@ __global__ __launch_bounds__(256) void memset32_kernel(uint32_t* dst, uint32_t v
   if (i < count) dst[i] = value;
 }
 
+// 16-byte vector accesses: element strides / offsets in multiples of 8 fp16, pointers on 16-byte lines
+inline bool al8(long v) { return v % 8 == 0; }
+inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+constexpr long kIntMax = 2147483647L;
+
 int host_lpr(int groups) {
   int l = 1;
   while (l < groups && l < 64) l <<= 1;
@@ -991,6 +997,10 @@ int launch_step_slice(const ImagenStepSliceParams* p, hipStream_t s) {
 int launch_rowstat(const ImagenRowstatParams* p, hipStream_t s) {
   IMAGEN_CHECK(p->C1 % 8 == 0 && p->C2 % 8 == 0 && p->ld1 % 8 == 0, "rowstat: channels/stride must be multiples of 8");
   IMAGEN_CHECK(p->rows > 0 && p->rows_per_batch > 0, "rowstat: empty");
+  IMAGEN_CHECK(p->x1 && p->rs && p->C1 > 0 && (!p->x2 || p->C2 > 0) && p->mode >= 0 && p->mode <= 2 && (p->mode != 1 || p->mu),
+               "rowstat: null x1 / rs (mode 1: mu), no channels or mode %d", p->mode);
+  IMAGEN_CHECK(al8(p->bs1) && al16(p->x1) && (!p->x2 || (al8(p->ld2) && al8(p->bs2) && al16(p->x2))),
+               "rowstat: strides must be multiples of 8 and the rows 16-byte aligned (bs1=%d ld2=%d bs2=%d)", p->bs1, p->ld2, p->bs2);
   const int lpr = host_lpr((p->C1 + (p->x2 ? p->C2 : 0)) / 8);
   const int rpb = 256 / lpr;
   hipLaunchKernelGGL(rowstat_kernel, dim3((p->rows + rpb - 1) / rpb), dim3(256), 0, s, *p, lpr);
@@ -999,6 +1009,9 @@ int launch_rowstat(const ImagenRowstatParams* p, hipStream_t s) {
 
 int launch_gate_residual(const ImagenGateResidualParams* p, hipStream_t s) {
   IMAGEN_CHECK(p->C % 8 == 0, "gate_residual: C %% 8");
+  IMAGEN_CHECK(p->h && p->res && p->out && p->C > 0 && p->rows > 0 && p->rows_per_batch > 0, "gate_residual: null tensors / empty problem");
+  IMAGEN_CHECK(al8(p->ld_h) && al8(p->ld_res) && al8(p->ld_out) && al16(p->h) && al16(p->res) && al16(p->out) && (!p->gate || al16(p->gate)),
+               "gate_residual: row strides must be multiples of 8 and the rows 16-byte aligned (ld_h=%d ld_res=%d ld_out=%d)", p->ld_h, p->ld_res, p->ld_out);
   const int lpr = host_lpr(p->C / 8);
   const int rpb = 256 / lpr;
   hipLaunchKernelGGL(gate_residual_kernel, dim3((p->rows + rpb - 1) / rpb), dim3(256), 0, s, *p, lpr);
@@ -1007,6 +1020,12 @@ int launch_gate_residual(const ImagenGateResidualParams* p, hipStream_t s) {
 
 int launch_ln_residual(const ImagenLnResidualParams* p, hipStream_t s) {
   IMAGEN_CHECK(p->C % 8 == 0, "ln_residual: C %% 8");
+  IMAGEN_CHECK(p->y && p->g && p->out && p->C > 0 && p->rows > 0 && p->rows_per_batch > 0, "ln_residual: null tensors / empty problem");
+  IMAGEN_CHECK(!p->mu_out == !p->rs_out, "ln_residual: mu_out and rs_out come together");
+  IMAGEN_CHECK(al8(p->ld_y) && al8(p->bs_y) && al8(p->ld_out) && al8(p->bs_out) && al16(p->y) && al16(p->out) &&
+                   (!p->res || (al8(p->ld_res) && al8(p->bs_res) && al16(p->res))),
+               "ln_residual: strides must be multiples of 8 and the rows 16-byte aligned (ld_y=%d bs_y=%d ld_res=%d bs_res=%d ld_out=%d bs_out=%d)", p->ld_y,
+               p->bs_y, p->ld_res, p->bs_res, p->ld_out, p->bs_out);
   const int lpr = host_lpr(p->C / 8);
   const int rpb = 256 / lpr;
   hipLaunchKernelGGL(ln_residual_kernel, dim3((p->rows + rpb - 1) / rpb), dim3(256), 0, s, *p, lpr);
@@ -1014,13 +1033,32 @@ int launch_ln_residual(const ImagenLnResidualParams* p, hipStream_t s) {
 }
 
 int launch_qnorm(const ImagenQnormParams* p, hipStream_t s) {
+  IMAGEN_CHECK(p->q && p->q_scale && p->rows > 0 && p->heads > 0, "qnorm: null tensors / empty problem");
+  IMAGEN_CHECK(p->head_dim == 0 || p->head_dim == 32 || p->head_dim == 64, "qnorm: head_dim %d", p->head_dim);
+  IMAGEN_CHECK(al8(p->ld) && al16(p->q) && p->ld >= p->heads * (p->head_dim == 32 ? 32 : 64), "qnorm: row stride %d must be a multiple of 8 covering the %d heads, rows 16-byte aligned",
+               p->ld, p->heads);
+  IMAGEN_CHECK((long)p->rows * p->heads <= kIntMax - 64, "qnorm: rows * heads does not fit an int");
   const int items = p->rows * p->heads;
   hipLaunchKernelGGL(qnorm_kernel, dim3((items + 31) / 32), dim3(256), 0, s, *p);
   return imagen_hip_status("qnorm");
 }
 
+// (the jobs of a KV_PREP_MULTI launch live in device memory and are not read back by its launcher: ops.kv_prep_multi applies these checks to
+// each job on the host before it uploads them)
+static int check_kv_prep(const ImagenKvPrepParams* p) {
+  IMAGEN_CHECK(p->rows > 0 && p->B > 0 && p->heads > 0 && p->r0 >= 0, "kv_prep: empty");
+  IMAGEN_CHECK(p->k_src && p->v_src && p->k_scale && p->khat && p->vt, "kv_prep: null pointer");
+  IMAGEN_CHECK(p->head_dim == 0 || p->head_dim == 32 || p->head_dim == 64, "kv_prep: head_dim %d", p->head_dim);
+  IMAGEN_CHECK(al8(p->k_bs) && al8(p->k_hs) && al8(p->k_rs) && al16(p->khat), "kv_prep: K-hat strides must be multiples of 8, rows 16-byte aligned (%d %d %d)",
+               p->k_bs, p->k_hs, p->k_rs);
+  IMAGEN_CHECK(p->src_is_f32 || (al8(p->src_bs) && al8(p->src_rs) && al8(p->src_hs) && al16(p->k_src) && al16(p->v_src)),
+               "kv_prep: fp16 source strides / offsets must be multiples of 8 (%d %d %d)", p->src_bs, p->src_rs, p->src_hs);
+  IMAGEN_CHECK((long)p->B * p->heads <= 65535, "kv_prep: B * heads = %ld exceeds the grid", (long)p->B * p->heads);
+  return 0;
+}
+
 int launch_kv_prep(const ImagenKvPrepParams* p, hipStream_t s) {
-  IMAGEN_CHECK(p->rows > 0, "kv_prep: empty");
+  if (check_kv_prep(p) != 0) return -1;
   hipLaunchKernelGGL(kv_prep_kernel, dim3((p->rows + 31) / 32, p->B * p->heads), dim3(256), 0, s, *p);
   return imagen_hip_status("kv_prep");
 }
@@ -1084,12 +1122,16 @@ int launch_gca_tail(const ImagenGcaTailParams* p, hipStream_t s) {
 }
 
 int launch_time_embed(const ImagenTimeEmbedParams* p, hipStream_t s) {
+  IMAGEN_CHECK(p->freqs && p->w && p->bias && p->hid && (p->step_ptr ? p->coef != nullptr : p->times != nullptr), "time_embed: null pointer");
+  IMAGEN_CHECK(p->B > 0 && p->out_dim > 0 && p->half_dim >= 0 && p->ld_hid >= p->out_dim && (long)p->B * p->out_dim <= kIntMax - 256, "time_embed: bad shape");
   const int n = p->B * p->out_dim;
   hipLaunchKernelGGL(time_embed_kernel, dim3((n + 255) / 256), dim3(256), 0, s, *p);
   return imagen_hip_status("time_embed");
 }
 
 int launch_scale_shift(const ImagenScaleShiftParams* p, hipStream_t s) {
+  IMAGEN_CHECK(p->ss && p->gamma_s && p->idx_scale && p->idx_shift && p->pa && p->ps, "scale_shift: null pointer");
+  IMAGEN_CHECK(p->B > 0 && p->total_c > 0 && (long)p->B * p->total_c <= kIntMax - 256, "scale_shift: bad shape");
   const int n = p->B * p->total_c;
   hipLaunchKernelGGL(scale_shift_kernel, dim3((n + 255) / 256), dim3(256), 0, s, *p);
   return imagen_hip_status("scale_shift");
@@ -1105,6 +1147,10 @@ int launch_linear_f32(const ImagenLinearF32Params* p, hipStream_t s) {
 }
 
 int launch_pack_image(const ImagenPackImageParams* p, hipStream_t s) {
+  IMAGEN_CHECK(p->a && p->out && (p->Cb == 0 || p->b), "pack_image: null pointer");
+  IMAGEN_CHECK(p->B > 0 && p->Brep > 0 && p->H > 0 && p->W > 0 && p->Ca > 0 && p->Cb >= 0 && p->Cpad > 0 && p->Ca + p->Cb <= p->Cpad,
+               "pack_image: bad shape (Ca=%d Cb=%d Cpad=%d)", p->Ca, p->Cb, p->Cpad);
+  IMAGEN_CHECK((long)p->B * p->Brep * p->H * p->W <= kIntMax - 256, "pack_image: B * Brep * H * W does not fit an int");
   const int n = p->B * p->Brep * p->H * p->W;
   hipLaunchKernelGGL(pack_image_kernel, dim3((n + 255) / 256), dim3(256), 0, s, *p);
   return imagen_hip_status("pack_image");
@@ -1112,6 +1158,10 @@ int launch_pack_image(const ImagenPackImageParams* p, hipStream_t s) {
 
 int launch_rows_copy(const ImagenRowsCopyParams* p, hipStream_t s) {
   IMAGEN_CHECK(p->C % 8 == 0, "rows_copy: C %% 8");
+  IMAGEN_CHECK(p->src && p->dst && p->B > 0 && p->rows > 0 && p->C > 0, "rows_copy: null tensors / empty problem");
+  IMAGEN_CHECK(al8(p->src_bs) && al8(p->src_rs) && al8(p->dst_bs) && al8(p->dst_rs) && al16(p->src) && al16(p->dst),
+               "rows_copy: strides and offsets must be multiples of 8 (src %d %d, dst %d %d)", p->src_bs, p->src_rs, p->dst_bs, p->dst_rs);
+  IMAGEN_CHECK((long)p->B * p->rows * (p->C / 8) <= kIntMax - 256, "rows_copy: B * rows * C / 8 does not fit an int");
   const int n = p->B * p->rows * (p->C / 8);
   hipLaunchKernelGGL(rows_copy_kernel, dim3((n + 255) / 256), dim3(256), 0, s, *p);
   return imagen_hip_status("rows_copy");
@@ -1119,6 +1169,9 @@ int launch_rows_copy(const ImagenRowsCopyParams* p, hipStream_t s) {
 
 int launch_select_rows(const ImagenSelectRowsParams* p, hipStream_t s) {
   IMAGEN_CHECK(p->C % 8 == 0, "select_rows: C %% 8");
+  IMAGEN_CHECK(p->a && p->nul && p->src && p->keep && p->dst && p->R > 0 && p->L > 0 && p->C > 0, "select_rows: null tensors / empty problem");
+  IMAGEN_CHECK(al16(p->a) && al16(p->nul) && al16(p->dst), "select_rows: rows must be 16-byte aligned");
+  IMAGEN_CHECK((long)p->R * p->L * (p->C / 8) <= kIntMax - 256, "select_rows: R * L * C / 8 does not fit an int");
   const int n = p->R * p->L * (p->C / 8);
   hipLaunchKernelGGL(select_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, s, *p);
   return imagen_hip_status("select_rows");
@@ -1126,12 +1179,17 @@ int launch_select_rows(const ImagenSelectRowsParams* p, hipStream_t s) {
 
 int launch_mean_rows(const ImagenMeanRowsParams* p, hipStream_t s) {
   IMAGEN_CHECK(p->C % 8 == 0 && p->rows > 0, "mean_rows: bad shape");
+  IMAGEN_CHECK(p->x && p->out && p->B > 0 && p->C > 0, "mean_rows: null tensors / empty problem");
+  IMAGEN_CHECK(al8(p->bs_x) && al8(p->ld_x) && al8(p->ld_out) && al16(p->x) && al16(p->out), "mean_rows: strides must be multiples of 8 (bs_x=%d ld_x=%d ld_out=%d)",
+               p->bs_x, p->ld_x, p->ld_out);
+  IMAGEN_CHECK((long)p->B * (p->C / 8) <= kIntMax - 256, "mean_rows: B * C / 8 does not fit an int");
   const int n = p->B * (p->C / 8);
   hipLaunchKernelGGL(mean_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, s, *p);
   return imagen_hip_status("mean_rows");
 }
 
 int launch_memset32(const ImagenMemset32Params* p, hipStream_t s) {
+  IMAGEN_CHECK(p->dst && p->count > 0 && p->count <= kIntMax - 255, "memset32: null dst or a count (%d) outside [1, 2^31 - 256]", p->count);
   hipLaunchKernelGGL(memset32_kernel, dim3((p->count + 255) / 256), dim3(256), 0, s, reinterpret_cast<uint32_t*>(p->dst), p->value,
                      p->count);
   return imagen_hip_status("memset32");

@@ -770,6 +770,24 @@ def kv_prep(plan: Plan, k_src: torch.Tensor, v_src: torch.Tensor, k_scale: torch
     return p
 
 
+def _check_kv_job(p, i: int):
+    """launch_kv_prep's host checks (csrc/elementwise.hip) on job i of a multi launch, whose launcher sees the jobs in device memory only."""
+    def refuse(msg):
+        raise _abi.ImagenHipError(f"kv_prep_multi: job {i}: {msg}")
+    if not (p.rows > 0 and p.B > 0 and p.heads > 0 and p.r0 >= 0):
+        refuse("empty")
+    if not (p.k_src and p.v_src and p.k_scale and p.khat and p.vt):
+        refuse("null pointer")
+    if p.head_dim not in (0, 32, 64):
+        refuse(f"head_dim {p.head_dim}")
+    if p.k_bs % 8 or p.k_hs % 8 or p.k_rs % 8 or p.khat % 16:
+        refuse(f"K-hat strides must be multiples of 8, rows 16-byte aligned ({p.k_bs} {p.k_hs} {p.k_rs})")
+    if not p.src_is_f32 and (p.src_bs % 8 or p.src_rs % 8 or p.src_hs % 8 or p.k_src % 16 or p.v_src % 16):
+        refuse(f"fp16 source strides / offsets must be multiples of 8 ({p.src_bs} {p.src_rs} {p.src_hs})")
+    if p.B * p.heads > 65535:
+        refuse(f"B * heads = {p.B * p.heads} exceeds the grid")
+
+
 def kv_prep_multi(plan: Plan, batch: list, device, label: str = ""):
     """One launch for the jobs collected with kv_prep(batch=...): their parameter blocks are uploaded once, at plan build."""
     if not batch:
@@ -777,6 +795,8 @@ def kv_prep_multi(plan: Plan, batch: list, device, label: str = ""):
     if len(batch) == 1:
         plan.add(batch[0][0], label or "kv_prep", batch[0][1])
         return batch[0][0]
+    for i, (job, _) in enumerate(batch):
+        _check_kv_job(job, i)
     blob = b"".join(bytes(j) for j, _ in batch)
     jobs = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(device)
     p = STRUCTS["ImagenKvPrepMultiParams"]()

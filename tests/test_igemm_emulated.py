@@ -85,6 +85,20 @@ def test_emulated_rowchain_kernels():
 
 
 @pytest.mark.skipif(not os.path.exists(CLANG), reason="host clang of the ROCm toolchain not present")
+def test_emulated_elementwise_kernels():
+    """csrc/elementwise.hip — every glue kernel on every branch an engine call site selects, per row / per element against fp64, sentinels
+    around every output, the launchers' refusals — on the emulation in a child pytest (tests/test_elementwise_kernels_gpu.py; the whole file
+    takes seconds there; only the ACT_PREP launch above the grid cap is left to hardware)."""
+    env = dict(os.environ, IMAGEN_LIB_PATH=_lib(""), IMAGEN_EMUL_TESTS="1")
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_elementwise_kernels_gpu.py"), "-q", "-m", "gpu", "-p", "no:cacheprovider"],
+                       env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
+    out = r.stdout.decode()
+    assert r.returncode == 0 and "failed" not in out, out[-3000:]
+    passed = int(out.split(" passed")[0].split()[-1])
+    assert passed >= 409 and " 1 skipped" in out.splitlines()[-1], out[-800:]
+
+
+@pytest.mark.skipif(not os.path.exists(CLANG), reason="host clang of the ROCm toolchain not present")
 def test_emulated_kernels_follow_their_contract_launch_by_launch(tmp_path):
     """tools/op_audit.py on the emulation: every launch of README unet1's plans (a 16 x 16 image, the unconditional row) executed by the kernel
     sources and by the plan interpreter FROM IDENTICAL INPUTS.  Two fp32 computations of one quantity round to the same fp16 value almost
