@@ -18,6 +18,7 @@
 #include <type_traits>
 #include <utility>
 #include "common.h"
+#include "conv_families.h"
 #include "conv_epilogue.h"
 
 namespace {

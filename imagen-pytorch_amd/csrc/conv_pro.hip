@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <utility>
 #include "common.h"
+#include "conv_families.h"
 
 namespace {
 

@@ -17,6 +17,7 @@
 // Contract: ImagenIgemmParams with KH = KW = 1, stride 1, no prologue, plain NHWC output, C1 and C2 multiples of 32.
 #include <algorithm>
 #include "common.h"
+#include "conv_families.h"
 
 namespace {
 

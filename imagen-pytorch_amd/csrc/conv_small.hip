@@ -33,6 +33,7 @@
 // output tiles of 32 pixels as 4 x 8, 2 x 16 or 1 x 32 (partial tiles at the map's edge are masked).
 #include <cstdio>
 #include "common.h"
+#include "conv_families.h"
 #include "conv_epilogue.h"
 
 namespace {

@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include "common.h"
+#include "conv_families.h"
 #include "conv_epilogue.h"
 
 namespace {

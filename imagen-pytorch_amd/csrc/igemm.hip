@@ -18,6 +18,7 @@
 #include <type_traits>
 #include <utility>
 #include "common.h"
+#include "conv_families.h"
 
 namespace {
 
@@ -1014,50 +1015,39 @@ int launch_cfg(const ImagenIgemmParams& p, hipStream_t s) {
 
 }  // namespace
 
-// kernel family 2 (conv_dma.hip): tile cfg ids kNumCfgs ..   (family 1, the LDS-staged kernel with an in-kernel prologue, was retired in round 3)
-int imagen_conv_dma_num_configs();
-int imagen_conv_dma_config_info(int idx, int* tile_pixels, int* tile_cout, int* kgroups);
-long imagen_conv_dma_lds_bytes(int idx, int KH, int KW, int TH, int TW);
-int imagen_conv_dma_ring(int idx);
-int launch_conv_dma(const ImagenIgemmParams* p, int idx, hipStream_t s);
-static inline int cfg_base_dma() { return kNumCfgs; }
-// kernel family 3 (conv_stream.hip): tile cfg ids behind family 2's
-int imagen_conv_stream_num_configs();
-int imagen_conv_stream_config_info(int idx, int* tile_pixels, int* tile_cout, int* kgroups);
-long imagen_conv_stream_lds_bytes(int idx, int KH, int KW, int TH, int TW);
-int launch_conv_stream(const ImagenIgemmParams* p, int idx, hipStream_t s);
-static inline int cfg_base_stream() { return cfg_base_dma() + imagen_conv_dma_num_configs(); }
-// kernel family 4 (conv_pw.hip): the streaming pointwise convolution, tile cfg ids behind family 3's
-int imagen_conv_pw_num_configs();
-int imagen_conv_pw_config_info(int idx, int* tile_pixels, int* tile_cout, int* kchunks);
-long imagen_conv_pw_lds_bytes(int idx, int KH, int KW, int TH, int TW);
-int launch_conv_pw(const ImagenIgemmParams* p, int idx, hipStream_t s);
-static inline int cfg_base_pw() { return cfg_base_stream() + imagen_conv_stream_num_configs(); }
-// kernel family 5 (conv_big.hip): the big-tile all-DMA 3x3 convolution (256 / 128 px x 128 couts, 64 x 64 per wave), tile cfg ids behind family 4's
-int imagen_conv_big_num_configs();
-int imagen_conv_big_config_info(int idx, int* tile_pixels, int* tile_cout, int* kgroups);
-long imagen_conv_big_lds_bytes(int idx, int KH, int KW, int TH, int TW);
-int launch_conv_big(const ImagenIgemmParams* p, int idx, hipStream_t s);
-static inline int cfg_base_big() { return cfg_base_pw() + imagen_conv_pw_num_configs(); }
-// kernel family 6 (conv_pro.hip): the streaming 3x3 convolution with the Block prologue on register-staged rows (C_out = 32 from 32 | 32 + 32 channels)
-int imagen_conv_pro_num_configs();
-int imagen_conv_pro_config_info(int idx, int* tile_pixels, int* tile_cout, int* kgroups);
-long imagen_conv_pro_lds_bytes(int idx, int KH, int KW, int TH, int TW);
-int launch_conv_pro(const ImagenIgemmParams* p, int idx, hipStream_t s);
-static inline int cfg_base_pro() { return cfg_base_big() + imagen_conv_big_num_configs(); }
-// kernel family 7 (conv_gemm.hip): the tiled pointwise GEMM of the token / small-map layers (1x1, 128-row x 128-cout workgroup tiles, K loop)
-int imagen_conv_gemm_num_configs();
-int imagen_conv_gemm_config_info(int idx, int* tile_pixels, int* tile_cout, int* kgroups);
-long imagen_conv_gemm_lds_bytes(int idx, int KH, int KW, int TH, int TW);
-int launch_conv_gemm(const ImagenIgemmParams* p, int idx, hipStream_t s);
-static inline int cfg_base_gemm() { return cfg_base_pro() + imagen_conv_pro_num_configs(); }
-// kernel family 8 (conv_small.hip): the 3x3 convolutions of the small maps (32 pixels x 32 | 64 | 128 couts per workgroup, K split over its waves)
-int imagen_conv_small_num_configs();
-int imagen_conv_small_config_info(int idx, int* tile_pixels, int* tile_cout, int* kgroups);
-long imagen_conv_small_lds_bytes(int idx, int KH, int KW, int TH, int TW);
-int launch_conv_small(const ImagenIgemmParams* p, int idx, hipStream_t s);
-static inline int cfg_base_small() { return cfg_base_gemm() + imagen_conv_gemm_num_configs(); }
-static inline int cfg_end() { return cfg_base_small() + imagen_conv_small_num_configs(); }
+// The other kernel families, in tile cfg id order: family 0 owns the ids below kNumCfgs, each of these the next num() ids.  The ids are visible
+// to the planner (imagen_igemm_config_info / _config_family rows): a new family goes at the END.
+static const ConvFamily kFamilies[] = {
+    {2, imagen_conv_dma_num_configs, imagen_conv_dma_config_info, imagen_conv_dma_lds_bytes, launch_conv_dma, 3, 3, imagen_conv_dma_ring},
+    {3, imagen_conv_stream_num_configs, imagen_conv_stream_config_info, imagen_conv_stream_lds_bytes, launch_conv_stream, 3, 3, nullptr},
+    {4, imagen_conv_pw_num_configs, imagen_conv_pw_config_info, imagen_conv_pw_lds_bytes, launch_conv_pw, 1, 1, nullptr},
+    {5, imagen_conv_big_num_configs, imagen_conv_big_config_info, imagen_conv_big_lds_bytes, launch_conv_big, 3, 3, nullptr},
+    {6, imagen_conv_pro_num_configs, imagen_conv_pro_config_info, imagen_conv_pro_lds_bytes, launch_conv_pro, 3, 3, nullptr},
+    {7, imagen_conv_gemm_num_configs, imagen_conv_gemm_config_info, imagen_conv_gemm_lds_bytes, launch_conv_gemm, 1, 1, nullptr},
+    {8, imagen_conv_small_num_configs, imagen_conv_small_config_info, imagen_conv_small_lds_bytes, launch_conv_small, 3, 3, nullptr},   // (3, 3 although the kernel also runs 1x1: imagen_igemm_stage_slots() has always answered 0 for those)
+};
+
+struct CfgRef {
+  const ConvFamily* fam;   // nullptr: family 0 (or a negative id)
+  int idx;                 // the family's own index; at or past fam->num() for an id behind the last one (every family's functions range-check it)
+};
+
+static CfgRef cfg_ref(int cfg) {
+  CfgRef r = {nullptr, cfg};
+  int base = kNumCfgs;
+  for (const ConvFamily& f : kFamilies) {
+    if (cfg < base) break;
+    r = {&f, cfg - base};
+    base += f.num();
+  }
+  return r;
+}
+
+static int cfg_end() {
+  int n = kNumCfgs;
+  for (const ConvFamily& f : kFamilies) n += f.num();
+  return n;
+}
 
 int launch_igemm(const ImagenIgemmParams* pp, hipStream_t s) {
   const ImagenIgemmParams& p = *pp;
@@ -1068,13 +1058,8 @@ int launch_igemm(const ImagenIgemmParams* pp, hipStream_t s) {
   IMAGEN_CHECK(!p.pad_x1 || p.cfg < kNumCfgs, "igemm: pad_x1 (an x padding of its own) is implemented by kernel family 0 only (cfg %d)", p.cfg);
   IMAGEN_CHECK(p.pad_x1 >= 0, "igemm: pad_x1 %d", p.pad_x1);
   IMAGEN_CHECK(!p.gca_part || p.cfg >= kNumCfgs, "igemm: gca_part is implemented by the kernel families 2, 5, 7 and 8 only (cfg %d)", p.cfg);
-  if (p.cfg >= cfg_base_small()) return launch_conv_small(pp, p.cfg - cfg_base_small(), s);
-  if (p.cfg >= cfg_base_gemm()) return launch_conv_gemm(pp, p.cfg - cfg_base_gemm(), s);
-  if (p.cfg >= cfg_base_pro()) return launch_conv_pro(pp, p.cfg - cfg_base_pro(), s);
-  if (p.cfg >= cfg_base_big()) return launch_conv_big(pp, p.cfg - cfg_base_big(), s);
-  if (p.cfg >= cfg_base_pw()) return launch_conv_pw(pp, p.cfg - cfg_base_pw(), s);
-  if (p.cfg >= cfg_base_stream()) return launch_conv_stream(pp, p.cfg - cfg_base_stream(), s);
-  if (p.cfg >= cfg_base_dma()) return launch_conv_dma(pp, p.cfg - cfg_base_dma(), s);
+  const CfgRef r = cfg_ref(p.cfg);
+  if (r.fam) return r.fam->launch(pp, r.idx, s);
   switch (p.cfg) {
     case 0: return launch_cfg<2, 1, 4, 1, 4>(p, s);
     case 1: return launch_cfg<4, 1, 1, 4, 4>(p, s);
@@ -1098,27 +1083,21 @@ int launch_igemm(const ImagenIgemmParams* pp, hipStream_t s) {
 
 extern "C" int imagen_igemm_num_configs(void) { return cfg_end(); }
 
-extern "C" int imagen_igemm_config_family(int cfg) {   // 0: wave-specialised persistent kernel (this file), 2: all-DMA kernel (conv_dma.hip), 3: streaming kernel (conv_stream.hip)
+// the kernel family of a tile cfg id: 0 the wave-specialised persistent kernel (this file), 2 .. 8 ConvFamily::id (conv_families.h); -1: no such id
+extern "C" int imagen_igemm_config_family(int cfg) {
   if (cfg < 0 || cfg >= imagen_igemm_num_configs()) return -1;
-  if (cfg >= cfg_base_small()) return 8; // 8: small-map 3x3 convolution with the K split over the waves of a workgroup (conv_small.hip)
-  if (cfg >= cfg_base_gemm()) return 7;  // 7: tiled pointwise GEMM (conv_gemm.hip)
-  if (cfg >= cfg_base_pro()) return 6;   // 6: streaming kernel with the prologue on register-staged rows (conv_pro.hip)
-  if (cfg >= cfg_base_big()) return 5;   // 5: big-tile all-DMA kernel (conv_big.hip)
-  return cfg >= cfg_base_pw() ? 4 : cfg >= cfg_base_stream() ? 3 : cfg >= cfg_base_dma() ? 2 : 0;   // 4: streaming pointwise kernel (conv_pw.hip)
+  const CfgRef r = cfg_ref(cfg);
+  return r.fam ? r.fam->id : 0;
 }
 
 extern "C" int imagen_igemm_config_ring(int cfg) {   // weight look-ahead ring depth in stages (family 2; 0 elsewhere)
-  return (cfg >= cfg_base_dma() && cfg < cfg_base_stream()) ? imagen_conv_dma_ring(cfg - cfg_base_dma()) : 0;
+  const CfgRef r = cfg_ref(cfg);
+  return r.fam && r.fam->ring ? r.fam->ring(r.idx) : 0;
 }
 
 extern "C" int imagen_igemm_config_info(int cfg, int* tile_pixels, int* tile_cout, int* kgroups) {
-  if (cfg >= cfg_base_small()) return imagen_conv_small_config_info(cfg - cfg_base_small(), tile_pixels, tile_cout, kgroups);
-  if (cfg >= cfg_base_gemm()) return imagen_conv_gemm_config_info(cfg - cfg_base_gemm(), tile_pixels, tile_cout, kgroups);
-  if (cfg >= cfg_base_pro()) return imagen_conv_pro_config_info(cfg - cfg_base_pro(), tile_pixels, tile_cout, kgroups);
-  if (cfg >= cfg_base_big()) return imagen_conv_big_config_info(cfg - cfg_base_big(), tile_pixels, tile_cout, kgroups);
-  if (cfg >= cfg_base_pw()) return imagen_conv_pw_config_info(cfg - cfg_base_pw(), tile_pixels, tile_cout, kgroups);   // (family 4: kgroups = 32-channel input chunks)
-  if (cfg >= cfg_base_stream()) return imagen_conv_stream_config_info(cfg - cfg_base_stream(), tile_pixels, tile_cout, kgroups);
-  if (cfg >= cfg_base_dma()) return imagen_conv_dma_config_info(cfg - cfg_base_dma(), tile_pixels, tile_cout, kgroups);
+  const CfgRef r = cfg_ref(cfg);
+  if (r.fam) return r.fam->info(r.idx, tile_pixels, tile_cout, kgroups);
   if (cfg < 0 || cfg >= kNumCfgs) return -1;
   const TileCfg& c = kCfgs[cfg];
   if (tile_pixels) *tile_pixels = 32 * c.MI * c.WM;
@@ -1136,12 +1115,8 @@ static constexpr int ksc_of(int G, int ks) {   // the launch_cfg dispatch, as a 
 }
 
 extern "C" int imagen_igemm_stage_slots(int cfg, int KH, int KW) {
-  if (cfg >= cfg_base_small()) return (KH == 3 && KW == 3) ? 1 << 20 : 0;
-  if (cfg >= cfg_base_gemm()) return (KH == 1 && KW == 1) ? 1 << 20 : 0;
-  if (cfg >= cfg_base_pro()) return (KH == 3 && KW == 3) ? 1 << 20 : 0;
-  if (cfg >= cfg_base_big()) return (KH == 3 && KW == 3) ? 1 << 20 : 0;
-  if (cfg >= cfg_base_pw()) return (KH == 1 && KW == 1) ? 1 << 20 : 0;
-  if (cfg >= cfg_base_dma()) return (KH == 3 && KW == 3) ? 1 << 20 : 0;   // (no register staging: the tile shape is fixed per cfg; families 2 and 3)
+  const CfgRef r = cfg_ref(cfg);
+  if (r.fam) return (KH == r.fam->kh && KW == r.fam->kw) ? 1 << 20 : 0;   // (no register staging: the tile shape is fixed per cfg)
   if (cfg < 0 || cfg >= kNumCfgs || KH < 1 || KW < 1) return -1;
   const TileCfg& c = kCfgs[cfg];
   return stage_slots(32 * c.MI * c.WM, c.G, ksc_of(c.G, (KH * KW * c.G + 1) / 2));
@@ -1149,13 +1124,8 @@ extern "C" int imagen_igemm_stage_slots(int cfg, int KH, int KW) {
 
 // dynamic LDS bytes of a launch of `cfg` with a KH x KW kernel (at `stride`) and a TH x TW output tile; -1: the combination is not launchable
 extern "C" long imagen_igemm_lds_bytes(int cfg, int KH, int KW, int stride, int TH, int TW) {
-  if (cfg >= cfg_base_small()) return stride == 1 ? imagen_conv_small_lds_bytes(cfg - cfg_base_small(), KH, KW, TH, TW) : -1;
-  if (cfg >= cfg_base_gemm()) return stride == 1 ? imagen_conv_gemm_lds_bytes(cfg - cfg_base_gemm(), KH, KW, TH, TW) : -1;
-  if (cfg >= cfg_base_pro()) return stride == 1 ? imagen_conv_pro_lds_bytes(cfg - cfg_base_pro(), KH, KW, TH, TW) : -1;
-  if (cfg >= cfg_base_big()) return stride == 1 ? imagen_conv_big_lds_bytes(cfg - cfg_base_big(), KH, KW, TH, TW) : -1;
-  if (cfg >= cfg_base_pw()) return stride == 1 ? imagen_conv_pw_lds_bytes(cfg - cfg_base_pw(), KH, KW, TH, TW) : -1;
-  if (cfg >= cfg_base_stream()) return stride == 1 ? imagen_conv_stream_lds_bytes(cfg - cfg_base_stream(), KH, KW, TH, TW) : -1;
-  if (cfg >= cfg_base_dma()) return stride == 1 ? imagen_conv_dma_lds_bytes(cfg - cfg_base_dma(), KH, KW, TH, TW) : -1;
+  const CfgRef r = cfg_ref(cfg);
+  if (r.fam) return stride == 1 ? r.fam->lds(r.idx, KH, KW, TH, TW) : -1;
   if (cfg < 0 || KH < 1 || KW < 1 || TH < 1 || TW < 1) return -1;
   const TileCfg& c = kCfgs[cfg];
   if (TH * TW != 32 * c.MI * c.WM) return -1;

@@ -8,8 +8,9 @@ from __future__ import annotations
 
 import ctypes
 import math
+import os
 from dataclasses import dataclass
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -25,9 +26,11 @@ _CFG_TABLE = None
 
 
 def cfg_table():
-    """[(tile pixels, tile couts, G, family)] per tile cfg id; family 0 = wave-specialised persistent kernel (csrc/igemm.hip),
-    2 = all-DMA kernel (csrc/conv_dma.hip: prologue-free 3x3, stride 1), 3 = streaming kernel (csrc/conv_stream.hip), 4 = streaming pointwise
-    kernel (conv_pw.hip), 5 = big-tile all-DMA kernel (conv_big.hip), 6 = streaming kernel with the prologue on register-staged rows (conv_pro.hip)."""
+    """[(tile pixels, tile couts, G, family)] per tile cfg id.  Families: 0 = wave-specialised persistent kernel (csrc/igemm.hip),
+    2 = all-DMA kernel (conv_dma.hip: prologue-free 3x3, stride 1), 3 = streaming kernel (conv_stream.hip), 4 = streaming pointwise kernel
+    (conv_pw.hip; its G column counts 32-channel input chunks), 5 = big-tile all-DMA kernel (conv_big.hip), 6 = streaming kernel with the prologue on
+    register-staged rows (conv_pro.hip), 7 = tiled pointwise GEMM (conv_gemm.hip), 8 = small-map kernel with the K split over a workgroup's waves
+    (conv_small.hip)."""
     global _CFG_TABLE
     if _CFG_TABLE is None:
         lib = load_library()
@@ -255,8 +258,6 @@ def pack_weight(w: torch.Tensor, bias: Optional[torch.Tensor], device, in_scale:
 
 # ------------------------------------------------------------------------------------------------ igemm
 
-import os as _os
-
 MAX_LDS_BYTES = 160 * 1024
 
 
@@ -289,7 +290,7 @@ CONV_STREAM = 1    # (module constant) the streaming kernel family (conv_stream.
 STREAM_MIN_TILES = 512   # ... of launches with at least this many 16x16 tiles (persistent workgroups need a few tiles each)
 
 
-CONV_PRO = int(_os.environ.get("IMAGEN_CONV_PRO", "1"))             # A/B switch: conv_pro.hip for the 32-channel 3x3 convs that need the Block prologue (2: the raw ones too)
+CONV_PRO = int(os.environ.get("IMAGEN_CONV_PRO", "1"))             # A/B switch: conv_pro.hip for the 32-channel 3x3 convs that need the Block prologue (2: the raw ones too)
 PRO_MIN_TILES = 1024     # ... of launches with at least this many 8x16 tiles (two per resident workgroup)
 
 
@@ -297,7 +298,7 @@ CONV_PW = 1        # (module constant) the streaming pointwise family (conv_pw.h
 PW_MIN_TILES = 512     # ... of at least this many tiles, i.e. two per CU (the big maps; below, the launch is latency-bound either way)
 
 
-CONV_GEMM = int(_os.environ.get("IMAGEN_CONV_GEMM", "1"))             # A/B switch: the tiled pointwise GEMM (conv_gemm.hip) for the deep 1x1 layers
+CONV_GEMM = int(os.environ.get("IMAGEN_CONV_GEMM", "1"))             # A/B switch: the tiled pointwise GEMM (conv_gemm.hip) for the deep 1x1 layers
 GEMM_MIN_K = 128         # ... with at least this many input channels (below: family 4 / the wave-specialised kernel)
 GEMM_MAX_K = 2048        # ... and at most this many (the launcher's limit, conv_gemm.hip: the prologue affine table in LDS; a split-precision
                          # weight counts its input channels twice) — wider layers stay on the wave-specialised kernel
@@ -333,7 +334,7 @@ def pw_cfg(kchunks: int, Cout: int) -> Optional[int]:
     return best
 
 
-CONV_SMALL = int(_os.environ.get("IMAGEN_CONV_SMALL", "2"))   # A/B switch: conv_small.hip (family 8) for the 3x3 convs of the small maps (2: their 1x1 res_conv / upsample GEMMs too)
+CONV_SMALL = int(os.environ.get("IMAGEN_CONV_SMALL", "2"))   # A/B switch: conv_small.hip (family 8) for the 3x3 convs of the small maps (2: their 1x1 res_conv / upsample GEMMs too)
 SMALL_MAX_ROWS = 4096   # ... of at most this many output pixels per launch (16 images of 8^2 / 16^2; call H: with the 32^2 maps, 16384, unet2 loses 1.3 ms per step)
 SMALL_MAX_STREAM_MB = 64    # ... whose pixel tiles together stream at most this much weight data out of L2 (every 32-pixel tile reads all of its slab: README unet1's
                             # layers 38 - 57 MB; C2's 512 -> 512 @16^2 and 1024 -> 1024 @8^2 604 MB — 75 / 86 us against 33 / 48 on the wave-specialised kernel, round 5 call J;
@@ -456,32 +457,32 @@ def pick_cfg(G: int, Cout: int, OH: int, OW: int, B: int, KH: int = 1, KW: int =
         if got is not None:
             return got
     assert family != 2, "no all-DMA tile configuration for this layer"
-    for fam in ([family] if family is not None else [0]):
-        avail = {}
-        for i, (tp, bn, g, f) in enumerate(tab):
-            if g == G and f == fam and (tp, bn) not in avail:
-                sh = launchable_shapes(i, OH, OW, KH, KW, stride)
-                if sh:
-                    avail[(tp, bn)] = (i, sh[0])
+    fam = 0 if family is None else family
+    avail = {}
+    for i, (tp, bn, g, f) in enumerate(tab):
+        if g == G and f == fam and (tp, bn) not in avail:
+            sh = launchable_shapes(i, OH, OW, KH, KW, stride)
+            if sh:
+                avail[(tp, bn)] = (i, sh[0])
 
-        def wgs(key):
-            return B * avail[key][1][0] * math.ceil(Cout / key[1]) if key in avail else 0
+    def wgs(key):
+        return B * avail[key][1][0] * math.ceil(Cout / key[1]) if key in avail else 0
 
-        if Cout <= 32:
-            order = [(256, 32)] if wgs((256, 32)) >= 1024 else []
-            order += [(128, 32), (256, 32), (64, 64), (64, 128)]
-        elif Cout <= 64:
-            order = [(256, 64)] if wgs((256, 64)) >= 1024 and KH * KW > 1 else []
-            order += [(64, 64), (64, 128), (128, 32), (256, 32)]
-        else:
-            order = [(64, 128)] if wgs((64, 128)) >= 192 or (full_cout and Cout <= 128) else []
-            order += [(64, 64), (64, 128), (128, 32), (256, 32)]
-        if fam == 0:
-            order += [(128, 128), (256, 64)]
-        for key in order:
-            if key in avail:
-                i, (_, _, th, tw) = avail[key]
-                return i, th, tw
+    if Cout <= 32:
+        order = [(256, 32)] if wgs((256, 32)) >= 1024 else []
+        order += [(128, 32), (256, 32), (64, 64), (64, 128)]
+    elif Cout <= 64:
+        order = [(256, 64)] if wgs((256, 64)) >= 1024 and KH * KW > 1 else []
+        order += [(64, 64), (64, 128), (128, 32), (256, 32)]
+    else:
+        order = [(64, 128)] if wgs((64, 128)) >= 192 or (full_cout and Cout <= 128) else []
+        order += [(64, 64), (64, 128), (128, 32), (256, 32)]
+    if fam == 0:
+        order += [(128, 128), (256, 64)]
+    for key in order:
+        if key in avail:
+            i, (_, _, th, tw) = avail[key]
+            return i, th, tw
     raise ValueError(f"no igemm tile configuration for G={G} Cout={Cout} {OH}x{OW} k{KH}x{KW} s{stride}")
 
 
@@ -500,15 +501,168 @@ def _twice(plan: "Plan", v: Optional[torch.Tensor], C: int, n: int) -> Optional[
     return hit[1]
 
 
+class Align(NamedTuple):
+    """The 16-byte facts of one fp16 NHWC operand (8 elements): pixel pitch, image pitch, base address."""
+    ld8: bool; bs8: bool; p16: bool   # noqa: E702
+    strides8 = property(lambda a: a.ld8 and a.bs8)
+
+
+def _align(a) -> Optional[Align]:
+    return Align(a.ld % 8 == 0, a.bs % 8 == 0, a.ptr % 16 == 0) if isinstance(a, Act) else None
+
+
+@dataclass(frozen=True)
+class ConvReq:
+    """One conv / GEMM launch request as the routing sees it: what a family gate may ask about, computed once by igemm().  The sub-predicates
+    the gates share are defined once, below the fields; a term only one family has stays in that family's function."""
+    B: int; H: int; W: int; OH: int; OW: int; KH: int; KW: int; stride: int; pad: int   # noqa: E702  geometry
+    C1: int; C2: int; Cin_pad: int; Cout: int; Cout_pad: int; G: int; split: bool       # noqa: E702  channels of x1 / x2 and of the packed weight
+    mu: bool; rs: bool; pa: bool; ps: bool; ssq_a: bool; ssq_b: bool                    # noqa: E702  prologue: which operands are given
+    pstride: int; act_in: int                                                           # noqa: E702
+    act_out: int; out_mode: int; gate: bool                                             # noqa: E702  epilogue
+    want_ssq: bool; want_post: bool; gca: bool                                          # noqa: E702  what it is asked for (gca: at all; want_gca: where it can be given)
+    x1: Align; x2: Optional[Align]; y: Optional[Align]; addend: Optional[Align]; res: Optional[Align]   # noqa: E702  None: no such operand (y: not an NHWC Act)
+
+    rows = property(lambda r: r.B * r.OH * r.OW)
+    is_3x3 = property(lambda r: r.KH == 3 and r.KW == 3 and r.stride == 1 and r.pad == 1 and r.G == 4)   # the "same" 3x3 convs over 32-channel chunks
+    is_1x1 = property(lambda r: r.KH == 1 and r.KW == 1 and r.stride == 1 and r.pad == 0)
+    chunks32 = property(lambda r: r.C1 % 32 == 0 and r.C2 % 32 == 0 and r.Cin_pad == r.C1 + r.C2)   # whole 32-channel chunks that fill the weight's input channels
+    ld_aligned = property(lambda r: r.x1.ld8 and (r.x2 is None or r.x2.ld8))                          # every input pixel starts on 16 bytes
+    x_aligned = property(lambda r: r.ld_aligned and r.x1.bs8 and (r.x2 is None or r.x2.bs8))          # ... and every input image too
+    no_pro = property(lambda r: not (r.mu or r.rs or r.pa or r.ps or r.ssq_a) and r.act_in == ACT_NONE)   # raw inputs
+    # the Block prologue on the producers' sums of squares: ChanRMSNorm -> per-channel affine (-> SiLU)
+    ssq_pro = property(lambda r: not (r.mu or r.rs) and r.pa and r.ssq_a and r.act_in in (ACT_NONE, ACT_SILU))
+    stats_ok = property(lambda r: not r.mu or r.rs)                                                   # explicit statistics come as rs alone or as (mu, rs)
+    plain_ep = property(lambda r: r.act_out == ACT_NONE and r.out_mode == OUT_NHWC and r.addend is None and r.res is None)   # bias + NHWC store
+    cout_vec4 = property(lambda r: r.out_mode == OUT_NCHW_F32 or r.Cout % 4 == 0)                     # the fp16 epilogues store four channels at a time
+    want_gca = property(lambda r: r.gca and r.plain_ep and not r.want_post)
+    full_cout = property(lambda r: (r.want_ssq or r.want_post or r.want_gca) and r.out_mode == OUT_NHWC)   # the epilogue needs all channels of a pixel in one tile
+    # the GlobalContext partials are to come out of this launch's epilogue (16x16 tiles): such a layer goes to family 2, the persistent streaming
+    # kernels measured slower with them (round 4 call F)
+    gca_from_epilogue = property(lambda r: r.want_gca and r.tiles(16, 16) <= GCA_EPILOGUE_MAX_TILES)
+
+    def tiles(self, th: int, tw: int) -> int:
+        return self.B * math.ceil(self.OH / th) * math.ceil(self.OW / tw)
+
+
+def _route_small(r: ConvReq):
+    """Family 8: the 3x3 convs (and, CONV_SMALL >= 2, the 1x1 res_conv / upsample GEMMs) of the small maps, any prologue of the contract
+    (statistics / affine / SiLU), any epilogue; the all-cout epilogues (ssq_out / post / GlobalContext partials) where a 32 | 64 | 128-cout
+    tile covers Cout."""
+    small_1x1 = r.is_1x1 and r.G >= 2 and r.OH > 1 and CONV_SMALL >= 2   # (spatial maps only: the token linears keep their kernels)
+    if not (CONV_SMALL and (r.is_3x3 or small_1x1) and r.rows <= SMALL_MAX_ROWS):
+        return None
+    tile = small_tile(r.OH, r.OW)
+    sc = small_cfg(r.Cout, r.full_cout and r.Cout <= 128)   # (wider layers: the 32-cout tile, statistics / post left to the caller's fallback as on family 0)
+    if tile is None or sc is None:
+        return None
+    # launch_conv_small's own predicates (a shape it refuses falls through to the older families), then the weight-stream bound
+    ok = (r.C1 % 8 == 0 and r.C2 % 8 == 0 and r.C1 + r.C2 == r.Cin_pad and r.Cin_pad % 32 == 0   # (8-channel, not 32-channel inputs: not chunks32)
+          and r.x_aligned and r.x1.p16 and (r.x2 is None or r.x2.p16)
+          and r.act_in in (ACT_NONE, ACT_SILU) and r.stats_ok and (r.pstride == 0 or r.pstride >= r.Cin_pad)
+          and r.cout_vec4 and (r.out_mode != OUT_PIXEL_SHUFFLE or r.Cout % 16 == 0)
+          and not (r.addend is not None and (r.res is not None or not r.gate))
+          and small_lds_bytes(tile[0], tile[1], r.Cin_pad, cfg_table()[sc][1]) <= MAX_LDS_BYTES
+          and (r.rows // 32) * r.Cout_pad * r.Cin_pad * 2 * r.KH * r.KW <= SMALL_MAX_STREAM_MB << 20)
+    return (sc, tile[0], tile[1]) if ok else None
+
+
+def _route_pro(r: ConvReq):
+    """Family 6: exactly 32 output channels from 32 | 32 + 32 input channels, or 64 from two or three 32-channel chunks (64 | 64 + 32 | 32 + 32):
+    the ssq-statistics SiLU prologue on register-staged rows (CONV_PRO = 2: raw inputs too), plain / post (/ ssq_out, 32 couts) epilogue."""
+    if not (CONV_PRO and r.is_3x3 and pro_cfg(r.Cout) is not None):
+        return None
+    ssq_silu = r.ssq_pro and r.act_in == ACT_SILU and (r.x2 is None) == (not r.ssq_b)   # (stricter than family 3's: SiLU, and a statistic per input)
+    nch = (r.C1 + r.C2) // 32
+    chunks_ok = r.chunks32 and ((r.Cout == 32 and nch in (1, 2) and r.C1 == 32) or (r.Cout == 64 and nch in (2, 3)))
+    ok = (chunks_ok and r.x_aligned and (ssq_silu or (r.no_pro and CONV_PRO >= 2)) and not r.gca_from_epilogue
+          and (r.Cout == 32 or r.want_post or not r.want_ssq) and r.tiles(8, 16) >= PRO_MIN_TILES and r.plain_ep
+          and r.y is not None and r.y.strides8 and not r.split)
+    return (pro_cfg(r.Cout), 8, 16) if ok else None
+
+
+def _route_stream(r: ConvReq):
+    """Family 3, the streaming family: C_out <= 32 from one or two 32-channel inputs, raw or with the ssq-statistics Block prologue."""
+    if not (CONV_STREAM and r.is_3x3):
+        return None
+    ok = (r.Cout <= 32 and r.chunks32 and r.C1 == 32 and r.C2 in (0, 32) and r.ld_aligned   # (the pixel pitch only, where families 6 - 8 also ask for the image pitch)
+          and (r.no_pro or r.ssq_pro) and not r.gca_from_epilogue and r.tiles(16, 16) >= STREAM_MIN_TILES and stream_cfg() is not None)
+    return (stream_cfg(), 16, 16) if ok else None
+
+
+def _route_pw(r: ConvReq):
+    """Family 4, the streaming pointwise family: the res_conv GEMMs of the large maps (raw inputs in 32-channel chunks, <= 64 output channels,
+    bias + gate * addend | residual epilogue)."""
+    if not (CONV_PW and r.is_1x1 and r.out_mode == OUT_NHWC):
+        return None
+    ok = (r.no_pro and r.act_out == ACT_NONE and not r.want_post and not r.gca   # (gca given at all, not want_gca: an addend / residual launch that asks for partials stays out)
+          and r.chunks32 and r.Cout % 8 == 0 and r.ld_aligned
+          and (r.addend is None or r.addend.strides8) and (r.res is None or r.res.strides8) and r.y is not None and r.y.strides8)
+    pc = pw_cfg((r.C1 + r.C2) // 32, r.Cout) if ok else None
+    if pc is None:
+        return None
+    tp = cfg_table()[pc][0]
+    if r.B * math.ceil(r.OH * r.OW / tp) < PW_MIN_TILES:
+        return None
+    return pc, tp // min(r.OW, tp), min(r.OW, tp)
+
+
+def _route_gemm(r: ConvReq):
+    """Family 7, the tiled pointwise GEMM: the token / small-map 1x1 layers too deep for family 4's register-resident weights — raw rows
+    or the LayerNorm prologue (mu / rs statistics, per-channel affine), every epilogue; 128-row x 128-cout workgroup tiles."""
+    if not (CONV_GEMM and r.is_1x1 and gemm_cfg() is not None):
+        return None
+    ln_pro = not (r.ssq_a or r.ssq_b) and r.act_in == ACT_NONE and r.stats_ok
+    tiles = r.B * math.ceil(r.OH * r.OW / 128) * math.ceil(r.Cout / 128)
+    # (measured, call O: it wins where the epilogue is the plain store and the slabs are full — qkv 29.6 -> 18.6 us, to_q 23.6 -> 16.0 —
+    # and loses with the generic epilogue, whose operand round trips a one-tile workgroup cannot hide: res_conv 17.0 -> 22.4;
+    # IMAGEN_CONV_GEMM=2 routes those too)
+    ok = ((CONV_GEMM >= 2 or (r.plain_ep and r.Cout >= GEMM_MIN_COUT))
+          and ln_pro and r.chunks32 and GEMM_MIN_K <= r.C1 + r.C2 <= GEMM_MAX_K and tiles >= GEMM_MIN_TILES
+          and r.x_aligned and r.cout_vec4)   # (ssq_out / post / gca wider than the 128-cout tile: not emitted, as in family 0)
+    if not ok:
+        return None
+    tw = 128 if r.OW >= 128 else 1 << (r.OW.bit_length() - 1)   # (the largest power of two inside the row, 128 pixels per tile)
+    return gemm_cfg(), 128 // tw, tw
+
+
+def _route_tiled(r: ConvReq):
+    """Families 5, 2 and 0 (pick_cfg): the big-tile and the all-DMA kernel for the prologue-free single-input 3x3 convs over 32-channel
+    chunks, the wave-specialised kernel for everything else.  Raises where no tile configuration fits."""
+    raw = r.x2 is None and r.no_pro and r.chunks32 and r.ld_aligned
+    return pick_cfg(r.G, r.Cout, r.OH, r.OW, r.B, r.KH, r.KW, r.stride, full_cout=r.full_cout, raw=raw)
+
+
+# DESIGN §4.2 as code: first match wins.  Each function answers (cfg, TH, TW) or None; the constants are read when a request is routed
+# (tests and the A/B tools assign them as module attributes).
+ROUTES = (_route_small, _route_pro, _route_stream, _route_pw, _route_gemm, _route_tiled)
+
+
+def route(req: ConvReq) -> tuple:
+    """(cfg, TH, TW) of the first family of ROUTES that takes the request (_route_tiled, the last, answers or raises)."""
+    return next(got for got in (fn(req) for fn in ROUTES) if got is not None)
+
+
 def igemm(plan: Plan, x1: Act, pw: PackedWeight, y, *, x2: Optional[Act] = None, mu=None, rs=None, pa=None, ps=None,
           pstride: int = 0, act_in: int = ACT_NONE, act_out: int = ACT_NONE, addend: Optional[Act] = None, gate=None,
           res: Optional[Act] = None, out_mode: int = OUT_NHWC, stride: int = 1, pad: Optional[int] = None,
           cfg: Optional[tuple] = None, ssq_a=None, ssq_b=None, ssq_wb: float = 1.0, ssq_out=None, post: Optional[dict] = None,
           gca: Optional[dict] = None, causal_rows: bool = False, label: str = ""):
-    """... ssq_a / ssq_b: producers' per-pixel sums of squares of x1 / x2 (ChanRMSNorm statistics without a separate pass);
-    ssq_out: emit the per-pixel sum of squares of the output — honoured only when the chosen tile covers all Cout
-    (`p.ssq_emitted` tells the caller, who otherwise falls back to a ROWSTAT op)."""
-    """Append one implicit-GEMM launch.  y: Act (NHWC / pixel-shuffle target) or fp32 NCHW tensor (OUT_NCHW_F32)."""
+    """Append one implicit-GEMM launch (ImagenIgemmParams): y = epilogue(conv(prologue(concat(x1, x2)), pw)).  Returns the params struct.
+    x1, x2: NHWC inputs (x2 optional, concatenated behind x1);  pw: the packed weight (a split-precision one reads x1 twice);
+    y: Act (NHWC / pixel-shuffle target) or an fp32 NCHW tensor (out_mode OUT_NCHW_F32);  stride, pad: of the window (pad: "same" at stride 1, else 0).
+    Prologue, per input element: (v - mu) * rs * pa + ps, then act_in.  mu, rs: fp32 per-pixel statistics;  pa, ps: fp32 per-channel scale /
+    shift, per batch row at a pitch of `pstride` floats (0: shared);  ssq_a, ssq_b: the producers' per-pixel sums of squares of x1 / x2
+    instead of rs (ChanRMSNorm statistics without a separate pass; rs = 1 / sqrt(ssq_a + ssq_wb * ssq_b)).
+    Epilogue: + bias, act_out, then `gate` [B, Cout] * `addend` + . | + `res` (residual), stored as out_mode says.
+    ssq_out: fp32 [rows], emit the per-pixel sum of squares of the output — honoured only when the chosen tile covers all Cout
+    (`p.ssq_emitted` tells the caller, who otherwise falls back to a ROWSTAT op).
+    post: dict(pa, ps, pstride) — the NEXT Block's ChanRMSNorm -> scale / shift -> SiLU applied to this conv's output in the epilogue
+    (`p.post_applied` tells the caller, who otherwise keeps the prologue on the consuming conv); excludes ssq_out.
+    gca: dict(wk = fp32 [Cout], bk = float) — GlobalContext partials of the output from the epilogue (one tile over all Cout, kernel families
+    2, 5, 7, 8); `p.gca_part_t` ([B, chunks, Cout + 2], chunks = tiles per image = `p.gca_chunks`) then feeds GCA_FINAL directly, None: not emitted.
+    cfg: (tile cfg id, TH, TW) to launch with instead of routing (tests, benches);  causal_rows: a KH x 1 window that ends at its own row
+    (kernel family 0, below);  label: the op's name in the plan."""
     KH, KW = pw.KH, pw.KW
     if pad is None:
         pad = (KH - 1) // 2 if stride == 1 else 0
@@ -526,86 +680,16 @@ def igemm(plan: Plan, x1: Act, pw: PackedWeight, y, *, x2: Optional[Act] = None,
         pad, pad_x1, OH, OW = KH - 1, 1, H, W
     C2 = x2.C if x2 is not None else 0
     assert x1.C + C2 == pw.Cin, f"{label}: input channels {x1.C}+{C2} != weight Cin {pw.Cin}"
-    want_gca = gca is not None and out_mode == OUT_NHWC and act_out == ACT_NONE and addend is None and res is None and post is None
-    if causal_rows:
-        cfg = pick_cfg(pw.G, pw.Cout, OH, OW, x1.B, KH, KW, stride, full_cout=ssq_out is not None and out_mode == OUT_NHWC, family=0)
-    small_3x3 = KH == 3 and KW == 3 and pad == 1 and pw.G == 4
-    small_1x1 = KH == 1 and KW == 1 and pad == 0 and pw.G >= 2 and OH > 1 and CONV_SMALL >= 2   # (spatial maps only: the token linears keep their kernels)
-    if cfg is None and CONV_SMALL and stride == 1 and (small_3x3 or small_1x1) and x1.B * OH * OW <= SMALL_MAX_ROWS:
-        # family 8: the 3x3 convs (and, CONV_SMALL >= 2, the 1x1 res_conv / upsample GEMMs) of the small maps, any prologue of the contract
-        # (statistics / affine / SiLU), any epilogue; the all-cout epilogues (ssq_out / post / GlobalContext partials) where a 32 | 64 | 128-cout
-        # tile covers Cout
-        full = (ssq_out is not None or post is not None or want_gca) and out_mode == OUT_NHWC
-        tile = small_tile(OH, OW)
-        sc = small_cfg(pw.Cout, full and pw.Cout <= 128)   # (wider layers: the 32-cout tile, statistics / post left to the caller's fallback as on family 0)
-        if (tile is not None and sc is not None and x1.C % 8 == 0 and C2 % 8 == 0 and x1.C + C2 == pw.Cin_pad
-                and x1.ld % 8 == 0 and x1.bs % 8 == 0 and (x2 is None or (x2.ld % 8 == 0 and x2.bs % 8 == 0))
-                and act_in in (ACT_NONE, ACT_SILU) and (mu is None or rs is not None) and (pstride == 0 or pstride >= pw.Cin_pad)
-                and (out_mode == OUT_NCHW_F32 or pw.Cout % 4 == 0) and (out_mode != OUT_PIXEL_SHUFFLE or pw.Cout % 16 == 0)
-                and pw.Cin_pad % 32 == 0 and not (addend is not None and (res is not None or gate is None))
-                and x1.ptr % 16 == 0 and (x2 is None or x2.ptr % 16 == 0)     # (launch_conv_small's own predicates: a shape it refuses falls through to the older families)
-                and small_lds_bytes(tile[0], tile[1], pw.Cin_pad, cfg_table()[sc][1]) <= MAX_LDS_BYTES
-                and (x1.B * OH * OW // 32) * pw.Cout_pad * pw.Cin_pad * 2 * KH * KW <= SMALL_MAX_STREAM_MB << 20):
-            cfg = (sc, tile[0], tile[1])
-    if cfg is None and CONV_PRO and KH == 3 and KW == 3 and stride == 1 and pad == 1 and pw.G == 4 and pro_cfg(pw.Cout) is not None:
-        # family 6: exactly 32 output channels from 32 | 32 + 32 input channels, or 64 from two or three 32-channel chunks (64 | 64 + 32 | 32 + 32):
-        # the ssq-statistics SiLU prologue on register-staged rows (CONV_PRO = 2: raw inputs too), plain / post (/ ssq_out, 32 couts) epilogue
-        no_pro = mu is None and rs is None and pa is None and ps is None and ssq_a is None and act_in == ACT_NONE
-        ssq_pro = mu is None and rs is None and pa is not None and ssq_a is not None and act_in == ACT_SILU and ((x2 is None) == (ssq_b is None))
-        nch = (x1.C + C2) // 32
-        chunks_ok = x1.C % 32 == 0 and C2 % 32 == 0 and pw.Cin_pad == x1.C + C2 and ((pw.Cout == 32 and nch in (1, 2) and x1.C == 32)
-                                                                                      or (pw.Cout == 64 and nch in (2, 3)))
-        tiles = x1.B * math.ceil(OH / 8) * math.ceil(OW / 16)
-        gca_here = want_gca and x1.B * math.ceil(OH / 16) * math.ceil(OW / 16) <= GCA_EPILOGUE_MAX_TILES
-        if (chunks_ok and x1.ld % 8 == 0 and x1.bs % 8 == 0 and (x2 is None or (x2.ld % 8 == 0 and x2.bs % 8 == 0))
-                and (ssq_pro or (no_pro and CONV_PRO >= 2)) and not gca_here and (pw.Cout == 32 or post is not None or ssq_out is None)
-                and tiles >= PRO_MIN_TILES and out_mode == OUT_NHWC and addend is None and res is None and act_out == ACT_NONE
-                and isinstance(y, Act) and y.ld % 8 == 0 and y.bs % 8 == 0 and not pw.split):
-            cfg = (pro_cfg(pw.Cout), 8, 16)
-    if cfg is None and CONV_STREAM and KH == 3 and KW == 3 and stride == 1 and pad == 1 and pw.G == 4:
-        # the streaming family: C_out <= 32 from one or two 32-channel inputs, raw or with the ssq-statistics Block prologue
-        no_pro = mu is None and rs is None and pa is None and ps is None and ssq_a is None and act_in == ACT_NONE
-        ssq_pro = mu is None and rs is None and pa is not None and ssq_a is not None and act_in in (ACT_NONE, ACT_SILU)
-        tiles16 = x1.B * math.ceil(OH / 16) * math.ceil(OW / 16)
-        gca_here = want_gca and tiles16 <= GCA_EPILOGUE_MAX_TILES   # (a layer whose epilogue emits the GlobalContext partials goes to family 2: the persistent streaming kernel measured slower with them, round 4 call F)
-        if (pw.Cout <= 32 and x1.C == 32 and C2 in (0, 32) and pw.Cin_pad == x1.C + C2 and x1.ld % 8 == 0 and (x2 is None or x2.ld % 8 == 0)
-                and (no_pro or ssq_pro) and not gca_here and tiles16 >= STREAM_MIN_TILES
-                and stream_cfg() is not None):
-            cfg = (stream_cfg(), 16, 16)
-    if cfg is None and CONV_PW and KH == 1 and KW == 1 and stride == 1 and pad == 0 and out_mode == OUT_NHWC:
-        # the streaming pointwise family: the res_conv GEMMs of the large maps (raw inputs in 32-channel chunks, <= 64 output channels,
-        # bias + gate * addend | residual epilogue)
-        no_pro = mu is None and rs is None and pa is None and ps is None and ssq_a is None and act_in == ACT_NONE
-        if (no_pro and act_out == ACT_NONE and post is None and gca is None and x1.C % 32 == 0 and C2 % 32 == 0 and pw.Cin_pad == x1.C + C2
-                and pw.Cout % 8 == 0 and x1.ld % 8 == 0 and (x2 is None or x2.ld % 8 == 0)
-                and (addend is None or (addend.ld % 8 == 0 and addend.bs % 8 == 0)) and (res is None or (res.ld % 8 == 0 and res.bs % 8 == 0))
-                and isinstance(y, Act) and y.ld % 8 == 0 and y.bs % 8 == 0):
-            pc = pw_cfg((x1.C + C2) // 32, pw.Cout)
-            if pc is not None and x1.B * math.ceil(OH * OW / cfg_table()[pc][0]) >= PW_MIN_TILES:
-                tp = cfg_table()[pc][0]
-                cfg = (pc, tp // min(OW, tp), min(OW, tp))
-    if cfg is None and CONV_GEMM and KH == 1 and KW == 1 and stride == 1 and pad == 0 and gemm_cfg() is not None:
-        # family 7, the tiled pointwise GEMM: the token / small-map 1x1 layers too deep for family 4's register-resident weights — raw rows
-        # or the LayerNorm prologue (mu / rs statistics, per-channel affine), every epilogue; 128-row x 128-cout workgroup tiles
-        ln_pro = ssq_a is None and ssq_b is None and act_in == ACT_NONE and (mu is None or rs is not None)
-        tiles = x1.B * math.ceil(OH * OW / 128) * math.ceil(pw.Cout / 128)
-        # (measured, call O: it wins where the epilogue is the plain store and the slabs are full — qkv 29.6 -> 18.6 us, to_q 23.6 -> 16.0 —
-        # and loses with the generic epilogue, whose operand round trips a one-tile workgroup cannot hide: res_conv 17.0 -> 22.4;
-        # IMAGEN_CONV_GEMM=2 routes those too)
-        plain_ep = act_out == ACT_NONE and out_mode == OUT_NHWC and addend is None and res is None
-        if ((CONV_GEMM >= 2 or (plain_ep and pw.Cout >= GEMM_MIN_COUT))
-                and ln_pro and x1.C % 32 == 0 and C2 % 32 == 0 and pw.Cin_pad == x1.C + C2 and GEMM_MIN_K <= x1.C + C2 <= GEMM_MAX_K and tiles >= GEMM_MIN_TILES
-                and x1.ld % 8 == 0 and x1.bs % 8 == 0 and (x2 is None or (x2.ld % 8 == 0 and x2.bs % 8 == 0))
-                and (out_mode == OUT_NCHW_F32 or pw.Cout % 4 == 0)):   # (ssq_out / post / gca wider than the 128-cout tile: not emitted, as in family 0)
-            tw = 128 if OW >= 128 else 1 << (OW.bit_length() - 1)   # (the largest power of two inside the row, 128 pixels per tile)
-            cfg = (gemm_cfg(), 128 // tw, tw)
-    if cfg is None:
-        raw = (x2 is None and mu is None and rs is None and pa is None and ps is None and ssq_a is None and act_in == ACT_NONE
-               and x1.C % 32 == 0 and pw.Cin_pad == x1.C and x1.ld % 8 == 0)
-    if cfg is None:
-        cfg = pick_cfg(pw.G, pw.Cout, OH, OW, x1.B, KH, KW, stride,
-                       full_cout=(ssq_out is not None or post is not None or want_gca) and out_mode == OUT_NHWC, raw=raw)
-    cid, th, tw = cfg
+    req = ConvReq(B=x1.B, H=H, W=W, OH=OH, OW=OW, KH=KH, KW=KW, stride=stride, pad=pad, C1=x1.C, C2=C2,
+                  Cin_pad=pw.Cin_pad, Cout=pw.Cout, Cout_pad=pw.Cout_pad, G=pw.G, split=pw.split,
+                  mu=mu is not None, rs=rs is not None, pa=pa is not None, ps=ps is not None, ssq_a=ssq_a is not None, ssq_b=ssq_b is not None,
+                  pstride=pstride, act_in=act_in, act_out=act_out, out_mode=out_mode, gate=gate is not None, gca=gca is not None,
+                  want_ssq=ssq_out is not None, want_post=post is not None,
+                  x1=_align(x1), x2=_align(x2), y=_align(y), addend=_align(addend), res=_align(res))
+    if causal_rows:   # (full_cout: the callers ask for no post / gca here, so this is the "ssq_out wanted" it has always been)
+        cfg = pick_cfg(pw.G, pw.Cout, OH, OW, x1.B, KH, KW, stride, full_cout=req.full_cout, family=0)
+    cid, th, tw = cfg if cfg is not None else route(req)
+    bn, fam = cfg_table()[cid][1], cfg_table()[cid][3]
     p = STRUCTS["ImagenIgemmParams"]()
     p.x1, p.C1, p.ld1, p.bs1 = x1.ptr, x1.C, x1.ld, x1.bs
     if x2 is not None:
@@ -646,33 +730,23 @@ def igemm(plan: Plan, x1: Act, pw: PackedWeight, y, *, x2: Optional[Act] = None,
     if ssq_a is not None:
         p.ssq_a, p.ssq_b, p.ssq_wb = ssq_a.data_ptr(), ptr(ssq_b), ssq_wb
         keep += [ssq_a, ssq_b]
-    # post: dict(pa, ps, pstride) — the NEXT Block's ChanRMSNorm -> scale/shift -> SiLU applied to this conv's output in the epilogue
-    # (`p.post_applied` tells the caller, who otherwise keeps the prologue on the consuming conv); excludes ssq_out
-    posted = False
-    if (post is not None and out_mode == OUT_NHWC and pw.Cout <= cfg_table()[cid][1] and addend is None and res is None
-            and act_out == ACT_NONE and pw.Cout % 4 == 0):
+    # the all-cout epilogues, where the chosen tile covers Cout: post (which excludes ssq_out), ssq_out, the GlobalContext partials
+    p.post_applied = req.want_post and req.plain_ep and pw.Cout <= bn and pw.Cout % 4 == 0
+    if p.post_applied:
         p.post_pa, p.post_ps, p.post_pstride = post["pa"].data_ptr(), post["ps"].data_ptr(), post["pstride"]
         keep += [post["pa"], post["ps"]]
-        posted = True
-        ssq_out = None
-    emitted = False
-    if ssq_out is not None and out_mode == OUT_NHWC and pw.Cout <= cfg_table()[cid][1]:
+    p.ssq_emitted = req.want_ssq and not p.post_applied and out_mode == OUT_NHWC and pw.Cout <= bn
+    if p.ssq_emitted:
         p.ssq_out = ssq_out.data_ptr()
         keep.append(ssq_out)
-        emitted = True
-    # gca: dict(wk=fp32 [Cout], bk=float): GlobalContext partials of the output from the epilogue (kernel family 2, one tile over
-    # all Cout); `p.gca_part_t` ([B, chunks, Cout + 2], chunks = tiles per image = `p.gca_chunks`) then feeds GCA_FINAL directly
     p.gca_part_t, p.gca_chunks = None, 0
     chunks = math.ceil(OH / th) * math.ceil(OW / tw)
-    fam = cfg_table()[cid][3]
-    if want_gca and pw.Cout <= cfg_table()[cid][1] and fam in (2, 5, 7, 8) and x1.B * chunks <= GCA_EPILOGUE_MAX_TILES:
+    if req.want_gca and pw.Cout <= bn and fam in (2, 5, 7, 8) and x1.B * chunks <= GCA_EPILOGUE_MAX_TILES:
         part = torch.empty(x1.B, chunks, pw.Cout + 2, dtype=torch.float32, device=x1.t.device)
         p.gca_wk, p.gca_part, p.gca_bk = gca["wk"].data_ptr(), part.data_ptr(), gca["bk"]
         keep += [gca["wk"], part]
         p.gca_part_t, p.gca_chunks = part, chunks
     plan.add(p, label or "igemm", keep)
-    p.ssq_emitted = emitted
-    p.post_applied = posted
     return p
 
 
@@ -982,7 +1056,7 @@ def ln_residual(plan: Plan, y: Act, g: torch.Tensor, out: Act, *, beta=None, res
     return p
 
 
-ROWCHAIN = int(_os.environ.get("IMAGEN_ROWCHAIN", "2"))   # A/B switch: 0 = the launch-per-op plan; 1 = the token chains of the <= 32^2 levels as one ROWCHAIN
+ROWCHAIN = int(os.environ.get("IMAGEN_ROWCHAIN", "2"))   # A/B switch: 0 = the launch-per-op plan; 1 = the token chains of the <= 32^2 levels as one ROWCHAIN
                                                            # launch each; 2 (default) = also the res_conv + gate tails of the big-tile levels (RESPREP)
 CHAIN_TILE64_MIN_ROWS = 16384    # 64-row tiles (every weight fragment feeds two MFMAs) once that still gives one workgroup per CU
 
