@@ -36,41 +36,53 @@ __global__ __launch_bounds__(256) void temporal_peg_kernel(const ImagenTemporalP
 }
 
 // ------------------------------------------------------------------------------------------------ temporal attention
-__device__ __forceinline__ float wave_sum(float v) {
+// Both kernels are templates over the head dim D in {64, 32} (ABI 12: ImagenTemporalAttentionParams.head_dim, 0 = 64): 64 is every README
+// config, 32 the reference's Unet3DConfig default (16 heads x 32).  The <64> instantiations are the kernels of before, statement by statement.
+template <int D>
+__device__ __forceinline__ float group_sum(float v) {   // sum over the D lanes that share lane / D
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  for (int off = D / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
   return v;
 }
 
 constexpr int kMaxFrames = 32;
-constexpr int kKvRow = 64;   // floats per key / value row in LDS (lane d reads column d: conflict-free)
+constexpr int kKvRow = 64;   // floats per key / value row in LDS (lane l reads column l: conflict-free)
 
-// One wave per (clip b, pixel px); lane d owns dimension d of the 64-wide head.  The F keys / values of the pixel (shared by all
-// heads) and the null key / value are normalised once into LDS; then for every head and query frame the F+1 similarities are
-// wave reductions, the (online) softmax is computed redundantly by every lane, and lane d accumulates output dimension d.
+// One wave per 64 / D (clip b, pixel px) items: lane l owns dimension l % D of item l / D (D = 64: one pixel per wave, lane d = dimension d;
+// D = 32: a pixel per half-wave, every reduction stays inside the half).  The F keys / values of the pixel (shared by all heads) and the
+// null key / value are normalised once into LDS; then for every head and query frame the F+1 similarities are group reductions, the
+// (online) softmax is computed redundantly by every lane, and each lane accumulates its output dimension.  F, heads and the causal
+// bounds are the same for every item, so the items of a wave run in lockstep; a wave whose last item does not exist computes the last
+// real one again in those lanes and does not store it.
+template <int D>
 __global__ __launch_bounds__(256) void temporal_attention_kernel(const ImagenTemporalAttentionParams p) {
   extern __shared__ float lds[];
+  constexpr int PPW = 64 / D;                               // items per wave
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const size_t item = (size_t)blockIdx.x * 4 + wave;       // (b, px)
-  if (item >= (size_t)p.B * p.P) return;                    // whole wave exits together
+  const int d = lane & (D - 1);
+  const size_t items = (size_t)p.B * p.P;
+  const size_t item0 = ((size_t)blockIdx.x * 4 + wave) * PPW;
+  if (item0 >= items) return;                               // whole wave exits together
+  const bool ok = item0 + lane / D < items;
+  const size_t item = ok ? item0 + lane / D : items - 1;   // (b, px)
   const int b = (int)(item / p.P), px = (int)(item - (size_t)b * p.P);
   const int F = p.F, J = F + 1;
   float* kh = lds + (size_t)wave * 2 * (kMaxFrames + 1) * kKvRow;
   float* vv = kh + (kMaxFrames + 1) * kKvRow;
   const f16* base = reinterpret_cast<const f16*>(p.qkv) + ((size_t)b * F * p.P + px) * p.ld;
   const size_t fstride = (size_t)p.P * p.ld;                // elements between consecutive frames of one pixel
-  const int inner = p.heads * 64;
-  const float ks = p.k_scale[lane], qs = p.q_scale[lane] * p.scale;
+  const int inner = p.heads * D;
+  const float ks = p.k_scale[d], qs = p.q_scale[d] * p.scale;
   {  // null key / value (row 0), then the F frames
-    const float nk = p.null_kv[lane], nv = p.null_kv[64 + lane];
-    const float inv = 1.0f / fmaxf(sqrtf(wave_sum(nk * nk)), 1e-12f);
+    const float nk = p.null_kv[d], nv = p.null_kv[D + d];
+    const float inv = 1.0f / fmaxf(sqrtf(group_sum<D>(nk * nk)), 1e-12f);
     kh[lane] = nk * inv * ks;
     vv[lane] = nv;
   }
   for (int j = 0; j < F; ++j) {
     const f16* row = base + (size_t)j * fstride + inner;
-    const float k = (float)row[lane], v = (float)row[64 + lane];
-    const float inv = 1.0f / fmaxf(sqrtf(wave_sum(k * k)), 1e-12f);
+    const float k = (float)row[d], v = (float)row[D + d];
+    const float inv = 1.0f / fmaxf(sqrtf(group_sum<D>(k * k)), 1e-12f);
     kh[(1 + j) * kKvRow + lane] = k * inv * ks;
     vv[(1 + j) * kKvRow + lane] = v;
   }
@@ -80,19 +92,19 @@ __global__ __launch_bounds__(256) void temporal_attention_kernel(const ImagenTem
   for (int h = 0; h < p.heads; ++h) {
     const float* bias_h = p.bias + (size_t)h * F * J;
     for (int i = 0; i < F; ++i) {
-      const float q = (float)base[(size_t)i * fstride + h * 64 + lane];
-      const float qn = q * (1.0f / fmaxf(sqrtf(wave_sum(q * q)), 1e-12f)) * qs;
+      const float q = (float)base[(size_t)i * fstride + h * D + d];
+      const float qn = q * (1.0f / fmaxf(sqrtf(group_sum<D>(q * q)), 1e-12f)) * qs;
       const int last = p.causal ? i + 1 : F;                // keys 0 (null) .. last are visible
       float mx = -3.0e38f, den = 0.f, acc = 0.f;             // online softmax: no per-key array (it would live in scratch)
       for (int j = 0; j <= last; ++j) {
-        const float s = wave_sum(qn * kh[j * kKvRow + lane]) + bias_h[i * J + j];
+        const float s = group_sum<D>(qn * kh[j * kKvRow + lane]) + bias_h[i * J + j];
         const float mn = fmaxf(mx, s);
         const float c = __expf(mx - mn), e = __expf(s - mn);
         den = den * c + e;
         acc = acc * c + e * vv[j * kKvRow + lane];
         mx = mn;
       }
-      obase[(size_t)i * ostride + h * 64 + lane] = (f16)(acc / den);
+      if (ok) obase[(size_t)i * ostride + h * D + d] = (f16)(acc / den);
     }
   }
 }
@@ -105,6 +117,8 @@ __global__ __launch_bounds__(256) void temporal_attention_kernel(const ImagenTem
 // fp16 hi + lo pairs (three products per K step: hi.hi + lo.hi + hi.lo), so the logits keep the fp32 accuracy of the kernel above — they
 // reach 18 with the scale vectors the reference trains, where a bare fp16 operand would cost 5e-3 in the softmax weights; P is fp16 as in
 // attention.hip.  V^T (dims x 32 keys, fp16) and the bias table go through LDS; per pixel 64 MFMAs instead of ~1200 wave reductions.
+// D = 64: four 16-dim K steps and two 32-dim blocks of O^T; D = 32: two K steps, one block, V^T 32 x 32 — twice the rows per pixel at equal
+// inner width (16 heads x 32 against 8 x 64), so the same MFMA count per pixel in the PV product and half of it per row in S^T.
 constexpr int kTaVtRow = 72;   // LDS bytes per V^T row (32 keys x 2 B + 8: conflict-free ds_read_b64, attention.hip's VSTR)
 
 __device__ __forceinline__ void ta_split(const float (&x)[8], f16x8& hi, f16x8& lo) {
@@ -115,8 +129,11 @@ __device__ __forceinline__ void ta_split(const float (&x)[8], f16x8& hi, f16x8& 
   }
 }
 
+template <int D>
 __global__ __launch_bounds__(256) void temporal_attention_mfma_kernel(const ImagenTemporalAttentionParams p) {
   extern __shared__ float lds[];
+  constexpr int KS = D / 16;   // 16-dim K steps of S^T
+  constexpr int DB = D / 32;   // 32-dim blocks of O^T
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int half = lane >> 5, l31 = lane & 31;
   const int F = p.F, J = F + 1;
@@ -124,30 +141,33 @@ __global__ __launch_bounds__(256) void temporal_attention_mfma_kernel(const Imag
   float* s_bias = lds;                                                   // [heads][F][J]
   const int nb = p.heads * F * J;
   for (int i = threadIdx.x; i < nb; i += 256) s_bias[i] = p.bias[i];
-  char* vt = reinterpret_cast<char*>(lds + ((nb + 3) & ~3)) + (size_t)wave * 64 * kTaVtRow;   // this wave's V^T: [64 dims][32 keys] fp16
+  char* vt = reinterpret_cast<char*>(lds + ((nb + 3) & ~3)) + (size_t)wave * D * kTaVtRow;   // this wave's V^T: [D dims][32 keys] fp16
   __syncthreads();
   const size_t item = (size_t)blockIdx.x * 4 + wave;       // (b, px)
   if (item >= (size_t)p.B * p.P) return;                    // (behind the only workgroup barrier)
   const int b = (int)(item / p.P), px = (int)(item - (size_t)b * p.P);
   const f16* base = reinterpret_cast<const f16*>(p.qkv) + ((size_t)b * F * p.P + px) * p.ld;
   const size_t fstride = (size_t)p.P * p.ld;
-  const int inner = p.heads * 64;
+  const int inner = p.heads * D;
   const int rows = p.heads * F;
-  f16x8 qraw[4];   // the query rows of a 32-row block as loaded (row r0 + l31 = (head, frame), dims 16 s + 8 half ..)
+  f16x8 qraw[KS];   // the query rows of a 32-row block as loaded (row r0 + l31 = (head, frame), dims 16 s + 8 half ..)
   auto q_fetch = [&](int r0) __attribute__((always_inline)) {
     const int r = r0 + l31;
     const int h = r < rows ? r / F : 0, i = r < rows ? r - h * F : 0;
 #pragma unroll
-    for (int s = 0; s < 4; ++s) qraw[s] = *reinterpret_cast<const f16x8*>(base + (size_t)i * fstride + h * 64 + 16 * s + 8 * half);
+    for (int s = 0; s < KS; ++s) qraw[s] = *reinterpret_cast<const f16x8*>(base + (size_t)i * fstride + h * D + 16 * s + 8 * half);
   };
   q_fetch(0);      // (in flight behind the V^T gather and the K^ rows)
 
-  // ---- V^T: lane d gathers column d of the J value rows (null value first); keys J..31 are zero
+  // ---- V^T: lane d gathers column d of the J value rows (null value first); keys J..31 are zero.  (D = 32: the two half-waves share a
+  //      column, half 0 the even key slots, half 1 the odd ones)
   {
-    f16* col = reinterpret_cast<f16*>(vt + lane * kTaVtRow);
-    col[0] = (f16)p.null_kv[64 + lane];
-    for (int j = 0; j < F; ++j) col[1 + j] = base[(size_t)j * fstride + inner + 64 + lane];
-    for (int j = J; j < 32; ++j) col[j] = (f16)0.f;
+    constexpr int PPW = 64 / D;
+    const int d = lane & (D - 1);
+    f16* col = reinterpret_cast<f16*>(vt + d * kTaVtRow);
+    if (lane < D) col[0] = (f16)p.null_kv[D + d];
+    for (int j = lane / D; j < F; j += PPW) col[1 + j] = base[(size_t)j * fstride + inner + D + d];
+    for (int j = J + lane / D; j < 32; j += PPW) col[j] = (f16)0.f;
   }
   // the tile is wave-private, but other LANES of the wave read what this lane stored: order the stores before the PV fragment reads
   // (hardware issues a wave's LDS operations in order; the fence keeps the compiler — and the CPU emulation's fibers — to that order)
@@ -155,12 +175,12 @@ __global__ __launch_bounds__(256) void temporal_attention_mfma_kernel(const Imag
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   // ---- K^ fragments (A operand: lane = key l31, dims 16 s + 8 half ..): l2norm * k_scale, as fp16 hi + lo; key 0 = the null key
-  f16x8 kh[4], kl[4];
+  f16x8 kh[KS], kl[KS];
   {
-    float kx[4][8];
+    float kx[KS][8];
     float ssq = 0.f;
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
+    for (int s = 0; s < KS; ++s) {
       const int d0 = 16 * s + 8 * half;
       if (l31 == 0) {
 #pragma unroll
@@ -179,7 +199,7 @@ __global__ __launch_bounds__(256) void temporal_attention_mfma_kernel(const Imag
     ssq += __shfl_xor(ssq, 32);
     const float inv = 1.0f / fmaxf(sqrtf(ssq), 1e-12f);
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
+    for (int s = 0; s < KS; ++s) {
       const int d0 = 16 * s + 8 * half;
 #pragma unroll
       for (int j = 0; j < 8; ++j) kx[s][j] *= inv * (p.k_scale[d0 + j] * p.q_scale[d0 + j] * p.scale);   // (q_scale * scale ride on K^: Q^ is the unit row)
@@ -187,16 +207,16 @@ __global__ __launch_bounds__(256) void temporal_attention_mfma_kernel(const Imag
     }
   }
   // The null value is an fp32 parameter and the same vector for every pixel: its fp16 part rides the MFMA as V^T column 0, the remainder
-  // nv - fp16(nv) is added behind it on the VALU with the null key's fp32 weight (32 FMAs per row block).  Dropped, it is a coherent
+  // nv - fp16(nv) is added behind it on the VALU with the null key's fp32 weight (D / 2 FMAs per row block).  Dropped, it is a coherent
   // bias of the whole map — a first frame under the causal mask gives the null key about half its weight — and the C5 denoiser's
   // distance to the oracle moved 1.00e-3 -> 1.05e-3 when this kernel replaced the fp32 vector kernel in round 4 (plan interpreter with
   // the null value rounded to fp16: 1.008e-3 -> 1.044e-3, round-5 session 2).
-  float nvlo[2][16];   // [db][4 qd + e]: dim 32 db + 8 qd + 4 half + e, the accumulator layout of O^T below
+  float nvlo[DB][16];   // [db][4 qd + e]: dim 32 db + 8 qd + 4 half + e, the accumulator layout of O^T below
 #pragma unroll
-  for (int db = 0; db < 2; ++db)
+  for (int db = 0; db < DB; ++db)
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const float nv = p.null_kv[64 + 32 * db + 8 * (e >> 2) + 4 * half + (e & 3)];
+      const float nv = p.null_kv[D + 32 * db + 8 * (e >> 2) + 4 * half + (e & 3)];
       nvlo[db][e] = nv - (float)(f16)nv;
     }
   f16* obase = reinterpret_cast<f16*>(p.o) + ((size_t)b * F * p.P + px) * p.ld_o;
@@ -208,12 +228,12 @@ __global__ __launch_bounds__(256) void temporal_attention_mfma_kernel(const Imag
     const int r = r0 + l31;
     const bool rok = r < rows;
     const int h = rok ? r / F : 0, i = rok ? r - h * F : 0;
-    f16x8 qh[4], ql[4];
+    f16x8 qh[KS], ql[KS];
     {
-      float qx[4][8];
+      float qx[KS][8];
       float ssq = 0.f;
 #pragma unroll
-      for (int s = 0; s < 4; ++s) {
+      for (int s = 0; s < KS; ++s) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           qx[s][j] = rok ? (float)qraw[s][j] : 0.f;
@@ -224,7 +244,7 @@ __global__ __launch_bounds__(256) void temporal_attention_mfma_kernel(const Imag
       ssq += __shfl_xor(ssq, 32);
       const float inv = 1.0f / fmaxf(sqrtf(ssq), 1e-12f);
 #pragma unroll
-      for (int s = 0; s < 4; ++s) {
+      for (int s = 0; s < KS; ++s) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) qx[s][j] *= inv;
         ta_split(qx[s], qh[s], ql[s]);
@@ -235,7 +255,7 @@ __global__ __launch_bounds__(256) void temporal_attention_mfma_kernel(const Imag
 #pragma unroll
     for (int e = 0; e < 16; ++e) sacc[e] = 0.f;
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
+    for (int s = 0; s < KS; ++s) {
       sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl[s], qh[s], sacc, 0, 0, 0);
       sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh[s], ql[s], sacc, 0, 0, 0);
       sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh[s], qh[s], sacc, 0, 0, 0);
@@ -266,15 +286,15 @@ __global__ __launch_bounds__(256) void temporal_attention_mfma_kernel(const Imag
     // the null key is key 0 = register 0 of the half-0 lane of the row
     const float w_null = __shfl(sacc[0] > -1.0e38f ? __expf(sacc[0] - mx) : 0.f, l31);
     // ---- O^T[d][row] += V^T . P   (k-step s covers the keys of accumulator registers 8 s .. 8 s + 7)
-    f32x16 oacc[2];
+    f32x16 oacc[DB];
 #pragma unroll
-    for (int db = 0; db < 2; ++db)
+    for (int db = 0; db < DB; ++db)
 #pragma unroll
       for (int e = 0; e < 16; ++e) oacc[db][e] = 0.f;
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
-      for (int db = 0; db < 2; ++db) {
+      for (int db = 0; db < DB; ++db) {
         const char* vrow = vt + (32 * db + l31) * kTaVtRow + (16 * s + 4 * half) * 2;
         const uint2 lo = *reinterpret_cast<const uint2*>(vrow);
         const uint2 hi = *reinterpret_cast<const uint2*>(vrow + 16);
@@ -284,14 +304,14 @@ __global__ __launch_bounds__(256) void temporal_attention_mfma_kernel(const Imag
         oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[s], oacc[db], 0, 0, 0);
       }
 #pragma unroll
-    for (int db = 0; db < 2; ++db)
+    for (int db = 0; db < DB; ++db)
 #pragma unroll
       for (int e = 0; e < 16; ++e) oacc[db][e] += w_null * nvlo[db][e];
     if (rok) {
       const float inv = 1.0f / den;
-      f16* o = obase + (size_t)i * ostride + h * 64;
+      f16* o = obase + (size_t)i * ostride + h * D;
 #pragma unroll
-      for (int db = 0; db < 2; ++db)
+      for (int db = 0; db < DB; ++db)
 #pragma unroll
         for (int qd = 0; qd < 4; ++qd) {
           f16x4 v;
@@ -301,6 +321,33 @@ __global__ __launch_bounds__(256) void temporal_attention_mfma_kernel(const Imag
         }
     }
   }
+}
+
+template <int D>
+int launch_temporal_attention_d(const ImagenTemporalAttentionParams* p, hipStream_t s) {
+  const size_t items = (size_t)p->B * p->P;
+  const size_t nb = (size_t)p->heads * p->F * (p->F + 1);
+  const size_t lds = ((nb + 3) & ~(size_t)3) * sizeof(float) + (size_t)4 * D * kTaVtRow;   // the bias table + four V^T tiles of D dims
+  // the MFMA kernel: F + 1 keys in one 32-key tile, the bias table of all heads in 64 KB of LDS (12+ heads at F = 31 do not fit: those
+  // shapes keep the vector kernel below, as every shape did before round 4), and aligned rows: a lane loads 8 halfs at column h D + 16 s +
+  // 8 half of a qkv row and stores 4 at column h D + 32 db + 8 qd + 4 half of an o row — multiples of 8 / 4 for both D, so the row strides
+  // and the base pointers decide
+  if (p->F <= 31 && p->ld % 8 == 0 && p->ld_o % 4 == 0 && ((size_t)p->qkv & 15) == 0 && ((size_t)p->o & 7) == 0 && lds <= 64 * 1024) {
+    hipLaunchKernelGGL(temporal_attention_mfma_kernel<D>, dim3((unsigned)((items + 3) / 4)), dim3(256), lds, s, *p);
+    return imagen_hip_status("temporal_attention");
+  }
+  const size_t lds_bytes = (size_t)4 * 2 * (kMaxFrames + 1) * kKvRow * sizeof(float);
+  static bool attr_set[16] = {};   // per device (and per instantiation)
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev < 0 || dev >= 16 || !attr_set[dev]) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(temporal_attention_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds_bytes);
+    if (dev >= 0 && dev < 16) attr_set[dev] = true;
+  }
+  const size_t waves = (items * D + 63) / 64;   // 64 / D items per wave
+  hipLaunchKernelGGL(temporal_attention_kernel<D>, dim3((unsigned)((waves + 3) / 4)), dim3(256), lds_bytes, s, *p);
+  return imagen_hip_status("temporal_attention");
 }
 
 }  // namespace
@@ -317,24 +364,6 @@ int launch_temporal_attention(const ImagenTemporalAttentionParams* p, hipStream_
   IMAGEN_CHECK(p->qkv && p->null_kv && p->q_scale && p->k_scale && p->bias && p->o, "temporal_attention: null pointer");
   IMAGEN_CHECK(p->F > 0 && p->F <= kMaxFrames, "temporal_attention: 1 <= F <= 32");
   IMAGEN_CHECK(p->heads > 0 && p->B > 0 && p->P > 0, "temporal_attention: bad shape");
-  const size_t items = (size_t)p->B * p->P;
-  const size_t nb = (size_t)p->heads * p->F * (p->F + 1);
-  const size_t lds = ((nb + 3) & ~(size_t)3) * sizeof(float) + (size_t)4 * 64 * kTaVtRow;
-  // the MFMA kernel: F + 1 keys in one 32-key tile, aligned rows, the bias table of all heads in 64 KB of LDS (12+ heads at F = 31 do not
-  // fit: those shapes keep the vector kernel below, as every shape did before round 4)
-  if (p->F <= 31 && p->ld % 8 == 0 && p->ld_o % 4 == 0 && ((size_t)p->qkv & 15) == 0 && ((size_t)p->o & 7) == 0 && lds <= 64 * 1024) {
-    hipLaunchKernelGGL(temporal_attention_mfma_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), lds, s, *p);
-    return imagen_hip_status("temporal_attention");
-  }
-  const size_t lds_bytes = (size_t)4 * 2 * (kMaxFrames + 1) * kKvRow * sizeof(float);
-  static bool attr_set[16] = {};   // per device
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 16 || !attr_set[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(temporal_attention_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds_bytes);
-    if (dev >= 0 && dev < 16) attr_set[dev] = true;
-  }
-  hipLaunchKernelGGL(temporal_attention_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), lds_bytes, s, *p);
-  return imagen_hip_status("temporal_attention");
+  IMAGEN_CHECK(p->head_dim == 0 || p->head_dim == 32 || p->head_dim == 64, "temporal_attention: head_dim must be 64 (or 0) or 32");
+  return p->head_dim == 32 ? launch_temporal_attention_d<32>(p, s) : launch_temporal_attention_d<64>(p, s);
 }

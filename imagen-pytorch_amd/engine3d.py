@@ -503,7 +503,6 @@ class UnetEngine3D(UnetEngine):
         nm = name + ".fn.fn"
         C, P = x.C, x.H * x.W
         heads, dh = attn.heads, attn.dim_head
-        assert dh == 64
         inner = heads * dh
         rows = R * f * P
         tok = Act(x.t, 1, 1, rows, C, C, rows * C, x.off)
@@ -515,7 +514,7 @@ class UnetEngine3D(UnetEngine):
         o = self.new(1, 1, rows, inner)
         ops.temporal_attention(plan, qkv, W.f32(nm + ".null_kv", lambda: attn.null_kv), W.f32(nm + ".q_scale", lambda: attn.q_scale),
                                W.f32(nm + ".k_scale", lambda: attn.k_scale), W.get(f"{nm}.bias.{f}", lambda: self._position_bias(attn, f).to(self.dev)),
-                               o, B=R, F=f, P=P, heads=heads, causal=attn.causal, scale=SIM_SCALE, label=nm + ".attn")
+                               o, B=R, F=f, P=P, heads=heads, causal=attn.causal, scale=SIM_SCALE, head_dim=dh, label=nm + ".attn")
         y = self.new(1, 1, rows, C)
         ops.igemm(plan, o, W.conv(nm + ".to_out", attn.to_out[0]), y, label=nm + ".to_out")
         out = self.new(x.B, x.H, x.W, C)

@@ -91,8 +91,9 @@ class Unet3D(nn.Module):
                 _unsupported(name)
         if not pixel_shuffle_upsample:
             _unsupported('pixel_shuffle_upsample=False')
-        if attn_dim_head != 64:
-            raise NotImplementedError("the attention kernels are specialised for dim_head = 64")
+        if attn_dim_head not in (32, 64):
+            raise NotImplementedError(f"attn_dim_head = {attn_dim_head}: the attention kernels (temporal attention included) are built for head dims 64 "
+                                      "(every README config) and 32 (the reference's Unet3DConfig default, configs.py:61-62)")
 
         self.self_cond = self_cond
         self.channels = channels

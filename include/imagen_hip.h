@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define IMAGEN_ABI_VERSION 11 /* 11: ImagenDdpmUpdateParams.row_keys (per-row Philox key + sample index: requests merged into one batch draw their own noise);  10: ImagenIgemmParams.pad_x1 (a KH x KW window with its own x padding: the causal temporal conv of Imagen-Video as ONE (3 x 1)-tap launch);  9: LINEAR_F32, SCALE_SHIFT ss_f32;  8: ROWCHAIN, the latency probes;  3: head_dim in the attention / QNORM / KV_PREP params; 4: DDPM_UPDATE x0_thr; 5: GCA_TAIL; 6: ACT_PREP self_stat, STEP_SLICE;
+#define IMAGEN_ABI_VERSION 12 /* 12: ImagenTemporalAttentionParams.head_dim (the temporal attention of Imagen-Video at head dim 32, the reference's Unet3DConfig default; 0 = 64: plans of before are unchanged);  11: ImagenDdpmUpdateParams.row_keys (per-row Philox key + sample index: requests merged into one batch draw their own noise);  10: ImagenIgemmParams.pad_x1 (a KH x KW window with its own x padding: the causal temporal conv of Imagen-Video as ONE (3 x 1)-tap launch);  9: LINEAR_F32, SCALE_SHIFT ss_f32;  8: ROWCHAIN, the latency probes;  3: head_dim in the attention / QNORM / KV_PREP params; 4: DDPM_UPDATE x0_thr; 5: GCA_TAIL; 6: ACT_PREP self_stat, STEP_SLICE;
                                * 7: every launch carries sizeof(its params struct) (a stale mirror of a struct fails loudly), ImagenIgemmParams.dbg -> launcher_word, kernel families 6 and 7, ImagenAttentionParams.softmax_mode */
 
 typedef void* imagen_stream_t; /* hipStream_t */
@@ -219,7 +219,9 @@ typedef struct ImagenKvPrepMultiParams {
  *   qh = l2norm(q[b,i,p,h,:]) * q_scale * scale ;  kh[0] = l2norm(null_k) * k_scale, kh[1+j] = l2norm(k[b,j,p,:]) * k_scale
  *   sim[i][j'] = qh . kh[j'] + bias[h][i][j']   (bias: [heads][F][F+1] fp32, column 0 = null-key bias, the rest = the generated
  *   relative position bias);  causal: keys with frame index > i are masked;  o[b,i,p,h,:] = softmax_j'(sim) @ [null_v, v[b,:,p,:]]
- * qkv rows (b, f, p) hold q (heads*64) | k (64) | v (64) at row stride ld (fp16); o rows have stride ld_o.  F <= 32. */
+ * D = head_dim is 64 or 32.  qkv rows (b, f, p) hold q (heads*D) | k (D) | v (D) at row stride ld (fp16); o rows hold heads*D values at
+ * stride ld_o (columns beyond heads*D are not written); null_kv is fp32 [2][D] (null key, null value), q_scale / k_scale are fp32 [D].
+ * F <= 32. */
 typedef struct ImagenTemporalPegParams {
   const void* x; const float* w; const float* bias; void* out;
   int32_t B, F, P, C, causal;
@@ -227,6 +229,7 @@ typedef struct ImagenTemporalPegParams {
 typedef struct ImagenTemporalAttentionParams {
   const void* qkv; const float* null_kv; const float* q_scale; const float* k_scale; const float* bias; void* o;
   int32_t B, F, P, heads, ld, ld_o, causal; float scale;
+  int32_t head_dim; /* 64 (0 means 64) or 32 */
 } ImagenTemporalAttentionParams;
 
 /* QNORM — q[r, h, :] = l2norm(q[r, h, :]) * q_scale * mult   in place (ip.py:559-560, 812-813). */
