@@ -275,12 +275,14 @@ __global__ __launch_bounds__(256) void lincomb_kernel(const ImagenLincombParams 
     if (p.t1) {
       float t = p.t1[i];
       if (p.thr_mode) t = fminf(fmaxf(t, -s1), s1) / s1;
+      if (p.thr1_out) p.thr1_out[i] = t;
       v += w1 * t;
     }
     if (p.t2) v += w2 * p.t2[i];
     if (p.t3) {
       float t = p.t3[i];
       if (p.thr_mode) t = fminf(fmaxf(t, -s3), s3) / s3;
+      if (p.thr3_out) p.thr3_out[i] = t;
       v += w3 * t;
     }
     if (p.mask && p.mask[i] == 0.0f) v = p.mask_else[i];
@@ -296,6 +298,8 @@ int launch_lincomb(const ImagenLincombParams* p, hipStream_t s) {
   IMAGEN_CHECK(p->t0 && p->out && p->coef && p->step_ptr, "lincomb: t0 / out / coef / step_ptr required");
   IMAGEN_CHECK(p->n_per_sample % 4 == 0 && p->B > 0, "lincomb: n_per_sample %% 4");
   IMAGEN_CHECK(!p->mask || p->mask_else, "lincomb: mask needs mask_else");
+  IMAGEN_CHECK(!p->thr1_out || p->t1, "lincomb: thr1_out needs t1");
+  IMAGEN_CHECK(!p->thr3_out || p->t3, "lincomb: thr3_out needs t3");
   const size_t n = (size_t)p->B * p->n_per_sample;
   hipLaunchKernelGGL(lincomb_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, *p);
   if (p->advance) hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, s, p->step_ptr);

@@ -14,7 +14,9 @@ initial noise, per-call `sigma_min` / `sigma_max` select another table set, and 
 repeats every timestep's rows `inpaint_resample_times` times with two extra LINCOMB launches in the same captured sequence — the known
 pixels blended into x before the churn noise (x_hat = where(mask, known, x) + noise, el.py:497-498) and x += (sigma - sigma_next) * z
 after the Heun combination, with identity weights on the rows where the reference skips it.  Video stages (Unet3D, prompt frames)
-as in `Imagen`.  Training (`forward`) and self-conditioning unets raise.
+as in `Imagen`.  Self-conditioning unets (el.py:496, 518, 538): the Euler op also writes out the clamped model output it sums
+(LINCOMB `thr1_out`) — the second evaluation's `self_cond` — and the Heun op that of the second evaluation (`thr3_out`) — the next
+step's; both go straight into the engine's `self_cond_in`, which every evaluation packs at its start.  Training (`forward`) raises.
 """
 from __future__ import annotations
 
@@ -143,9 +145,6 @@ class ElucidatedImagen(Imagen):
     def _build_stage(self, idx: int, B: int, device, *, cond_scale: float, with_text: bool, inject_noise: bool, sample_offset: int,
                      resample_times: int = 0, frames: int = 0, prompt_frames: tuple = (0, 0)):
         unet = self.unets[idx]
-        if getattr(unet, 'self_cond', False):
-            from .imagen import _out_of_scope
-            _out_of_scope("ElucidatedImagen sampling with self-conditioning unets (el.py:496, 518)")
         S = self.image_sizes[idx]
         hp = self.hparams[idx]
         over = getattr(self._tls, 'sigma_overrides', None)          # sample(sigma_min=, sigma_max=), el.py:425-426, 647-648
@@ -170,6 +169,10 @@ class ElucidatedImagen(Imagen):
             eng = engine.UnetEngine(unet, rows, B, S, device, with_text=with_text)
         n = eng.x_in[0].numel()
         dev = device
+        # self-conditioning (el.py:496, 518, 538): every evaluation packs `sc`; the Euler op leaves the first evaluation's clamped output in
+        # it for the Heun evaluation, the Heun op the second one's for the next step (or the next resample of the same timestep)
+        sc = eng.self_cond_in if getattr(unet, 'self_cond', False) else None
+        assert sc is None or sc.numel() == B * n
         init_sigma, (coef, w_hat, w_euler, w_heun, w_renoise) = self._tables(hp, max(R, 1))
         coef, w_hat, w_euler, w_heun, w_renoise = (t.to(dev) for t in (coef, w_hat, w_euler, w_heun, w_renoise))
         if inject_noise:   # the churn noise comes in through t1 (weight col 1) instead of the in-kernel Philox stream (col 4)
@@ -217,28 +220,30 @@ class ElucidatedImagen(Imagen):
         full = Plan(f"edm-stage{idx}-step")
         first_eval(full)
         ops.lincomb(full, xhat, xnext, w_euler, step_ptr, t1=x0a, q1=qa if dyn else None, out2=eng.x_in, thr_mode=thr, advance=True,
-                    label="edm.euler", **kw)
+                    thr1_out=sc, label="edm.euler", **kw)
         full.extend(step_plan)
         ops.cfg_x0(full, xnext, eng.out, coef, step_ptr, x0b, absx0, B=B, n_per_sample=n, cfg=cfg, cond_scale=float(cond_scale),
                    objective="noise", label="edm.precond2")
         if dyn:
             ops.quantile(full, absx0, qb, scr_b, B=B, n=n, q=q)
         ops.lincomb(full, xhat, x, w_heun, step_ptr, t1=x0a, t2=xnext, t3=x0b, q1=qa if dyn else None, q3=qb if dyn else None,
-                    thr_mode=thr, advance=not R, label="edm.heun", **kw)
+                    thr_mode=thr, advance=not R, thr3_out=sc, label="edm.heun", **kw)
         if R:   # RePaint re-noising before the next resample of the same timestep (identity weights where the reference skips it)
             ops.lincomb(full, x, x, w_renoise, step_ptr, t1=extra['noise_renoise'], advance=True, label="edm.inpaint.renoise",
                         **{**kw, "stream_id": idx | 0x200})
 
         last = Plan(f"edm-stage{idx}-last")       # sigma_next = 0: Euler step only, then clamp + unnormalise (el.py:515, 540-545)
+        # self-conditioning: it reads what the preceding Heun op left, and only with resampling, where the last timestep runs again on
+        # this evaluation's output (el.py:538), leaves anything behind
         first_eval(last)
         ops.lincomb(last, xhat, x, w_euler, step_ptr, t1=x0a, q1=qa if dyn else None, thr_mode=thr, final=True, final_out=final,
-                    advance=True, label="edm.euler.final", **kw)
+                    advance=True, thr1_out=sc if R > 1 else None, label="edm.euler.final", **kw)
 
         w_init = torch.zeros(1, 8, device=dev)
         w_init[0, 0] = init_sigma
         st = dict(eng=eng, plan=full, last=last, graph=None, graph_last=None, coef=coef, step_ptr=step_ptr, seed_dev=seed_dev, noise=noise,
                   final=final, T=hp.num_sample_steps, S=S, x=x, w_init=w_init, zero_ptr=zero_ptr,
-                  tables=(w_hat, w_euler, w_heun, w_renoise, w_one), video=video, frames=frames, R=R,
+                  tables=(w_hat, w_euler, w_heun, w_renoise, w_one), self_cond=sc, video=video, frames=frames, R=R,
                   bufs=(xhat, xnext, x0a, x0b, absx0, qa, qb, scr_a, scr_b), **extra)
         self._stages[key] = st
         return st
@@ -275,6 +280,8 @@ class ElucidatedImagen(Imagen):
             pl.run()
             if init_images is not None:
                 x.add_(init_images)                          # el.py:446-447
+            if st['self_cond'] is not None:
+                st['self_cond'].zero_()                      # el.py:451: x_start = None (also after the warm-up and when steps are skipped)
             st['step_ptr'].fill_(self._row(skip, inner - 1, T, inner))   # el.py:477-479: the skipped steps are never run
 
         st['seed_dev'].copy_(torch.tensor([seed & 0x7FFFFFFF, (seed >> 31) & 0x7FFFFFFF], dtype=torch.int32))

@@ -77,6 +77,10 @@ class UnetEngine3D(UnetEngine):
         div = getattr(unet, 'total_temporal_divisor', 1)
         assert pre_frames % div == 0 and post_frames % div == 0, \
             f'the number of conditioning frames must be divisible by {div}'                     # iv.py:1700, 1713
+        if getattr(unet, 'self_cond', False) and (pre_frames or post_frames):
+            from .imagen import _out_of_scope
+            _out_of_scope("Unet3D(self_cond=True) with cond_video_frames / post_cond_video_frames (the reference cannot concatenate a "
+                          "self-conditioning clip of the frames of x with the extended clip either, iv.py:1676, 1703)")
         super().__init__(unet, rows, src_batch, size, device, with_text=with_text, dry=dry)
 
     # ------------------------------------------------------------------------------------------ views
@@ -104,7 +108,14 @@ class UnetEngine3D(UnetEngine):
         # conditioning image (Unet3D(cond_images_channels=...), iv.py:1722-1731): ONE image per sample, repeated over every frame the
         # network runs on; the init conv reads it as a second, channel-concatenated input like the image Unet does
         cc = getattr(u, 'cond_images_channels', 0)
-        self.cimg = self.new(R * F, S, S, (cc + 7) // 8 * 8, zero=True) if cc else None
+        # self-conditioning clip (Unet3D(self_cond=True), iv.py:1674-1676): the previous evaluation's thresholded x0 over the frames of x,
+        # frame-major like `x_in`, zeros at first.  As on the image path it is the leading part of the init conv's second input
+        # `cimg`, packed at the start of every step.  It never meets a conditioning image (Unet3D refuses the two together) nor prompt
+        # frames (__init__), so F == Fx here
+        sc = u.channels if getattr(u, 'self_cond', False) else 0
+        assert not (sc and cc) and not (sc and F != Fx)
+        self.self_cond_in = self.f32buf(self.src_batch, Fx, sc, S, S, zero=True) if sc else None
+        self.cimg = self.new(R * F, S, S, (sc + cc + 7) // 8 * 8, zero=True) if sc + cc else None
 
     def set_cond_images(self, cond_images: torch.Tensor):
         """(src_batch, cond_images_channels, h, w), values as given: resized to this engine's resolution with the unet's resize_mode
@@ -138,6 +149,10 @@ class UnetEngine3D(UnetEngine):
         self.img_x = self.img if F == Fx else self.new(R * Fx, S, S, 8)       # the packed Fx frames [x | lowres | zero pad]
         self._pack_op = ops.pack_image(plan, xin, lin, self.img_x, brep=R // self.src_batch, label="pack_frames")
         plan.keep += [self.x_in, self.lowres_in] if self.lowres else [self.x_in]
+        if self.self_cond_in is not None:            # the second 8-channel image, as engine.UnetEngine packs it (F == Fx: _alloc_io)
+            self._self_cond_op = ops.pack_image(plan, self.self_cond_in.view(self.src_batch * Fx, u.channels, S, S), None, self.cimg,
+                                                brep=R // self.src_batch, label="pack_self_cond")
+            plan.keep += [self.self_cond_in]
         self.fin2 = None
         if F != Fx:
             # prompt frames: clip = [post | pre | x] (iv.py:1703, 1716); the prompt slots are static, the Fx frames land behind them
@@ -279,12 +294,19 @@ class UnetEngine3D(UnetEngine):
         u = self.unet
 
         cc = getattr(u, 'cond_images_channels', 0)
+        sc = u.channels if self.self_cond_in is not None else 0
+        c = u.channels
+        nl = c if self.lowres else 0
         auxp = self.cimg.C if self.cimg is not None else 0
 
         def spread(w):
-            """Reference input channels [cond image | x | lowres] (iv.py:1685, 1731) -> ours [x | lowres | 0.. (8)] ++ [cond image | 0.. (auxp)]."""
+            """Reference input channels [cond image | x | self_cond | lowres] (iv.py:1676, 1684, 1731), of which at most one of the cond
+            image and self_cond is there -> ours [x | lowres | 0.. (8)] ++ [self_cond or cond image | 0.. (auxp)]."""
+            assert w.shape[1] == cc + c + sc + nl and not (cc and sc)
             wp = torch.zeros(w.shape[0], 8 + auxp, *w.shape[2:])
-            wp[:, : w.shape[1] - cc] = w[:, cc:]
+            wp[:, :c] = w[:, cc: cc + c]
+            wp[:, c: c + nl] = w[:, cc + c + sc:]
+            wp[:, 8: 8 + sc] = w[:, c: c + sc]
             wp[:, 8: 8 + cc] = w[:, :cc]
             return wp
 

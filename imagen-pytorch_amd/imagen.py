@@ -469,9 +469,7 @@ class Imagen(nn.Module):
             ops.quantile(plan, absx0, quant, scratch, B=B, n=n, q=float(self.dynamic_thresholding_percentile))
         x0_thr = None
         if getattr(unet, 'self_cond', False):            # ip.py:2249: each step conditions on the previous step's thresholded x0
-            if video:
-                _out_of_scope("self-conditioning video unets")
-            x0_thr = torch.zeros(B, n, device=dev)
+            x0_thr = torch.zeros(B, n, device=dev)       # (video: the frame-major clip, as the state)
             eng.bind_self_cond(x0_thr)
             extra['x0_thr'] = x0_thr
         ops.ddpm_update(plan, eng.x_in, x0, quant if dyn else None, coef, noise, final, step_ptr, B=B, n_per_sample=n,

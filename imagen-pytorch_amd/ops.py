@@ -1359,9 +1359,11 @@ def lowres_prep(plan: Plan, img: torch.Tensor, noise: torch.Tensor, out: torch.T
 
 def lincomb(plan: Plan, t0, out, coef, step_ptr, *, B, n_per_sample, t1=None, t2=None, t3=None, q1=None, q3=None, out2=None,
             final_out=None, thr_mode: int = 0, final: bool = False, advance: bool = False, seed: int = 0, stream_id: int = 0,
-            sample_offset: int = 0, seed_ptr: Optional[torch.Tensor] = None, mask=None, mask_else=None, label: str = ""):
+            sample_offset: int = 0, seed_ptr: Optional[torch.Tensor] = None, mask=None, mask_else=None, thr1_out=None, thr3_out=None,
+            label: str = ""):
     """Per-step state update (ImagenLincombParams): out = w0*t0 + w1*thr(t1) + w2*t2 + w3*thr(t3) + w4*z, out2 = w5*out,
-    weights = coef[*step_ptr, 0:6]; with `mask` (fp32 0/1, same shape) out keeps `mask_else` where the mask is 0."""
+    weights = coef[*step_ptr, 0:6]; with `mask` (fp32 0/1, same shape) out keeps `mask_else` where the mask is 0.  `thr1_out` /
+    `thr3_out` (fp32, same shape, aliasing nothing else of the launch) receive thr(t1) / thr(t3) as summed."""
     p = STRUCTS["ImagenLincombParams"]()
     p.t0, p.t1, p.t2, p.t3 = t0.data_ptr(), ptr(t1), ptr(t2), ptr(t3)
     p.q1, p.q3, p.out, p.out2, p.final_out = ptr(q1), ptr(q3), out.data_ptr(), ptr(out2), ptr(final_out)
@@ -1369,9 +1371,12 @@ def lincomb(plan: Plan, t0, out, coef, step_ptr, *, B, n_per_sample, t1=None, t2
     p.B, p.n_per_sample, p.thr_mode, p.final, p.advance, p.sample_offset = B, n_per_sample, thr_mode, int(final), int(advance), sample_offset
     p.seed_lo, p.seed_hi, p.stream_id = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, stream_id
     p.mask, p.mask_else = ptr(mask), ptr(mask_else)
+    p.thr1_out, p.thr3_out = ptr(thr1_out), ptr(thr3_out)
     assert coef.dtype == torch.float32 and coef.shape[-1] == 8
+    for o in (thr1_out, thr3_out):
+        assert o is None or (o.dtype == torch.float32 and o.numel() == B * n_per_sample and o.is_contiguous())
     assert mask is None or (mask.dtype == torch.float32 and mask_else is not None and mask.numel() == B * n_per_sample)
-    plan.add(p, label or "lincomb", [t0, t1, t2, t3, q1, q3, out, out2, final_out, coef, step_ptr, seed_ptr, mask, mask_else])
+    plan.add(p, label or "lincomb", [t0, t1, t2, t3, q1, q3, out, out2, final_out, coef, step_ptr, seed_ptr, mask, mask_else, thr1_out, thr3_out])
     return p
 
 

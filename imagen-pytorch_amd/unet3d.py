@@ -86,11 +86,13 @@ class Unet3D(nn.Module):
         for name in ('use_linear_attn', 'use_linear_cross_attn'):
             if any(_cast_tuple(self._locals[name])):
                 _unsupported(name)
-        for name in ('cross_embed_downsample', 'self_cond', 'combine_upsample_fmaps', 'init_conv_to_final_conv_residual'):
+        for name in ('cross_embed_downsample', 'combine_upsample_fmaps', 'init_conv_to_final_conv_residual'):
             if self._locals[name]:
                 _unsupported(name)
         if not pixel_shuffle_upsample:
             _unsupported('pixel_shuffle_upsample=False')
+        if self_cond and cond_images_channels:
+            _unsupported('self_cond together with cond_images_channels')
         if attn_dim_head not in (32, 64):
             raise NotImplementedError(f"attn_dim_head = {attn_dim_head}: the attention kernels (temporal attention included) are built for head dims 64 "
                                       "(every README config) and 32 (the reference's Unet3DConfig default, configs.py:61-62)")
@@ -98,7 +100,7 @@ class Unet3D(nn.Module):
         self.self_cond = self_cond
         self.channels = channels
         self.channels_out = channels_out if channels_out is not None else channels
-        init_channels = channels * (1 + int(lowres_cond))
+        init_channels = channels * (1 + int(lowres_cond) + int(self_cond))          # iv.py:1302
         init_dim = init_dim if init_dim is not None else dim
         self.has_cond_image = cond_images_channels > 0            # iv.py:1307-1310: extra input channels of the init conv
         self.cond_images_channels = cond_images_channels
@@ -285,7 +287,6 @@ class Unet3D(nn.Module):
     @torch.no_grad()
     def _run(self, x, time, *, lowres_cond_img=None, lowres_noise_times=None, text_embeds=None, text_mask=None, cond_drop_prob=0.,
              ignore_time=False, cfg=False, cond_images=None, cond_video_frames=None, post_cond_video_frames=None, self_cond=None):
-        assert self_cond is None, 'self_cond: Unet3D is built without self-conditioning in this build'
         assert not (self.has_cond_image ^ (cond_images is not None)), \
             'you either requested to condition on an image on the unet, but the conditioning image is not supplied, or vice versa'   # iv.py:1722
         if cond_images is not None:
@@ -309,6 +310,8 @@ class Unet3D(nn.Module):
             eng.set_cond_video_frames(cond_video_frames, post_cond_video_frames)
         if cond_images is not None:
             eng.set_cond_images(cond_images)
+        if self.self_cond:                           # None: zeros (iv.py:1674-1676); a unet built without self_cond ignores the argument
+            eng.set_self_cond(None if self_cond is None else self_cond.float().permute(0, 2, 1, 3, 4))
         if cfg:
             keep = torch.cat((torch.ones(B, dtype=torch.bool), torch.zeros(B, dtype=torch.bool)))
         elif cond_drop_prob == 0:

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define IMAGEN_ABI_VERSION 12 /* 12: ImagenTemporalAttentionParams.head_dim (the temporal attention of Imagen-Video at head dim 32, the reference's Unet3DConfig default; 0 = 64: plans of before are unchanged);  11: ImagenDdpmUpdateParams.row_keys (per-row Philox key + sample index: requests merged into one batch draw their own noise);  10: ImagenIgemmParams.pad_x1 (a KH x KW window with its own x padding: the causal temporal conv of Imagen-Video as ONE (3 x 1)-tap launch);  9: LINEAR_F32, SCALE_SHIFT ss_f32;  8: ROWCHAIN, the latency probes;  3: head_dim in the attention / QNORM / KV_PREP params; 4: DDPM_UPDATE x0_thr; 5: GCA_TAIL; 6: ACT_PREP self_stat, STEP_SLICE;
+#define IMAGEN_ABI_VERSION 13 /* 13: ImagenLincombParams.thr1_out / thr3_out (LINCOMB writes out the thresholded operands it sums: the self-conditioning input of the ElucidatedImagen sampler; NULL = the launch of before);  12: ImagenTemporalAttentionParams.head_dim (the temporal attention of Imagen-Video at head dim 32, the reference's Unet3DConfig default; 0 = 64: plans of before are unchanged);  11: ImagenDdpmUpdateParams.row_keys (per-row Philox key + sample index: requests merged into one batch draw their own noise);  10: ImagenIgemmParams.pad_x1 (a KH x KW window with its own x padding: the causal temporal conv of Imagen-Video as ONE (3 x 1)-tap launch);  9: LINEAR_F32, SCALE_SHIFT ss_f32;  8: ROWCHAIN, the latency probes;  3: head_dim in the attention / QNORM / KV_PREP params; 4: DDPM_UPDATE x0_thr; 5: GCA_TAIL; 6: ACT_PREP self_stat, STEP_SLICE;
                                * 7: every launch carries sizeof(its params struct) (a stale mirror of a struct fails loudly), ImagenIgemmParams.dbg -> launcher_word, kernel families 6 and 7, ImagenAttentionParams.softmax_mode */
 
 typedef void* imagen_stream_t; /* hipStream_t */
@@ -401,7 +401,11 @@ typedef struct ImagenLowresPrepParams {
  * final != 0: final_out = (clamp(out, -1, 1) + 1)/2 (:540, unnormalize_img).  advance != 0: *step_ptr += 1 afterwards.
  * mask != NULL: out = mask[i] != 0 ? (the sum above) : mask_else[i] — the inpainting blend `img * ~mask + q_sample(inpaint) * mask`
  * (ip.py:2244-2246) with t0 = the known image, w0 = alpha_t, w4 = sigma_t; the same op with t0 = x re-noises x_{t_next} -> x_t
- * (q_sample_from_to, ip.py:286-307).  In-place use (out == mask_else or out == t0) is allowed. */
+ * (q_sample_from_to, ip.py:286-307).  In-place use (out == mask_else or out == t0) is allowed.
+ * thr1_out / thr3_out (optional): receive thr(t1, q1) / thr(t3, q3), exactly the value that enters the sum, whatever its weight w1 / w3 and
+ * whatever the mask — the clamped model output the sampler hands to a self-conditioning unet as the next evaluation's `self_cond`
+ * (elucidated_imagen.py:496, 518, 538).  thr1_out needs t1, thr3_out needs t3; neither may alias out, out2, final_out, the other one or any
+ * input of the same launch (another thread's group may still be unread).  Both NULL: the launch is the one of ABI 12. */
 typedef struct ImagenLincombParams {
   const float* t0; const float* t1; const float* t2; const float* t3;  /* fp32 [B, n_per_sample]; t1..t3 may be NULL */
   const float* q1; const float* q3;   /* [B] quantiles for thr_mode 1 */
@@ -411,6 +415,7 @@ typedef struct ImagenLincombParams {
   int32_t B, n_per_sample, thr_mode, final, advance, sample_offset;
   uint32_t seed_lo, seed_hi, stream_id;
   const float* mask; const float* mask_else;  /* optional fp32 [B, n_per_sample] 0/1 mask and the image kept where it is 0 */
+  float* thr1_out; float* thr3_out;           /* optional fp32 [B, n_per_sample]: the thresholded t1 / t3 as summed (ABI 13) */
 } ImagenLincombParams;
 
 /* STEP_SLICE — the part of the denoiser that depends on the timestep and the request's conditioning but NOT on x_t: time embedding ->
