@@ -120,6 +120,8 @@ OP_STRUCT = {
     ENUMS["IMAGEN_OP_STEP_SLICE"]: STRUCTS["ImagenStepSliceParams"],
     ENUMS["IMAGEN_OP_ROWCHAIN"]: STRUCTS["ImagenRowchainParams"],
     ENUMS["IMAGEN_OP_LINEAR_F32"]: STRUCTS["ImagenLinearF32Params"],
+    ENUMS["IMAGEN_OP_LINCTX"]: STRUCTS["ImagenLinCtxParams"],
+    ENUMS["IMAGEN_OP_LINEAR_XATTN"]: STRUCTS["ImagenLinearXattnParams"],
 }
 STRUCT_KIND = {v: k for k, v in OP_STRUCT.items()}
 

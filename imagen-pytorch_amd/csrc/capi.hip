@@ -50,6 +50,8 @@ extern "C" size_t imagen_sizeof(int kind) {
     case IMAGEN_OP_STEP_SLICE: return sizeof(ImagenStepSliceParams);
     case IMAGEN_OP_ROWCHAIN: return sizeof(ImagenRowchainParams);
     case IMAGEN_OP_LINEAR_F32: return sizeof(ImagenLinearF32Params);
+    case IMAGEN_OP_LINCTX: return sizeof(ImagenLinCtxParams);
+    case IMAGEN_OP_LINEAR_XATTN: return sizeof(ImagenLinearXattnParams);
     default: return 0;
   }
 }
@@ -93,6 +95,8 @@ extern "C" int imagen_launch(int kind, const void* params, size_t params_bytes, 
     case IMAGEN_OP_STEP_SLICE: return launch_step_slice(static_cast<const ImagenStepSliceParams*>(params), s);
     case IMAGEN_OP_ROWCHAIN: return launch_rowchain(static_cast<const ImagenRowchainParams*>(params), s);
     case IMAGEN_OP_LINEAR_F32: return launch_linear_f32(static_cast<const ImagenLinearF32Params*>(params), s);
+    case IMAGEN_OP_LINCTX: return launch_linctx(static_cast<const ImagenLinCtxParams*>(params), s);
+    case IMAGEN_OP_LINEAR_XATTN: return launch_linear_xattn(static_cast<const ImagenLinearXattnParams*>(params), s);
     default: imagen_set_error("imagen_launch: unknown op kind %d", kind); return -1;
   }
 }

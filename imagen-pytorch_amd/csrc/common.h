@@ -122,3 +122,5 @@ int launch_act_prep(const ImagenActPrepParams* p, hipStream_t s);
 int launch_gca_tail(const ImagenGcaTailParams* p, hipStream_t s);
 int launch_step_slice(const ImagenStepSliceParams* p, hipStream_t s);
 int launch_rowchain(const ImagenRowchainParams* p, hipStream_t s);
+int launch_linctx(const ImagenLinCtxParams* p, hipStream_t s);
+int launch_linear_xattn(const ImagenLinearXattnParams* p, hipStream_t s);

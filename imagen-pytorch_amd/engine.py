@@ -354,6 +354,7 @@ class UnetEngine:
         # ---- now that every attention site is known: the per-step conditioning K/V ops, spliced in before the traversal
         dyn = Plan("kv-dynamic")
         self._dyn_proj = self._emit_context_kv(dyn, self.c_time, rows_per_batch=self.ntt, k_row0_self=0, k_row0_cross=1, tag="dyn")
+        self._emit_linctx(dyn)
         plan.ops[self._kv_dynamic_anchor:self._kv_dynamic_anchor] = dyn.ops
         self._time_chain_ops += [st for _, st, label in dyn.ops if label in self._TIME_CHAIN]
         plan.keep.extend(dyn.keep)
@@ -623,6 +624,8 @@ class UnetEngine:
 
     # ---- CrossAttention inside a ResnetBlock (ip.py:745-751, 759-834)
     def _cross_attn(self, plan, h: Act, ca: CrossAttentionP, name: str) -> Act:
+        if getattr(ca, "linear", False):   # (the video path's cross-attention container has no linear form: Unet3D refuses the flag)
+            return self._linear_cross_attn(plan, h, ca, name)
         W, R = self.W, self.R
         N, C = h.H * h.W, h.C
         heads, dh = ca.heads, ca.dim_head
@@ -660,6 +663,35 @@ class UnetEngine:
         y = self.new(R, 1, N, C)
         ops.igemm(plan, o, wo, y, label=name + ".to_out")
         ops.ln_residual(plan, y, g_out, out.tokens(), res=tok, eps=1e-5, ssq_out=out.ssq, label=name + ".out_norm")
+        return out
+
+    # ---- LinearCrossAttention inside a ResnetBlock (ip.py:745-751, 836-874; Unet(use_linear_cross_attn=...))
+    def _linear_cross_attn(self, plan, h: Act, ca: CrossAttentionP, name: str) -> Act:
+        """LayerNorm -> to_q -> o = 8 softmax_d(q) M -> to_out -> LayerNorm + residual, one launch each at every resolution (no ROWCHAIN mode
+        for it yet: q and o make one HBM round trip each).  M = softmax_j(k)^T v of the row's conditioning tokens comes from the LINCTX
+        launch at the head of the step plan (_emit_linctx); the site only registers its k | v row buffer here."""
+        W, R = self.W, self.R
+        N, C = h.H * h.W, h.C
+        heads, dh = ca.heads, ca.dim_head
+        inner = heads * dh
+        tok = h.tokens()
+        wq = W.conv(name + ".to_q", ca.to_q, split=SPLIT_1X1 and self._split_small(C, 1, inner, R * N))
+        wo = W.conv(name + ".to_out", ca.to_out[0], split=SPLIT_1X1 and self._split_small(inner, 1, C, R * N))
+        J = self.NT + 1
+        kv = torch.zeros(R, J, 2 * inner, dtype=torch.float16, device=self.dev)    # row 0: null_kv; [1, 1 + ntt): time tokens; then the static tokens
+        M = self.f32buf(R, heads, dh, dh)
+        self.attn_sites.append(dict(kind="linear", name=name, mod=ca, kv=kv, M=M, heads=heads, dh=dh, J=J))
+        out = self.new(R, h.H, h.W, C)
+        out.ssq = self.f32buf(R * N)
+        mu, rs = self.f32buf(R * N), self.f32buf(R * N)
+        ops.rowstat(plan, tok, mode=1, rs=rs, mu=mu, eps=1e-5, label=name + ".norm")
+        q = self.new(R, 1, N, inner)
+        ops.igemm(plan, tok, wq, q, mu=mu, rs=rs, pa=W.f32(name + ".norm.g", lambda: _pad_vec(ca.norm.g, wq.Cin_pad)), label=name + ".to_q")
+        o = self.new(R, 1, N, inner)
+        ops.linear_xattn(plan, q, M, o, heads=heads, head_dim=dh, rows_per_batch=N, label=name + ".linear_attn")
+        y = self.new(R, 1, N, C)
+        ops.igemm(plan, o, wo, y, label=name + ".to_out")
+        ops.ln_residual(plan, y, W.f32(name + ".out_g", lambda: ca.to_out[1].g), out.tokens(), res=tok, eps=1e-5, ssq_out=out.ssq, label=name + ".out_norm")
         return out
 
     # ---- TransformerBlock (ip.py:992-1022): depth x [multi-query self attention + FeedForward]
@@ -827,7 +859,7 @@ class UnetEngine:
         self-attention `to_context` = LayerNorm(affine) + Linear (ip.py:527): the LN affine is folded into the Linear, so all
         sites share one normalised input; cross-attention `to_kv` (ip.py:783) consumes c directly."""
         selfs = [s for s in self.attn_sites if s["kind"] == "self" and s["n_ctx"] > 0]
-        crosses = [s for s in self.attn_sites if s["kind"] == "cross"]
+        crosses = [s for s in self.attn_sites if s["kind"] in ("cross", "linear")]   # a linear site's to_kv is the same Linear (ip.py:836: a subclass)
 
         def make_self():
             ws, bs = [], []
@@ -874,6 +906,11 @@ class UnetEngine:
             for s in crosses:
                 d_ = s["dh"]
                 inner = s["heads"] * d_
+                if s["kind"] == "linear":   # the projected (k | v) rows as they are, behind the null row of the site's row buffer (no l2norm, no k_scale)
+                    ops.rows_copy(plan, st.t, s["kv"], B=R, rows=n, C=2 * inner, src_bs=n * wc.Cout, src_rs=wc.Cout, dst_bs=s["J"] * 2 * inner,
+                                  dst_rs=2 * inner, src_off=col, dst_off=k_row0_cross * 2 * inner, label=f"ctx.{tag}.linear_rows")
+                    col += 2 * inner
+                    continue
                 ops.kv_prep(plan, st.t, st.t, W.f32(s["name"] + ".k_scale", lambda s=s: s["mod"].k_scale), s["khat"], s["vt"], B=R,
                             heads=s["heads"], rows=n, r0=k_row0_cross, src_strides=(n * wc.Cout, wc.Cout, d_), k_strides=s["k_strides"],
                             vt_strides=s["vt_strides"], k_off=col, v_off=col + inner, batch=jobs, head_dim=d_)
@@ -883,10 +920,27 @@ class UnetEngine:
             ops.kv_prep_multi(plan, jobs, self.dev, label=f"kv_ctx.{tag}")
         return proj
 
+    def _emit_linctx(self, plan):
+        """M = softmax_j(k)^T v of every LinearCrossAttention site in ONE launch: once per denoiser evaluation, behind the launches that
+        put the time tokens' rows in place (the static rows and the null row are there since set_conditioning)."""
+        jobs = []
+        for s in self.attn_sites:
+            if s["kind"] == "linear":
+                inner = s["heads"] * s["dh"]
+                ops.linctx_job(s["kv"], s["M"], R=self.R, heads=s["heads"], head_dim=s["dh"], J=s["J"], kv_bs=s["J"] * 2 * inner, kv_rs=2 * inner, batch=jobs)
+        if jobs:
+            ops.linctx(plan, jobs, self.dev, label="linctx")
+
     def _emit_null_kv(self, plan):
         """learned null key/value (ip.py:545-547 self: after the context; ip.py:805-808 cross: first)."""
         R, W = self.R, self.W
         for s in self.attn_sites:
+            if s["kind"] == "linear":   # row 0 of the site's row buffer, raw (ip.py:849-852): (null k per head | null v per head)
+                inner = s["heads"] * s["dh"]
+                row = W.f16(s["name"] + ".null_row", lambda s=s: s["mod"].null_kv.detach().repeat(1, s["heads"]).reshape(-1))
+                ops.rows_copy(plan, row, s["kv"], B=R, rows=1, C=2 * inner, src_bs=0, src_rs=2 * inner, dst_bs=s["J"] * 2 * inner, dst_rs=2 * inner,
+                              label=s["name"] + ".kv_null")
+                continue
             nk = W.f32(s["name"] + ".null_kv", lambda s=s: s["mod"].null_kv)
             r0 = s["n_ctx"] if s["kind"] == "self" else 0
             ops.kv_prep(plan, nk, nk, W.f32(s["name"] + ".k_scale", lambda s=s: s["mod"].k_scale), s["khat"], s["vt"], B=R, heads=s["heads"],

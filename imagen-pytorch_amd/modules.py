@@ -73,12 +73,14 @@ class UpsampleCombinerP(Holder):
 
 
 class CrossAttentionP(Holder):
-    """ip.py:759-791."""
+    """ip.py:759-791.  linear=True: `LinearCrossAttention` (ip.py:836-874), a subclass with the same parameters (q_scale / k_scale stay
+    in the state_dict, unused) and another forward."""
 
-    def __init__(self, dim, context_dim, dim_head=64, heads=8):
+    def __init__(self, dim, context_dim, dim_head=64, heads=8, linear=False):
         super().__init__()
         inner = dim_head * heads
         self.heads, self.dim_head = heads, dim_head
+        self.linear = bool(linear)
         self.norm = GainNorm(dim)
         self.null_kv = nn.Parameter(torch.randn(2, dim_head))
         self.to_q = nn.Linear(dim, inner, bias=False)
@@ -137,11 +139,12 @@ class GlobalContextP(Holder):
 class ResnetBlockP(Holder):
     """ip.py:693-732."""
 
-    def __init__(self, dim, dim_out, *, cond_dim=None, time_cond_dim=None, use_gca=False, heads=8, dim_head=64):
+    def __init__(self, dim, dim_out, *, cond_dim=None, time_cond_dim=None, use_gca=False, heads=8, dim_head=64, linear_attn=False):
         super().__init__()
         self.dim, self.dim_out = dim, dim_out
         self.time_mlp = nn.Sequential(nn.SiLU(), nn.Linear(time_cond_dim, dim_out * 2)) if time_cond_dim is not None else None
-        self.cross_attn = CrossAttentionP(dim_out, cond_dim, dim_head=dim_head, heads=heads) if cond_dim is not None else None
+        # ip.py:719: `attn_klass = CrossAttention if not linear_attn else LinearCrossAttention`
+        self.cross_attn = CrossAttentionP(dim_out, cond_dim, dim_head=dim_head, heads=heads, linear=linear_attn) if cond_dim is not None else None
         self.block1 = BlockP(dim, dim_out)
         self.block2 = BlockP(dim_out, dim_out)
         self.gca = GlobalContextP(dim_out, dim_out) if use_gca else None

@@ -881,6 +881,52 @@ def kv_prep_multi(plan: Plan, batch: list, device, label: str = ""):
     return p
 
 
+def linctx_job(kv: torch.Tensor, M: torch.Tensor, *, R, heads, head_dim, J, kv_bs, kv_rs, batch: list):
+    """One site of a LINCTX launch (include/imagen_hip.h): kv fp16 rows (k | v) of J tokens per image, row 0 the null row; M fp32
+    [R, heads, head_dim, head_dim].  The launcher sees the jobs in device memory only, so the checks are made here."""
+    def refuse(msg):
+        raise _abi.ImagenHipError(f"linctx: job {len(batch)}: {msg}")
+    if head_dim not in (32, 64):
+        refuse(f"head_dim {head_dim}: the kernel is built for 64 and 32")
+    if not (R > 0 and heads > 0 and J > 0):
+        refuse("empty")
+    if kv.dtype != torch.float16 or M.dtype != torch.float32 or not M.is_contiguous() or M.numel() != R * heads * head_dim * head_dim:
+        refuse("kv must be fp16 and M a contiguous fp32 [R, heads, head_dim, head_dim]")
+    if kv_rs < 2 * heads * head_dim or kv_bs < J * kv_rs or kv.numel() < R * kv_bs:
+        refuse(f"kv strides ({kv_bs}, {kv_rs}) do not hold {J} rows of {2 * heads * head_dim}")
+    p = STRUCTS["ImagenLinCtxJob"]()
+    p.kv, p.M = kv.data_ptr(), M.data_ptr()
+    p.R, p.heads, p.head_dim, p.J, p.kv_bs, p.kv_rs = R, heads, head_dim, J, kv_bs, kv_rs
+    batch.append((p, [kv, M]))
+    return p
+
+
+def linctx(plan: Plan, batch: list, device, label: str = ""):
+    """One LINCTX launch for the jobs collected with linctx_job: their parameter blocks are uploaded once, at plan build."""
+    assert batch
+    blob = b"".join(bytes(j) for j, _ in batch)
+    jobs = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(device)
+    p = STRUCTS["ImagenLinCtxParams"]()
+    p.jobs, p.n = jobs.data_ptr(), len(batch)
+    p.max_bh = max(j.R * j.heads for j, _ in batch)
+    plan.add(p, label or "linctx", [jobs] + [t for _, keep in batch for t in keep])
+    return p
+
+
+def linear_xattn(plan: Plan, q: Act, M: torch.Tensor, o: Act, *, heads: int, head_dim: int, rows_per_batch: int, label: str = ""):
+    """LINEAR_XATTN (include/imagen_hip.h): o = 8 * softmax_d(q) M per (pixel, head); q, o: token rows of R images x rows_per_batch."""
+    assert head_dim in (32, 64), f"linear cross-attention head dim {head_dim}: the kernel is built for 64 and 32"
+    assert q.rows == o.rows and q.rows % rows_per_batch == 0 and q.C == o.C == heads * head_dim
+    assert q.bs == q.H * q.W * q.ld and o.bs == o.H * o.W * o.ld, "rows of consecutive images must be consecutive"
+    R = q.rows // rows_per_batch
+    assert M.dtype == torch.float32 and M.is_contiguous() and M.numel() == R * heads * head_dim * head_dim
+    p = STRUCTS["ImagenLinearXattnParams"]()
+    p.q, p.M, p.o = q.ptr, M.data_ptr(), o.ptr
+    p.R, p.heads, p.head_dim, p.rows, p.ld_q, p.ld_o = R, heads, head_dim, rows_per_batch, q.ld, o.ld
+    plan.add(p, label or "linear_xattn", [q.t, M, o.t])
+    return p
+
+
 def qnorm(plan: Plan, q: torch.Tensor, q_scale: torch.Tensor, *, rows, heads, ld, mult, label: str = "", head_dim: int = 64):
     assert head_dim in (32, 64)
     p = STRUCTS["ImagenQnormParams"]()

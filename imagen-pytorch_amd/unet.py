@@ -103,10 +103,8 @@ class Unet(nn.Module):
         self._locals = ctor_kwargs
 
         # ---- scope gate: flags with no kernel plan fail loudly at construction
-        for name in ('use_linear_attn', 'use_linear_cross_attn'):
-            v = self._locals[name]
-            if any(_cast_tuple(v)):
-                _unsupported(name)
+        if any(_cast_tuple(use_linear_attn)):
+            _unsupported('use_linear_attn')
         if cross_embed_downsample:
             # the reference cannot build this either: partial(CrossEmbedLayer, kernel_sizes=...) is called with (dim_in, dim_out)
             # positionally (ip.py:1315, 1357, 1366), so dim_out collides with kernel_sizes and Unet(...) raises TypeError — no
@@ -173,9 +171,10 @@ class Unet(nn.Module):
         layer_attns = _cast_tuple(layer_attns, num_layers)
         layer_attns_depth = _cast_tuple(layer_attns_depth, num_layers)
         layer_cross_attns = _cast_tuple(layer_cross_attns, num_layers)
+        use_linear_cross_attn = tuple(bool(v) for v in _cast_tuple(use_linear_cross_attn, num_layers))   # ip.py:1306
         self._layer_cfg = dict(in_out=in_out, num_resnet_blocks=num_resnet_blocks, layer_attns=layer_attns,
                                layer_attns_depth=layer_attns_depth, layer_cross_attns=layer_cross_attns,
-                               memory_efficient=memory_efficient, attend_at_middle=attend_at_middle,
+                               use_linear_cross_attn=use_linear_cross_attn, memory_efficient=memory_efficient, attend_at_middle=attend_at_middle,
                                layer_mid_attns_depth=layer_mid_attns_depth, init_dim=init_dim, dim=dim)
 
         resnet = partial(ResnetBlockP, **attn_kwargs)
@@ -188,10 +187,11 @@ class Unet(nn.Module):
         self.downs = nn.ModuleList([])
         self.ups = nn.ModuleList([])
         skip_connect_dims = []
-        for ind, ((dim_in, dim_out), n_blocks, l_attn, l_depth, l_cross) in enumerate(
-                zip(in_out, num_resnet_blocks, layer_attns, layer_attns_depth, layer_cross_attns)):
+        for ind, ((dim_in, dim_out), n_blocks, l_attn, l_depth, l_cross, l_linear) in enumerate(
+                zip(in_out, num_resnet_blocks, layer_attns, layer_attns_depth, layer_cross_attns, use_linear_cross_attn)):
             is_last = ind >= (num_layers - 1)
-            layer_cond_dim = cond_dim if l_cross else None
+            # ip.py:1341: the linear flag conditions the level's first block even where layer_cross_attns is False
+            layer_cond_dim = cond_dim if (l_cross or l_linear) else None
             current_dim = dim_in
             pre_downsample = None
             if memory_efficient:
@@ -203,7 +203,7 @@ class Unet(nn.Module):
                 post_downsample = downsample_p(current_dim, dim_out) if not is_last else ParallelP(dim_in, dim_out)
             self.downs.append(nn.ModuleList([
                 pre_downsample,
-                resnet(current_dim, current_dim, cond_dim=layer_cond_dim, time_cond_dim=time_cond_dim),
+                resnet(current_dim, current_dim, cond_dim=layer_cond_dim, linear_attn=l_linear, time_cond_dim=time_cond_dim),   # ip.py:1370
                 nn.ModuleList([ResnetBlockP(current_dim, current_dim, time_cond_dim=time_cond_dim, use_gca=use_global_context_attn)
                                for _ in range(n_blocks)]),
                 (TransformerBlockP(dim=current_dim, depth=l_depth, ff_mult=ff_mult, context_dim=cond_dim, **attn_kwargs)
@@ -219,15 +219,15 @@ class Unet(nn.Module):
 
         # up path (ip.py:1392-1413)
         upsample_fmap_dims = []
-        for ind, ((dim_in, dim_out), n_blocks, l_attn, l_depth, l_cross) in enumerate(
+        for ind, ((dim_in, dim_out), n_blocks, l_attn, l_depth, l_cross, l_linear) in enumerate(
                 zip(reversed(in_out), reversed(num_resnet_blocks), reversed(layer_attns), reversed(layer_attns_depth),
-                    reversed(layer_cross_attns))):
+                    reversed(layer_cross_attns), reversed(use_linear_cross_attn))):
             is_last = ind == (num_layers - 1)
-            layer_cond_dim = cond_dim if l_cross else None
+            layer_cond_dim = cond_dim if (l_cross or l_linear) else None          # ip.py:1395
             skip_connect_dim = skip_connect_dims.pop()
             upsample_fmap_dims.append(dim_out)
             self.ups.append(nn.ModuleList([
-                resnet(dim_out + skip_connect_dim, dim_out, cond_dim=layer_cond_dim, time_cond_dim=time_cond_dim),
+                resnet(dim_out + skip_connect_dim, dim_out, cond_dim=layer_cond_dim, linear_attn=l_linear, time_cond_dim=time_cond_dim),   # ip.py:1409
                 nn.ModuleList([ResnetBlockP(dim_out + skip_connect_dim, dim_out, time_cond_dim=time_cond_dim, use_gca=use_global_context_attn)
                                for _ in range(n_blocks)]),
                 (TransformerBlockP(dim=dim_out, depth=l_depth, ff_mult=ff_mult, context_dim=cond_dim, **attn_kwargs)

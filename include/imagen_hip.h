@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define IMAGEN_ABI_VERSION 13 /* 13: ImagenLincombParams.thr1_out / thr3_out (LINCOMB writes out the thresholded operands it sums: the self-conditioning input of the ElucidatedImagen sampler; NULL = the launch of before);  12: ImagenTemporalAttentionParams.head_dim (the temporal attention of Imagen-Video at head dim 32, the reference's Unet3DConfig default; 0 = 64: plans of before are unchanged);  11: ImagenDdpmUpdateParams.row_keys (per-row Philox key + sample index: requests merged into one batch draw their own noise);  10: ImagenIgemmParams.pad_x1 (a KH x KW window with its own x padding: the causal temporal conv of Imagen-Video as ONE (3 x 1)-tap launch);  9: LINEAR_F32, SCALE_SHIFT ss_f32;  8: ROWCHAIN, the latency probes;  3: head_dim in the attention / QNORM / KV_PREP params; 4: DDPM_UPDATE x0_thr; 5: GCA_TAIL; 6: ACT_PREP self_stat, STEP_SLICE;
+#define IMAGEN_ABI_VERSION 14 /* 14: LINCTX, LINEAR_XATTN (LinearCrossAttention: Unet(use_linear_cross_attn=...); no struct of before changed);  13: ImagenLincombParams.thr1_out / thr3_out (LINCOMB writes out the thresholded operands it sums: the self-conditioning input of the ElucidatedImagen sampler; NULL = the launch of before);  12: ImagenTemporalAttentionParams.head_dim (the temporal attention of Imagen-Video at head dim 32, the reference's Unet3DConfig default; 0 = 64: plans of before are unchanged);  11: ImagenDdpmUpdateParams.row_keys (per-row Philox key + sample index: requests merged into one batch draw their own noise);  10: ImagenIgemmParams.pad_x1 (a KH x KW window with its own x padding: the causal temporal conv of Imagen-Video as ONE (3 x 1)-tap launch);  9: LINEAR_F32, SCALE_SHIFT ss_f32;  8: ROWCHAIN, the latency probes;  3: head_dim in the attention / QNORM / KV_PREP params; 4: DDPM_UPDATE x0_thr; 5: GCA_TAIL; 6: ACT_PREP self_stat, STEP_SLICE;
                                * 7: every launch carries sizeof(its params struct) (a stale mirror of a struct fails loudly), ImagenIgemmParams.dbg -> launcher_word, kernel families 6 and 7, ImagenAttentionParams.softmax_mode */
 
 typedef void* imagen_stream_t; /* hipStream_t */
@@ -67,7 +67,9 @@ enum ImagenOpKind {
   IMAGEN_OP_STEP_SLICE = 28,   /* copy the current step's rows of up to four per-step tables (the timestep-only conditioning, computed for all steps at once) into the buffers the step's kernels read */
   IMAGEN_OP_ROWCHAIN = 29,     /* a chain of row-local token layers (attention out-projection + LayerNorm + FeedForward | a whole cross-attention | LayerNorm + q/k/v projection + K^/V^T rows) in ONE launch */
   IMAGEN_OP_LINEAR_F32 = 30,   /* a Linear on per-sample vectors in fp32 end to end (the timestep-conditioning chain: to_time_cond, the ResnetBlocks' time MLPs) */
-  IMAGEN_OP_KIND_COUNT = 31
+  IMAGEN_OP_LINCTX = 31,       /* LinearCrossAttention: per (row, head) the column softmax of k over the conditioning tokens and M = k^T v, for every site in ONE launch */
+  IMAGEN_OP_LINEAR_XATTN = 32, /* LinearCrossAttention: o = 8 * softmax_d(q) M per (pixel, head), on MFMA */
+  IMAGEN_OP_KIND_COUNT = 33
 };
 
 /* ------------------------------------------------------------------------------------------------
@@ -207,6 +209,34 @@ typedef struct ImagenKvPrepParams {
 typedef struct ImagenKvPrepMultiParams {
   const ImagenKvPrepParams* jobs; int32_t n, max_rows, max_bh; /* max over the jobs of rows and B*heads (grid extents) */
 } ImagenKvPrepMultiParams;
+
+/* LINCTX — the conditioning side of LinearCrossAttention.forward (ip.py:836-874; lines 843-852 k, v and the null row, 867 the softmax of k
+ * over the tokens, 871 `context = einsum('b n d, b n e -> b d e', k, v)`).  The ResnetBlock calls it without a mask (ip.py:749), so none is applied.
+ * One job per attention site, grid.z = job, one workgroup per (row, head):
+ *   kv row j of image r at kv + r*kv_bs + j*kv_rs: fp16 (k | v), heads side by side (k of head h at column h*head_dim, v at heads*head_dim +
+ *   h*head_dim) — to_kv's output row as it is; row 0 is the null key / value, raw (no l2norm, no k_scale: the linear form has neither)
+ *   w[j][a]       = softmax over j in [0, J) of k[r][j][h][a]                  (fp32)
+ *   M[r][h][a][b] = sum_j w[j][a] * v[r][j][h][b]                              (fp32 [R][heads][head_dim][head_dim])
+ * M depends on the conditioning tokens of the row only: one launch per denoiser evaluation serves every pixel of every site. */
+typedef struct ImagenLinCtxJob {
+  const void* kv; float* M;
+  int32_t R, heads, head_dim, J;   /* head_dim: 64 or 32 */
+  int32_t kv_bs, kv_rs;            /* elements */
+} ImagenLinCtxJob;
+typedef struct ImagenLinCtxParams {
+  const ImagenLinCtxJob* jobs; int32_t n, max_bh; /* `jobs`: DEVICE array of n jobs; max_bh = max over the jobs of R*heads (grid extent) */
+} ImagenLinCtxParams;
+
+/* LINEAR_XATTN — the pixel side of LinearCrossAttention.forward (ip.py:866 `q.softmax(dim = -1)`, 869 `q * self.scale` with scale = 8,
+ * 872 `einsum('b n d, b d e -> b n e', q, context)`):
+ *   o[r*rows + n][h*head_dim + b] = 8 * sum_a softmax_a(q[r*rows + n][h*head_dim + a]) * M[r][h][a][b]
+ * q, o: fp16 token rows (row strides ld_q / ld_o elements); M: fp32 as LINCTX writes it.  The softmax and the accumulation are fp32; the
+ * product runs on MFMA with both operands as fp16 (hi, lo) pairs.  `rows` (pixels per image) is arbitrary. */
+typedef struct ImagenLinearXattnParams {
+  const void* q; const float* M; void* o;
+  int32_t R, heads, head_dim, rows;   /* head_dim: 64 or 32 */
+  int32_t ld_q, ld_o;
+} ImagenLinearXattnParams;
 
 /* ---- Imagen-Video (imagen_pytorch/imagen_video.py = "iv.py") ----------------------------------------------------------------
  * Video activations are fp16 [B, F, P, C]: the F frames of a clip are consecutive NHWC images of P = H*W pixels, so every per-frame
