@@ -1,5 +1,6 @@
 // temporal.hip — the two kernels the Imagen-Video denoiser (Unet3D) adds to the image path: the depthwise temporal PEG and the
-// per-pixel attention over the frame axis (a vector kernel for any F <= 32, and — round 4 — the MFMA kernel that takes every F <= 31).
+// per-pixel attention over the frame axis (a vector kernel for any F <= 32, — round 4 — the MFMA kernel that takes every F <= 31, and
+// — ABI 15 — the tiled MFMA kernel for clips of 33 .. 128 frames).
 #include "common.h"
 
 namespace {
@@ -323,8 +324,218 @@ __global__ __launch_bounds__(256) void temporal_attention_mfma_kernel(const Imag
   }
 }
 
+// ---- clips of 33 .. 128 frames (ABI 15): the keys no longer fit one 32-key tile, so they are walked in tiles of 32 frames with an online
+// softmax.  One WORKGROUP owns one (clip, pixel): its F key and value rows are normalised once into LDS — K^ as fp16 hi + lo rows (the
+// mfma kernel's operand precision, q_scale * scale riding on K^), V^T as [D dims][Fp keys] fp16, Fp = F rounded up to 32, the rows and
+// columns F .. Fp - 1 zero — 54 016 B at F = 128, D = 64 (an fp32 image of the same rows would be 66 KB), two workgroups per CU.  The four
+// waves share the pixel's heads x F query rows, each walking every fourth block of 32 rows; per (block, key tile) S^T = K^ . Q^T and
+// O^T += V^T . P are the mfma kernel's products, layouts and hi + lo splits.  The null key never enters a tile: its logit is an fp32 dot
+// product on the VALU and it SEEDS the running state of every row (maximum = its logit, sum = 1, accumulator = the fp32 null value), so the
+// null value is applied in fp32 throughout, a row always has a visible key and the running maximum is finite from the start — masked and
+// missing keys get weight 0 by a select, never through exp(-inf).  Under the causal mask a tile whose first frame lies behind every row
+// of the block is skipped; the bias rows are read from global memory (528 KB at F = 128 with 8 heads: L2, not LDS).
+constexpr int kMaxFramesLong = 128;
+
+template <int D>
+__global__ __launch_bounds__(256) void temporal_attention_long_kernel(const ImagenTemporalAttentionParams p) {
+  extern __shared__ float lds[];
+  constexpr int KS = D / 16;          // 16-dim K steps of S^T
+  constexpr int DB = D / 32;          // 32-dim blocks of O^T
+  constexpr int CH = D / 8;           // 8-half chunks per key / value row: the lanes that stage one row
+  constexpr int KROW = D * 2 + 16;    // LDS bytes per K^ row (16 B of padding: the ds_read_b128 of a fragment spreads over the banks)
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int half = lane >> 5, l31 = lane & 31;
+  const int F = p.F, J = F + 1, T = (F + 31) >> 5, Fp = T * 32;
+  const int vrow = Fp * 2 + 8;        // LDS bytes per V^T row (kTaVtRow at Fp = 32)
+  char* s_kh = reinterpret_cast<char*>(lds);
+  char* s_kl = s_kh + (size_t)Fp * KROW;
+  char* s_vt = s_kl + (size_t)Fp * KROW;
+  const size_t item = blockIdx.x;                           // (b, px): the grid is exactly B * P workgroups
+  const int b = (int)(item / p.P), px = (int)(item - (size_t)b * p.P);
+  const f16* base = reinterpret_cast<const f16*>(p.qkv) + ((size_t)b * F * p.P + px) * p.ld;
+  const size_t fstride = (size_t)p.P * p.ld;
+  const int inner = p.heads * D;
+  // ---- stage K^ (hi, lo) and V^T: CH consecutive lanes own one frame, 8 dims each; 256 / CH frames per pass (a wave's frames are
+  //      consecutive and Fp is a multiple of 32, so the trip count is wave-uniform)
+  {
+    const int c = threadIdx.x % CH;
+    float ksc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) ksc[e] = p.k_scale[8 * c + e] * p.q_scale[8 * c + e] * p.scale;
+    for (int j = threadIdx.x / CH; j < Fp; j += 256 / CH) {
+      float kx[8];
+      f16x8 v;
+      if (j < F) {
+        const f16* row = base + (size_t)j * fstride + inner + 8 * c;
+        const f16x8 k = *reinterpret_cast<const f16x8*>(row);
+        v = *reinterpret_cast<const f16x8*>(row + D);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) kx[e] = (float)k[e];
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          kx[e] = 0.f;
+          v[e] = (f16)0.f;
+        }
+      }
+      float ssq = 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) ssq += kx[e] * kx[e];
+#pragma unroll
+      for (int off = CH / 2; off > 0; off >>= 1) ssq += __shfl_xor(ssq, off);
+      const float inv = 1.0f / fmaxf(sqrtf(ssq), 1e-12f);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) kx[e] *= inv * ksc[e];
+      f16x8 hi, lo;
+      ta_split(kx, hi, lo);
+      *reinterpret_cast<f16x8*>(s_kh + (size_t)j * KROW + 16 * c) = hi;
+      *reinterpret_cast<f16x8*>(s_kl + (size_t)j * KROW + 16 * c) = lo;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) *reinterpret_cast<f16*>(s_vt + (size_t)(8 * c + e) * vrow + 2 * j) = v[e];
+    }
+  }
+  // ---- the null key, normalised and scaled in fp32, beside the tiles (every block of rows reads its dims back: 32 registers less
+  //      than holding them across the row loop, which is what keeps D = 64 at two waves per SIMD)
+  float* s_nk = reinterpret_cast<float*>(s_vt + (size_t)D * vrow);
+  if (threadIdx.x < D) {
+    const int d = threadIdx.x;
+    float ssq = 0.f;
+    for (int e = 0; e < D; ++e) ssq += p.null_kv[e] * p.null_kv[e];
+    s_nk[d] = p.null_kv[d] * (1.0f / fmaxf(sqrtf(ssq), 1e-12f)) * (p.k_scale[d] * p.q_scale[d] * p.scale);
+  }
+  __syncthreads();   // the only workgroup barrier: every wave reads what all four staged
+  const int rows = p.heads * F;
+  f16* obase = reinterpret_cast<f16*>(p.o) + ((size_t)b * F * p.P + px) * p.ld_o;
+  const size_t ostride = (size_t)p.P * p.ld_o;
+  for (int r0 = 32 * wave; r0 < rows; r0 += 128) {
+    // ---- Q^ fragments of row r0 + l31 = (head, frame) (B operand: lane = row), the unit row as fp16 hi + lo
+    const int r = r0 + l31;
+    const bool rok = r < rows;
+    const int h = rok ? r / F : 0, i = rok ? r - h * F : 0;
+    f16x8 qh[KS], ql[KS];
+    float s_null = 0.f;
+    {
+      float qx[KS][8];
+      float ssq = 0.f;
+#pragma unroll
+      for (int s = 0; s < KS; ++s) {
+        const f16x8 q = *reinterpret_cast<const f16x8*>(base + (size_t)i * fstride + h * D + 16 * s + 8 * half);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          qx[s][e] = (float)q[e];
+          ssq += qx[s][e] * qx[s][e];
+        }
+      }
+      ssq += __shfl_xor(ssq, 32);
+      const float inv = 1.0f / fmaxf(sqrtf(ssq), 1e-12f);
+#pragma unroll
+      for (int s = 0; s < KS; ++s) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          qx[s][e] *= inv;
+          s_null += qx[s][e] * s_nk[16 * s + 8 * half + e];
+        }
+        ta_split(qx[s], qh[s], ql[s]);
+      }
+      s_null += __shfl_xor(s_null, 32);
+    }
+    const float* brow = p.bias + ((size_t)h * F + i) * J;   // column 0: the null key; column 1 + j: frame j
+    // ---- the running state of the row, seeded by the null key: both lanes of a row hold the same maximum and sum
+    float mx = s_null + brow[0], den = 1.f;
+    f32x16 oacc[DB];
+#pragma unroll
+    for (int db = 0; db < DB; ++db)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) oacc[db][e] = p.null_kv[D + 32 * db + 8 * (e >> 2) + 4 * half + (e & 3)];   // the fp32 null value, weight 1
+    // the last frame any row of the block sees: a block that crosses a head boundary holds frame F - 1
+    const int r_last = min(r0 + 31, rows - 1);
+    const int h_last = r_last / F;
+    const int i_max = (r0 / F != h_last) ? F - 1 : r_last - h_last * F;
+    const int t_end = p.causal ? (i_max >> 5) : T - 1;
+    const int lastf = p.causal ? i : F - 1;                 // frames 0 .. lastf are visible to this row
+    for (int t = 0; t <= t_end; ++t) {
+      // ---- S^T[key][row]: register e of this lane = frame 32 t + (e & 3) + 8 (e >> 2) + 4 half of row l31
+      f32x16 sacc;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) sacc[e] = 0.f;
+#pragma unroll
+      for (int s = 0; s < KS; ++s) {
+        const size_t at = (size_t)(32 * t + l31) * KROW + (16 * s + 8 * half) * 2;
+        const f16x8 kh = *reinterpret_cast<const f16x8*>(s_kh + at);
+        const f16x8 kl = *reinterpret_cast<const f16x8*>(s_kl + at);
+        sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qh[s], sacc, 0, 0, 0);
+        sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, ql[s], sacc, 0, 0, 0);
+        sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[s], sacc, 0, 0, 0);
+      }
+      // ---- bias, causal mask, the tile's maximum over the visible frames (-3e38 when the row sees none of them: the state stays)
+      float tmx = -3.0e38f;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int j = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * half;
+        const bool vis = j <= lastf;                        // (lastf < F: the missing frames of a partial tile are never visible)
+        sacc[e] = vis ? sacc[e] + brow[vis ? 1 + j : 0] : -3.0e38f;
+        tmx = fmaxf(tmx, sacc[e]);
+      }
+      tmx = fmaxf(tmx, __shfl_xor(tmx, 32));
+      const float mn = fmaxf(mx, tmx);
+      const float c = __expf(mx - mn);                      // mx is finite: 0 < c <= 1
+      float sum = 0.f;
+      f16x8 pf[2], pl[2];   // the weights as fp16 hi + lo pairs, as in the mfma kernel
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const float w = sacc[e] > -1.0e38f ? __expf(sacc[e] - mn) : 0.f;
+        sum += w;
+        const f16 wh = (f16)w;
+        pf[e >> 3][e & 7] = wh;
+        pl[e >> 3][e & 7] = (f16)(w - (float)wh);
+      }
+      sum += __shfl_xor(sum, 32);
+      den = den * c + sum;
+      mx = mn;
+      // ---- O^T[d][row] = c O^T + V^T . P   (the row is the lane: one factor per lane)
+#pragma unroll
+      for (int db = 0; db < DB; ++db)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) oacc[db][e] *= c;
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int db = 0; db < DB; ++db) {
+          const char* vr = s_vt + (size_t)(32 * db + l31) * vrow + (32 * t + 16 * s + 4 * half) * 2;
+          const uint2 lo = *reinterpret_cast<const uint2*>(vr);
+          const uint2 hi = *reinterpret_cast<const uint2*>(vr + 16);
+          uint4 packed = make_uint4(lo.x, lo.y, hi.x, hi.y);
+          const f16x8 vf = *reinterpret_cast<const f16x8*>(&packed);
+          oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pl[s], oacc[db], 0, 0, 0);
+          oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[s], oacc[db], 0, 0, 0);
+        }
+    }
+    if (rok) {
+      const float inv = 1.0f / den;
+      f16* o = obase + (size_t)i * ostride + h * D;
+#pragma unroll
+      for (int db = 0; db < DB; ++db)
+#pragma unroll
+        for (int qd = 0; qd < 4; ++qd) {
+          f16x4 v;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = (f16)(oacc[db][4 * qd + e] * inv);
+          *reinterpret_cast<f16x4*>(o + 32 * db + 8 * qd + 4 * half) = v;
+        }
+    }
+  }
+}
+
 template <int D>
 int launch_temporal_attention_d(const ImagenTemporalAttentionParams* p, hipStream_t s) {
+  if (p->F > kMaxFrames) {   // 33 .. 128 frames: the tiled kernel; it has no unaligned form (a lane loads 8 halfs of a qkv row, stores 4 of an o row)
+    IMAGEN_CHECK(p->ld % 8 == 0 && p->ld_o % 4 == 0 && ((size_t)p->qkv & 15) == 0 && ((size_t)p->o & 7) == 0,
+                 "temporal_attention: F > 32 needs ld % 8 == 0, ld_o % 4 == 0, qkv 16-byte and o 8-byte aligned");
+    const int Fp = (p->F + 31) & ~31;
+    const size_t lds_long = (size_t)2 * Fp * (D * 2 + 16) + (size_t)D * (Fp * 2 + 8) + D * sizeof(float);   // K^ hi + lo rows, V^T, the null key: 54 016 B at F = 128, D = 64
+    hipLaunchKernelGGL(temporal_attention_long_kernel<D>, dim3((unsigned)((size_t)p->B * p->P)), dim3(256), lds_long, s, *p);
+    return imagen_hip_status("temporal_attention");
+  }
   const size_t items = (size_t)p->B * p->P;
   const size_t nb = (size_t)p->heads * p->F * (p->F + 1);
   const size_t lds = ((nb + 3) & ~(size_t)3) * sizeof(float) + (size_t)4 * D * kTaVtRow;   // the bias table + four V^T tiles of D dims
@@ -362,7 +573,7 @@ int launch_temporal_peg(const ImagenTemporalPegParams* p, hipStream_t s) {
 
 int launch_temporal_attention(const ImagenTemporalAttentionParams* p, hipStream_t s) {
   IMAGEN_CHECK(p->qkv && p->null_kv && p->q_scale && p->k_scale && p->bias && p->o, "temporal_attention: null pointer");
-  IMAGEN_CHECK(p->F > 0 && p->F <= kMaxFrames, "temporal_attention: 1 <= F <= 32");
+  IMAGEN_CHECK(p->F > 0 && p->F <= kMaxFramesLong, "temporal_attention: 1 <= F <= 128");
   IMAGEN_CHECK(p->heads > 0 && p->B > 0 && p->P > 0, "temporal_attention: bad shape");
   IMAGEN_CHECK(p->head_dim == 0 || p->head_dim == 32 || p->head_dim == 64, "temporal_attention: head_dim must be 64 (or 0) or 32");
   return p->head_dim == 32 ? launch_temporal_attention_d<32>(p, s) : launch_temporal_attention_d<64>(p, s);

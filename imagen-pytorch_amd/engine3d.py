@@ -73,7 +73,7 @@ class UnetEngine3D(UnetEngine):
         self.Fx, self.Fpre, self.Fpost = frames, pre_frames, post_frames   # frames of the sampler state / of the two prompts
         self.F = frames + pre_frames + post_frames                         # frames the network runs on
         self.ignore_time = ignore_time
-        assert self.F <= 32, "the temporal attention kernel holds at most 32 frames per pixel"
+        assert self.F <= 128, "the temporal attention kernels hold at most 128 frames per pixel"
         div = getattr(unet, 'total_temporal_divisor', 1)
         assert pre_frames % div == 0 and post_frames % div == 0, \
             f'the number of conditioning frames must be divisible by {div}'                     # iv.py:1700, 1713

@@ -1442,12 +1442,12 @@ def temporal_peg(plan: Plan, x: Act, w: torch.Tensor, bias: torch.Tensor, out: A
 def temporal_attention(plan: Plan, qkv: Act, null_kv: torch.Tensor, q_scale: torch.Tensor, k_scale: torch.Tensor, bias: torch.Tensor,
                        o: Act, *, B: int, F: int, P: int, heads: int, causal: bool, scale: float, head_dim: int = 64, label: str = ""):
     """qkv: rows (b, f, p) of q (heads*D) | k (D) | v (D), D = head_dim in (64, 32); null_kv: fp32 [2, D]; q_scale / k_scale: fp32 [D];
-    bias: fp32 [heads, F, F+1] (column 0 = null key); o: rows of heads*D.  (The struct carries D = 64 as 0: plans of before ABI 12 are unchanged.)"""
+    bias: fp32 [heads, F, F+1] (column 0 = null key); o: rows of heads*D; F <= 128 (33 .. 128 frames: the tiled kernel, ABI 15).  (The struct carries D = 64 as 0: plans of before ABI 12 are unchanged.)"""
     D = head_dim
     assert D in (32, 64), f"temporal_attention: head_dim {D} (kernels exist for 64 and 32)"
     assert qkv.rows == B * F * P == o.rows and qkv.C == heads * D + 2 * D and o.C == heads * D
     assert null_kv.numel() == 2 * D and q_scale.numel() == D and k_scale.numel() == D
-    assert tuple(bias.shape) == (heads, F, F + 1) and bias.dtype == torch.float32 and F <= 32
+    assert tuple(bias.shape) == (heads, F, F + 1) and bias.dtype == torch.float32 and F <= 128
     p = STRUCTS["ImagenTemporalAttentionParams"]()
     p.qkv, p.null_kv, p.q_scale, p.k_scale, p.bias, p.o = qkv.ptr, null_kv.data_ptr(), q_scale.data_ptr(), k_scale.data_ptr(), bias.data_ptr(), o.ptr
     p.B, p.F, p.P, p.heads, p.ld, p.ld_o, p.causal, p.scale = B, F, P, heads, qkv.ld, o.ld, int(causal), scale

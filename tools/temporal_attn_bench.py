@@ -5,6 +5,8 @@ keeps a launch off the MFMA route), and 8 heads x 64 on the MFMA kernel.  Events
 (as tools/attn_bench.py).
 
     python tools/temporal_attn_bench.py [--iters 30] [--out file.jsonl]
+    python tools/temporal_attn_bench.py --long     # the long-clip pair instead: 2 x 64 frames x 32^2, 8 heads x 64 on the tiled kernel
+                                                   # (ABI 15), and 2 x 32 frames x 32^2 on the route of before (F = 32: the vector kernel)
 
 One JSON line per case: us per launch, the bytes a launch has to move (qkv rows in, o rows out) and the GB/s that makes."""
 import argparse
@@ -20,20 +22,22 @@ from imagen_pytorch_amd import ops  # noqa: E402
 from imagen_pytorch_amd.ops import Act  # noqa: E402
 
 CASES = [("d32_mfma", 16, 32, 0), ("d32_vector", 16, 32, 2), ("d64_mfma", 8, 64, 0)]   # (name, heads, head dim, pad columns of an o row)
+LONG_CASES = [("d64_long_f64", 8, 64, 0, 64), ("d64_short_f32", 8, 64, 0, 32)]          # (..., frames) at P = 32^2
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--long", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
-    B, Fr, P = 2, 16, 64 * 64
-    rows = B * Fr * P
+    B, P = 2, (32 * 32 if args.long else 64 * 64)
     g = torch.Generator().manual_seed(0)
     lines, first = [], {}
-    for name, heads, D, pad in CASES:
+    for name, heads, D, pad, Fr in (LONG_CASES if args.long else [c + (16,) for c in CASES]):
         C = heads * D
+        rows = B * Fr * P
         null_kv, qs, ks = torch.randn(2, D, generator=g).to(dev), (torch.rand(D, generator=g) + 0.5).to(dev), (torch.rand(D, generator=g) + 0.5).to(dev)
         bias = torch.randn(heads, Fr, Fr + 1, generator=g).to(dev)
         src = torch.Generator().manual_seed(1)
@@ -53,9 +57,9 @@ def main():
         torch.cuda.synchronize()
         out = sets[0][1][:, :C].float()
         dist = None
-        if D in first:                                  # the two D = 32 routes compute the same thing
-            dist = float(((out - first[D]).norm() / first[D].norm()).item())
-        first.setdefault(D, out.clone())
+        if (D, Fr) in first:                            # the two D = 32 routes compute the same thing
+            dist = float(((out - first[D, Fr]).norm() / first[D, Fr].norm()).item())
+        first.setdefault((D, Fr), out.clone())
         for _ in range(3):
             plan.run()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
