@@ -16,6 +16,8 @@ from typing import Callable, Optional, Tuple
 import torch
 import torch.distributed as dist
 
+from .unet import check_negative_prompt
+
 
 def shard_bounds(total: int, rank: int, world: int) -> Tuple[int, int]:
     """Contiguous, balanced split of `total` samples: the first (total % world) ranks get one extra."""
@@ -24,22 +26,42 @@ def shard_bounds(total: int, rank: int, world: int) -> Tuple[int, int]:
     return lo, lo + base + (1 if rank < rem else 0)
 
 
+def shard_negative(lo: int, hi: int, total: int, negative_text_embeds: Optional[torch.Tensor], negative_text_masks: Optional[torch.Tensor]) -> dict:
+    """The negative-prompt keywords of the shard [lo, hi) of `total` samples: a per-sample negative prompt is sliced with its rows, a
+    batch-1 one (it serves every sample) goes to every rank as it is."""
+    check_negative_prompt(negative_text_embeds, negative_text_masks, total, None)
+    if negative_text_embeds is None:
+        return {}
+    cut = (lambda t: t) if negative_text_embeds.shape[0] == 1 else (lambda t: t[lo:hi])
+    return dict(negative_text_embeds=cut(negative_text_embeds), negative_text_masks=None if negative_text_masks is None else cut(negative_text_masks))
+
+
 def sample_sharded(sample_fn: Callable[..., torch.Tensor], text_embeds: torch.Tensor, *, text_masks: Optional[torch.Tensor] = None,
-                   group=None, gather: bool = True, **kwargs) -> torch.Tensor:
+                   negative_text_embeds: Optional[torch.Tensor] = None, negative_text_masks: Optional[torch.Tensor] = None,
+                   negative_texts=None, group=None, gather: bool = True, **kwargs) -> torch.Tensor:
     """Run `sample_fn(text_embeds=shard, text_masks=shard, sample_offset=lo, **kwargs)` on this rank's shard and all-gather.
 
     `sample_fn` is normally `Imagen.sample`; it must return a (b_local, C, H, W) tensor on the rank's device.
     Returns the full (B, C, H, W) batch on every rank (or the local shard if gather=False).
+    A negative prompt (negative_text_embeds / negative_text_masks, or negative_texts: one string for all samples or one per sample) is
+    sharded with its rows.
     """
-    if not dist.is_available() or not dist.is_initialized():
-        return sample_fn(text_embeds=text_embeds, text_masks=text_masks, sample_offset=0, **kwargs)
-    rank, world = dist.get_rank(group), dist.get_world_size(group)
     B = text_embeds.shape[0]
+    if negative_texts is not None:
+        if negative_text_embeds is not None:
+            raise ValueError('negative_texts and negative_text_embeds are both given: pass one of them')
+        if len(negative_texts) not in (1, B):
+            raise ValueError(f"negative_texts: {len(negative_texts)} strings, neither 1 nor the prompts' {B}")
+    neg = lambda lo, hi: (shard_negative(lo, hi, B, negative_text_embeds, negative_text_masks) if negative_texts is None else
+                          dict(negative_texts=list(negative_texts) if len(negative_texts) == 1 else list(negative_texts[lo:hi])))
+    if not dist.is_available() or not dist.is_initialized():
+        return sample_fn(text_embeds=text_embeds, text_masks=text_masks, sample_offset=0, **neg(0, B), **kwargs)
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
     lo, hi = shard_bounds(B, rank, world)
     local = None
     if hi > lo:
         local = sample_fn(text_embeds=text_embeds[lo:hi], text_masks=None if text_masks is None else text_masks[lo:hi],
-                          sample_offset=lo, **kwargs)
+                          sample_offset=lo, **neg(lo, hi), **kwargs)
     if not gather:
         return local
     return all_gather_images(local, B, group=group)

@@ -361,10 +361,14 @@ class ElucidatedImagen(Imagen):
         use_graph: bool = True,
         max_steps: Optional[int] = None,
         conditioning=None,
+        negative_texts: Optional[List[str]] = None,   # a second prompt on the null rows of guidance, as on Imagen.sample
+        negative_text_embeds=None,
+        negative_text_masks=None,
     ):
         with self._eval_mode():
             try:
                 self._tls.conditioning = conditioning
+                self._tls.negative = self._negative_of_call(conditioning, negative_texts, negative_text_embeds, negative_text_masks)
                 n_unets = len(self.unets)
                 self._tls.sigma_overrides = None if sigma_min is None and sigma_max is None else dict(
                     sigma_min=_cast_tuple(sigma_min, n_unets), sigma_max=_cast_tuple(sigma_max, n_unets))
@@ -380,4 +384,5 @@ class ElucidatedImagen(Imagen):
                                     max_steps)
             finally:
                 self._tls.conditioning = None
+                self._tls.negative = None
                 self._tls.sigma_overrides = None

@@ -157,7 +157,8 @@ class UnetEngine:
         self.NT = self.ntt + self.NS                                    # all conditioning tokens
         self.attn_sites: List[dict] = []   # attention K/V buffers + how to fill their conditioning rows
         self.taps: Dict[str, Act] = {}     # named intermediates (persistent buffers) for per-stage parity checks
-        self._static_plans: Dict[int, tuple] = {}   # n_tok -> (plan, te16, mask_u8)
+        self._static_plans: Dict[int, tuple] = {}   # n_tok -> (plan, te16, mask_u8, negative-prompt projection plan | None)
+        self._last_static: List[Plan] = []          # what the last set_conditioning() ran (a dry engine: what is to be run), in order
         self._cond_ready = False
         self._tt_plan = None        # sampler mode: the batched all-steps pass of the timestep-only conditioning (enable_time_table)
         self._alloc_io()
@@ -954,7 +955,7 @@ class UnetEngine:
         plan = Plan("unet-static")
         L = u.max_text_len
         src_batch = self.src_batch
-        te16 = mask_u8 = None
+        te16 = mask_u8 = neg_plan = None
         t_parts: List[Act] = []
         static_tokens: List[Act] = []   # pieces of c after the time tokens: [lowres time tokens][text tokens]
         # ---- low-res noise-level conditioning (ip.py:1583-1589)
@@ -974,12 +975,23 @@ class UnetEngine:
         if self.has_text:
             assert n_tok > 0
             ted = u.text_to_cond.weight.shape[1]
-            te16 = torch.zeros(src_batch, n_tok, ted, dtype=torch.float16, device=self.dev)
-            mask_u8 = torch.ones(src_batch, L, dtype=torch.uint8, device=self.dev)
-            tok = self.new(src_batch, 1, L, cd, zero=True)          # rows >= n_tok stay zero (F.pad, ip.py:1617)
+            # source rows [0, src_batch): the prompts.  A guided engine stages a second set, [src_batch, 2 src_batch), for a negative prompt:
+            # the null rows of a request that has one select those (set_conditioning points src_idx there and sets their keep flag)
+            n_src = 2 * src_batch if R == 2 * src_batch else src_batch
+            te16 = torch.zeros(n_src, n_tok, ted, dtype=torch.float16, device=self.dev)
+            mask_u8 = torch.ones(n_src, L, dtype=torch.uint8, device=self.dev)
+            tok = self.new(n_src, 1, L, cd, zero=True)              # rows >= n_tok stay zero (F.pad, ip.py:1617)
             te = Act(te16, src_batch, 1, n_tok, ted, ted, n_tok * ted)
             tok_head = Act(tok.t, src_batch, 1, n_tok, cd, cd, L * cd)
             ops.igemm(plan, te, W.conv("text_to_cond", u.text_to_cond, split=SPLIT_STATIC), tok_head, label="text_to_cond")
+            if n_src > src_batch:
+                # the negative prompts' projection: the same launch on the second set of source rows, in a plan of its own that runs ahead of
+                # this one only when a request brings a negative prompt (without one nothing reads those rows, and the launches are the
+                # same as before)
+                neg_plan = Plan("unet-static-negative")
+                ops.igemm(neg_plan, Act(te16, src_batch, 1, n_tok, ted, ted, n_tok * ted, src_batch * n_tok * ted),
+                          W.conv("text_to_cond", u.text_to_cond, split=SPLIT_STATIC),
+                          Act(tok.t, src_batch, 1, n_tok, cd, cd, L * cd, src_batch * L * cd), label="text_to_cond(negative)")
             xt = self.new(R, 1, L, cd)
             ops.select_rows(plan, tok.t, W.f16("null_text_embed", lambda: u.null_text_embed[0]), mask_u8, self.src_idx, self.keep_u8, xt.t,
                             R=R, L=L, C=cd, label="text_keep_select")
@@ -1022,7 +1034,7 @@ class UnetEngine:
             flat = Act(c_static.t, 1, 1, R * ns, cd, cd, R * ns * cd)
             self._emit_context_kv(plan, flat, rows_per_batch=ns, k_row0_self=self.ntt, k_row0_cross=1 + self.ntt, tag="static")
         self._emit_null_kv(plan)
-        return plan, te16, mask_u8
+        return plan, te16, mask_u8, neg_plan
 
     def _perceiver(self, plan, xt: Act, pr) -> Act:
         """PerceiverResampler (ip.py:447-498), depth x [PerceiverAttention (ip.py:408-445) + FeedForward(mult 4)]."""
@@ -1093,36 +1105,82 @@ class UnetEngine:
         return lat
 
     # ------------------------------------------------------------------------------------------ run-time API
-    def set_conditioning(self, *, text_embeds, text_mask, keep, lowres_noise_times):
-        """Stage the timestep-invariant inputs and run the static plan.  `keep`: bool [R] (True = conditional row)."""
+    def set_conditioning(self, *, text_embeds, text_mask, keep, lowres_noise_times, negative_text_embeds=None, negative_text_mask=None,
+                         negative_rows=None):
+        """Stage the timestep-invariant inputs and run the static plan.  `keep`: bool [R] (True = conditional row).
+
+        negative_text_embeds [src_batch | 1, n, text_embed_dim] (+ negative_text_mask, default any(embeds != 0, -1)): a second prompt for the
+        null rows of a guided engine (R = 2 src_batch) — they then run the conditional path on THAT prompt (text_to_cond, masked positions ->
+        null_text_embed, Perceiver pooling, the text hiddens' MLP, their K/V rows) instead of the learned null conditioning: the guided
+        output is neg + (pos - neg) * cond_scale.  A batch-1 negative prompt is repeated over the batch.  `negative_rows`: bool [src_batch],
+        the samples that have one (merged requests); the others keep the learned null rows.  Prompt and negative prompt share the static
+        plan of the longer one's token count: the shorter is zero-padded and its padded positions are masked."""
         R, u, src_batch = self.R, self.unet, self.src_batch
-        n_tok = 0
+        n_tok = n_pos = n_neg = 0
+        neg = negative_text_embeds
         if self.has_text:
             assert text_embeds is not None, "this engine was planned with text conditioning"
             text_embeds = text_embeds[:, : u.max_text_len]
-            n_tok = text_embeds.shape[1]
+            n_tok = n_pos = text_embeds.shape[1]
             assert text_embeds.shape[0] == src_batch
+        if neg is not None:
+            assert self.has_text, "negative_text_embeds: this engine was planned without text conditioning"
+            assert R == 2 * src_batch, "negative_text_embeds: only a guided engine (rows = 2 * batch) has null rows to put a prompt on"
+            assert neg.ndim == 3 and neg.shape[0] in (1, src_batch), \
+                f"negative_text_embeds: batch {neg.shape[0]} is neither 1 nor the prompts' {src_batch}"
+            assert neg.shape[-1] == text_embeds.shape[-1], \
+                f"negative_text_embeds: embedding width {neg.shape[-1]}, the prompts have {text_embeds.shape[-1]}"
+            neg = neg[:, : u.max_text_len]
+            n_neg = neg.shape[1]
+            n_tok = max(n_pos, n_neg)
+            if negative_text_mask is None:
+                negative_text_mask = torch.any(neg != 0., dim=-1)
         if n_tok not in self._static_plans:
             self._static_plans[n_tok] = self._build_static_plan(n_tok)
-        plan, te16, mask_u8 = self._static_plans[n_tok]
-        self.keep_u8.copy_(keep.to(torch.uint8))
-        self.src_idx.copy_(torch.arange(R, dtype=torch.int32) % src_batch)
+        plan, te16, mask_u8, neg_plan = self._static_plans[n_tok]
+        if neg is None:
+            self.keep_u8.copy_(keep.to(torch.uint8))
+            self.src_idx.copy_(torch.arange(R, dtype=torch.int32) % src_batch)
+        else:
+            keep_u8 = keep.to(torch.uint8).cpu().clone()
+            src_idx = torch.arange(R, dtype=torch.int32) % src_batch
+            has = torch.ones(src_batch, dtype=torch.bool) if negative_rows is None else negative_rows.to(torch.bool).cpu().reshape(src_batch)
+            keep_u8[src_batch:][has] = 1
+            src_idx[src_batch:][has] += src_batch            # < 2 * src_batch: the rows te16 / mask_u8 / tok were allocated with
+            self.keep_u8.copy_(keep_u8)
+            self.src_idx.copy_(src_idx)
         if self.lowres:
             assert lowres_noise_times is not None
             lt = lowres_noise_times.float().reshape(-1)
             self.lowres_times.copy_(lt.repeat(R // lt.numel()))
         if self.has_text:
-            te16.copy_(text_embeds.to(torch.float16))
             L = u.max_text_len
-            m = torch.zeros(src_batch, L, dtype=torch.uint8)
-            if text_mask is not None:
-                tm = text_mask[:, :L].to(torch.uint8).cpu()
-                m[:, : tm.shape[1]] = tm
-            else:
-                m[:, :] = 1      # no mask: the zero-padded positions stay zero tokens, they are NOT replaced by null_text_embed (ip.py:1619-1632)
-            mask_u8.copy_(m)
+
+            def stage(row0, emb, mask):
+                n = emb.shape[1]
+                emb = emb.expand(src_batch, -1, -1)
+                if n < n_tok:                          # the shorter of prompt and negative prompt: zero-padded, the padding masked
+                    te16[row0:row0 + src_batch].zero_()
+                    te16[row0:row0 + src_batch, :n].copy_(emb.to(torch.float16))
+                else:
+                    te16[row0:row0 + src_batch].copy_(emb.to(torch.float16))
+                m = torch.zeros(src_batch, L, dtype=torch.uint8)
+                if mask is not None:
+                    tm = mask[:, :L].to(torch.uint8).cpu().expand(src_batch, -1)
+                    m[:, : tm.shape[1]] = tm
+                elif n < n_tok:
+                    m[:, :n] = 1
+                else:
+                    m[:, :] = 1      # no mask: the zero-padded positions stay zero tokens, they are NOT replaced by null_text_embed (ip.py:1619-1632)
+                mask_u8[row0:row0 + src_batch].copy_(m)
+
+            stage(0, text_embeds, text_mask)
+            if neg is not None:
+                stage(src_batch, neg, negative_text_mask)
+        self._last_static = [neg_plan, plan] if neg is not None else [plan]
         if not self.dry:
-            plan.run()
+            for pl in self._last_static:
+                pl.run()
             if self._tt_plan is not None:
                 self._tt_plan.run()
         self._cond_ready = True

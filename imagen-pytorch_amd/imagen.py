@@ -10,7 +10,8 @@ Implemented options: text embeddings or the T5 hook (`texts=`), classifier-free 
 skip_steps, inpainting (images and videos), cond_images, self-conditioning unets, start/stop_at_unet_number, video cascades (Unet3D
 stages) with cond_video_frames / post_cond_video_frames.  Training (`forward`, p_losses) raises.  Extensions beyond
 the reference signature: `noise_fn`,
-`seed`, `sample_offset` (batch sharding), `conditioning` handles, lanes (`with imagen.lane(i)`) and `sample_pipelined`.
+`seed`, `sample_offset` (batch sharding), `conditioning` handles, lanes (`with imagen.lane(i)`), `sample_pipelined` and negative prompts
+(`negative_texts` / `negative_text_embeds` / `negative_text_masks`: a second prompt on the null rows of guidance).
 """
 from __future__ import annotations
 
@@ -29,7 +30,7 @@ from . import ops
 from .ops import Plan
 from .schedules import GaussianDiffusionContinuousTimes
 from .t5 import t5_encode_text
-from .unet import NullUnet, Unet
+from .unet import NullUnet, Unet, check_negative_prompt
 from .unet3d import Unet3D
 
 T5_DIMS = {  # d_model of the encoders the reference accepts by name (t5.py:47-58 reads it from the HF config)
@@ -86,8 +87,10 @@ class Conditioning:
     prompts, `start_at_unet_number` re-runs, ...) lets each stage keep what its static plan wrote the first time: the engine
     buffers are stamped with the handle's token and the static plan is skipped while the stamp matches."""
 
-    def __init__(self, text_embeds: Optional[torch.Tensor], text_masks: Optional[torch.Tensor], batch_size: int):
+    def __init__(self, text_embeds: Optional[torch.Tensor], text_masks: Optional[torch.Tensor], batch_size: int,
+                 negative_text_embeds: Optional[torch.Tensor] = None, negative_text_masks: Optional[torch.Tensor] = None):
         self.text_embeds, self.text_masks, self.batch_size = text_embeds, text_masks, batch_size
+        self.negative_text_embeds, self.negative_text_masks = negative_text_embeds, negative_text_masks   # the negative prompt rides along
         self.token = object()
 
 
@@ -287,7 +290,8 @@ class Imagen(nn.Module):
         """Extension (serving): several independent `sample()` requests MERGED into one batch — one set of kernel launches per denoiser step for
         all of them (48 images as two merged batches of 24 sample 16 % faster on MI355X than as six concurrent requests of 8, profiles/r06_q_*).
         `requests` is a list of per-request keyword dicts (`text_embeds=` | `texts=`, `text_masks=`, `seed=`, `batch_size=` for unconditional
-        cascades), `common` the keywords shared by all (`cond_scale=`, `max_steps=`, ...).  Every row draws the noise of ITS OWN request — that
+        cascades, `negative_texts=` | `negative_text_embeds=`, `negative_text_masks=`), `common` the keywords shared by all (`cond_scale=`,
+        `max_steps=`, ...).  Requests with and without a negative prompt merge: the null rows of those without stay the learned ones.  Every row draws the noise of ITS OWN request — that
         request's Philox key and sample indices 0 .. b-1 (ABI 11: ImagenDdpmUpdateParams.row_keys) — so a request's images are the ones
         `sample(**common, **request)` produces up to the fp16 rounding of a different batch's tile configuration.  Returns one tensor per request.
         Not covered (raise): inpainting, init images, conditioning images / frames, `noise_fn`, `start_image_or_video`."""
@@ -299,12 +303,18 @@ class Imagen(nn.Module):
             _out_of_scope(f"{type(self).__name__}.sample_requests (its sampler's noise launches take one key per batch)")
         if not requests:
             return []
-        embeds, masks, seeds, sizes = [], [], [], []
+        embeds, masks, seeds, sizes, negs, neg_rows = [], [], [], [], [], None
+        neg_keys = ('negative_texts', 'negative_text_embeds', 'negative_text_masks')
+        if any(common.get(k) is not None for k in neg_keys) and any(r.get(k) is not None for r in requests for k in neg_keys):
+            raise ValueError('negative_texts / negative_text_embeds: pass the negative prompt per request or as a common keyword, not both')
         for r in requests:
-            extra = set(r) - {'texts', 'text_embeds', 'text_masks', 'seed', 'batch_size'}
+            extra = set(r) - {'texts', 'text_embeds', 'text_masks', 'seed', 'batch_size', *neg_keys}
             assert not extra, f'per-request keywords {sorted(extra)} must be the same for all merged requests: pass them as common keywords'
             te, tm = self._resolve_text(r.get('texts'), r.get('text_embeds'), r.get('text_masks'), self.device)
             b = te.shape[0] if te is not None else int(r.get('batch_size', 1))
+            ne, nm = self._resolve_negative(r.get('negative_texts'), r.get('negative_text_embeds'), r.get('negative_text_masks'), self.device,
+                                            batch=b, whose="the request's")
+            negs.append(None if ne is None else (ne.expand(b, -1, -1), nm.expand(b, -1)))
             embeds.append(te)
             masks.append(tm)
             sizes.append(b)
@@ -313,12 +323,23 @@ class Imagen(nn.Module):
         kw.setdefault('use_tqdm', False)
         if embeds[0] is not None:
             width = max(e.shape[1] for e in embeds)       # (prompts of different lengths: zero-padded, masked)
-            pad = lambda t, fill: torch.cat((t, t.new_full((t.shape[0], width - t.shape[1], *t.shape[2:]), fill)), 1) if t.shape[1] < width else t
-            kw['text_embeds'] = torch.cat([pad(e, 0.0) for e in embeds])
-            kw['text_masks'] = torch.cat([pad(m, False) for m in masks])
+            pad = lambda t, fill, w: torch.cat((t, t.new_full((t.shape[0], w - t.shape[1], *t.shape[2:]), fill)), 1) if t.shape[1] < w else t
+            kw['text_embeds'] = torch.cat([pad(e, 0.0, width) for e in embeds])
+            kw['text_masks'] = torch.cat([pad(m, False, width) for m in masks])
+            if any(n is not None for n in negs):      # one row per sample; the requests without a negative prompt get zero rows that nothing reads
+                nwidth = max(n[0].shape[1] for n in negs if n is not None)
+                zero = lambda b: (torch.zeros(b, nwidth, self.text_embed_dim, device=self.device), torch.zeros(b, nwidth, dtype=torch.bool, device=self.device))
+                pairs = [zero(b) if n is None else n for n, b in zip(negs, sizes)]
+                kw['negative_text_embeds'] = torch.cat([pad(e, 0.0, nwidth) for e, _ in pairs])
+                kw['negative_text_masks'] = torch.cat([pad(m, False, nwidth) for _, m in pairs])
+                neg_rows = torch.cat([torch.full((b,), n is not None) for n, b in zip(negs, sizes)])
         else:
             kw['batch_size'] = sum(sizes)
-        out = self.sample(seed=seeds, **kw)
+        try:
+            self._tls.negative_rows = neg_rows      # bool [rows]: the samples the merged negative prompt applies to (sample() reads it here)
+            out = self.sample(seed=seeds, **kw)
+        finally:
+            self._tls.negative_rows = None
         return list(torch.split(out, sizes))
 
     @torch.no_grad()
@@ -341,6 +362,21 @@ class Imagen(nn.Module):
             jobs.append(kw)
         if n_stages == 1 or len(jobs) == 0:
             return [self.sample(**kw) for kw in jobs]
+        # a negative prompt is checked here, against the guidance scales of the WHOLE cascade and before a thread starts: a worker runs
+        # one stage per sample() call, and a stage at cond_scale 1 beside guided ones is no error (it has no null rows to put the prompt on)
+        for kw in jobs:
+            cond = kw.get('conditioning')
+            negative = self._negative_of_call(cond, kw.get('negative_texts'), kw.get('negative_text_embeds'), kw.get('negative_text_masks'))
+            if negative is None:
+                continue
+            te = cond.text_embeds if cond is not None else kw.get('text_embeds')
+            rows = te.shape[0] if te is not None else len(kw['texts']) if kw.get('texts') is not None else \
+                cond.batch_size if cond is not None else int(kw.get('batch_size', 1))
+            device = torch.device(kw['device']) if kw.get('device') is not None else self.device
+            ne, nm, _ = self._check_negative(negative, rows, _cast_tuple(kw.get('cond_scale', 1.), n_stages), device)
+            if cond is None:                             # encoded once for all stages of the batch
+                kw.pop('negative_texts', None)
+                kw['negative_text_embeds'], kw['negative_text_masks'] = ne, nm
         caller = torch.cuda.current_stream(self.device)
         ready = torch.cuda.Event()
         ready.record(caller)
@@ -349,6 +385,7 @@ class Imagen(nn.Module):
 
         def worker(s: int):
             try:
+                self._tls.pipelined_stage = True         # (this thread's: its sample() calls are single stages of cascades checked above)
                 with self.lane(0x100 + s), torch.cuda.device(self.device):
                     torch.cuda.current_stream().wait_event(ready)
                     while True:
@@ -715,10 +752,14 @@ class Imagen(nn.Module):
         use_graph: bool = True,
         max_steps: Optional[int] = None,
         conditioning: Optional[Conditioning] = None,   # extension: handle from prepare_conditioning() instead of texts / text_embeds
+        negative_texts: Optional[List[str]] = None,    # extension: a second prompt on the null rows of guidance (batch 1 or the prompts' batch):
+        negative_text_embeds=None,                     #   every guided evaluation is neg + (pos - neg) * cond_scale
+        negative_text_masks=None,
     ):
         with self._eval_mode():
             try:
                 self._tls.conditioning = conditioning
+                self._tls.negative = self._negative_of_call(conditioning, negative_texts, negative_text_embeds, negative_text_masks)
                 if conditioning is not None:
                     assert texts is None and text_embeds is None and text_masks is None, 'pass either `conditioning` or texts / text_embeds'
                     text_embeds, text_masks = conditioning.text_embeds, conditioning.text_masks
@@ -731,6 +772,55 @@ class Imagen(nn.Module):
                                     max_steps)
             finally:
                 self._tls.conditioning = None
+                self._tls.negative = None
+
+    def _negative_of_call(self, conditioning, negative_texts, negative_text_embeds, negative_text_masks):
+        """The negative prompt of one sample() call as given — by keyword, or on the conditioning handle — for _sample, which resolves and
+        checks it once the batch and the guidance scales are known.  (The fourth entry, the samples it applies to, is sample_requests'.)"""
+        negative_rows = getattr(self._tls, 'negative_rows', None)
+        given = negative_texts is not None or negative_text_embeds is not None or negative_text_masks is not None
+        if conditioning is not None:
+            if given:
+                raise ValueError('negative_texts / negative_text_embeds: a `conditioning` handle carries its own negative prompt '
+                                 '(prepare_conditioning(negative_text_embeds=...)); pass one or the other')
+            negative_text_embeds, negative_text_masks = conditioning.negative_text_embeds, conditioning.negative_text_masks
+            given = negative_text_embeds is not None
+        return (negative_texts, negative_text_embeds, negative_text_masks, negative_rows) if given else None
+
+    def _resolve_negative(self, texts, text_embeds, text_masks, device, batch=None, whose="the prompts'"):
+        """negative_texts -> the `encode_text` hook; default mask = any non-zero feature (as _resolve_text does for the prompt).  Returns
+        (embeds [b, n, text_embed_dim], mask [b, n]) with b = 1 or `batch`, or (None, None) when no negative prompt was given."""
+        if texts is None and text_embeds is None:
+            check_negative_prompt(None, text_masks, None, None)
+            return None, None
+        if texts is not None and text_embeds is not None:
+            raise ValueError('negative_texts and negative_text_embeds are both given: pass one of them')
+        kw = 'negative_texts' if texts is not None else 'negative_text_embeds'
+        if self.unconditional:
+            raise ValueError(f'{kw}: this model was built with condition_on_text=False, there is no text branch to put a negative prompt on')
+        if texts is not None:
+            assert all([*map(len, texts)]), 'negative_texts: text cannot be empty'
+            text_embeds, text_masks = self.encode_text(texts, return_attn_mask=True)
+        check_negative_prompt(text_embeds, text_masks, batch, self.text_embed_dim, kw=kw, whose=whose)
+        text_embeds = text_embeds.to(device)
+        text_masks = text_masks.to(device) if text_masks is not None else torch.any(text_embeds != 0., dim=-1)
+        return text_embeds, text_masks
+
+    def _check_negative(self, negative, batch_size, cond_scales, device):
+        """Resolve and check the negative prompt of one call (`negative`: what _negative_of_call returned) for `batch_size` samples.
+        `cond_scales`: the guidance scales of the stages the call runs — all 1 would silently ignore the prompt, which is refused; None
+        when sample_pipelined has already checked the whole cascade's and this call is one stage of it.  Returns (embeds, masks, rows)."""
+        kw = 'negative_texts' if negative[0] is not None else 'negative_text_embeds'
+        neg_embeds, neg_masks = self._resolve_negative(*negative[:3], device, batch=batch_size)
+        neg_rows = negative[3]
+        if neg_rows is not None and tuple(neg_rows.shape) != (batch_size,):
+            raise ValueError(f'{kw}: the merged requests mark {tuple(neg_rows.shape)} samples, the batch has {batch_size}')
+        if not self.can_classifier_guidance:
+            raise ValueError(f'{kw}: imagen was not trained with conditional dropout (cond_drop_prob == 0) and cannot do classifier free '
+                             f'guidance, which is where a negative prompt acts')
+        if cond_scales is not None and all(cs == 1. for cs in cond_scales):
+            raise ValueError(f'{kw}: cond_scale is 1 on every stage of this call, so the negative prompt would be silently ignored')
+        return neg_embeds, neg_masks, neg_rows
 
     def _resolve_text(self, texts, text_embeds, text_masks, device):
         """ip.py:2326-2337: texts -> encoder hook; default mask = any non-zero feature."""
@@ -745,15 +835,19 @@ class Imagen(nn.Module):
 
     @torch.no_grad()
     def prepare_conditioning(self, texts: Optional[List[str]] = None, *, text_embeds=None, text_masks=None, batch_size: int = 1,
-                             device=None) -> Conditioning:
-        """Encode / stage the prompts once; reuse the returned handle with `sample(conditioning=handle, ...)`."""
+                             device=None, negative_texts: Optional[List[str]] = None, negative_text_embeds=None,
+                             negative_text_masks=None) -> Conditioning:
+        """Encode / stage the prompts (and the negative prompt, if any) once; reuse the returned handle with
+        `sample(conditioning=handle, ...)`."""
         device = torch.device(device) if device is not None else self.device
         text_embeds, text_masks = self._resolve_text(texts, text_embeds, text_masks, device)
         assert not (self.condition_on_text and text_embeds is None), 'text or text encodings must be passed into imagen if specified'
         assert not (not self.condition_on_text and text_embeds is not None), 'imagen specified not to be conditioned on text, yet it is presented'
         assert not (text_embeds is not None and text_embeds.shape[-1] != self.text_embed_dim), \
             f'invalid text embedding dimension being passed in (should be {self.text_embed_dim})'
-        return Conditioning(text_embeds, text_masks, text_embeds.shape[0] if text_embeds is not None else batch_size)
+        neg, neg_masks = self._resolve_negative(negative_texts, negative_text_embeds, negative_text_masks, device,
+                                                batch=None if text_embeds is None else text_embeds.shape[0])
+        return Conditioning(text_embeds, text_masks, text_embeds.shape[0] if text_embeds is not None else batch_size, neg, neg_masks)
 
     def _sample(self, texts, text_masks, text_embeds, video_frames, cond_images, cond_video_frames, post_cond_video_frames,
                 inpaint_videos, inpaint_images, inpaint_masks, inpaint_resample_times, init_images, skip_steps, batch_size, cond_scale,
@@ -824,6 +918,13 @@ class Imagen(nn.Module):
         cond_scale = _cast_tuple(cond_scale, num_unets)
         if seed is None:
             seed = self._next_seed()
+        # the negative prompt of this call: resolved and checked here, before any stage is built or anything is launched
+        neg_embeds = neg_masks = neg_rows = None
+        negative = getattr(self._tls, 'negative', None)
+        if negative is not None:
+            last = num_unets if stop_at_unet_number is None else stop_at_unet_number
+            scales = None if getattr(self._tls, 'pipelined_stage', False) else cond_scale[start_at_unet_number - 1:last]
+            neg_embeds, neg_masks, neg_rows = self._check_negative(negative, batch_size, scales, device)
 
         img = None
         if start_at_unet_number > 1:
@@ -923,8 +1024,11 @@ class Imagen(nn.Module):
                 cond = getattr(self._tls, 'conditioning', None)
                 stamp = None if cond is None else (cond.token, None if lowres_logsnr is None else float(lowres_logsnr[0]))
                 if stamp is None or getattr(eng, '_cond_stamp', None) != stamp:
+                    neg_kw = {}
+                    if neg_embeds is not None and with_text and rows == 2 * batch_size:     # (a stage at cond_scale 1 has no null rows)
+                        neg_kw = dict(negative_text_embeds=neg_embeds, negative_text_mask=neg_masks, negative_rows=neg_rows)
                     eng.set_conditioning(text_embeds=text_embeds if with_text else None, text_mask=text_masks if with_text else None,
-                                         keep=keep, lowres_noise_times=lowres_logsnr)
+                                         keep=keep, lowres_noise_times=lowres_logsnr, **neg_kw)
                     eng.static_runs = getattr(eng, 'static_runs', 0) + 1
                 eng._cond_stamp = stamp
                 timing = os.environ.get("IMAGEN_TIMING")

@@ -38,6 +38,35 @@ def _unsupported(flag):
     )
 
 
+def check_negative_prompt(embeds, masks, batch, width, *, kw='negative_text_embeds', whose="the prompts'"):
+    """The shape rules of a negative prompt, stated once for every entry point that takes one (the unets, Imagen.sample and its relatives,
+    distributed.sample_sharded): (b, n, width) embeddings with b = 1 (it serves every sample) or b = `batch`, and a mask, if there is
+    one, of the embeddings' (b, n).  `kw` is the keyword the caller used; `width` / `batch` None: not known here, not checked."""
+    if embeds is None:
+        if masks is not None:
+            raise ValueError('negative_text_masks given without negative_texts / negative_text_embeds')
+        return
+    if embeds.ndim != 3 or (width is not None and embeds.shape[-1] != width):
+        raise ValueError(f"{kw}: invalid text embedding shape {tuple(embeds.shape)} (should be (b, n, {'d' if width is None else width}))")
+    if batch is not None and embeds.shape[0] not in (1, batch):
+        raise ValueError(f"{kw}: batch {embeds.shape[0]} is neither 1 nor {whose} {batch}")
+    if masks is not None and tuple(masks.shape) != tuple(embeds.shape[:2]):
+        raise ValueError(f"negative_text_masks: shape {tuple(masks.shape)} does not match the negative prompt's {tuple(embeds.shape[:2])}")
+
+
+def _guided_negative(unet, cond_scale, text_embeds, negative_texts, negative_text_embeds, negative_text_masks):
+    """What Unet and Unet3D.forward_with_cond_scale refuse of a negative prompt before they run anything.  `negative_texts` is part of the
+    signature so that the keywords are the same at every level, but only Imagen has the `encode_text` hook that can serve it."""
+    if negative_texts is not None:
+        raise ValueError("negative_texts: a unet has no text encoder; pass negative_text_embeds (Imagen.sample encodes negative_texts)")
+    if negative_text_embeds is None:
+        return check_negative_prompt(None, negative_text_masks, None, None)
+    if not unet.cond_on_text or text_embeds is None:
+        raise ValueError("negative_text_embeds: this unet is not conditioned on text (cond_on_text=False, or no text_embeds given)")
+    if cond_scale == 1:
+        raise ValueError("negative_text_embeds: cond_scale is 1, the negative prompt would be ignored")
+
+
 class Unet(nn.Module):
     def __init__(
         self,
@@ -306,12 +335,23 @@ class Unet(nn.Module):
     def release_engines(self):
         self._engines.clear()
 
-    def forward_with_cond_scale(self, *args, cond_scale=1., **kwargs):
-        """ip.py:1510-1522 — the cond and null branches run as ONE 2B-row batch through the kernel plan."""
+    def forward_with_cond_scale(self, *args, cond_scale=1., negative_text_embeds=None, negative_text_masks=None, negative_texts=None, **kwargs):
+        """ip.py:1510-1522 — the cond and null branches run as ONE 2B-row batch through the kernel plan.
+
+        Extension: negative_text_embeds (+ negative_text_masks, default any(embeds != 0, -1)) puts a second prompt on the null branch — the
+        result is neg + (pos - neg) * cond_scale with both branches evaluated at cond_drop_prob = 0.  A batch-1 negative prompt serves the
+        whole batch.  (`negative_texts` needs an encoder: Imagen.sample takes it; a bare unet has none.)
+
+        Prompt and negative prompt share one token axis, the longer one's.  One consequence for a call WITHOUT `text_mask` whose prompt is
+        the shorter of the two: the positions it is padded by are masked, so they become null_text_embed, where the same call without a
+        negative prompt leaves zero tokens from the prompt's end to max_text_len.  It is the result of passing text_mask = all ones over
+        the prompt's own tokens; pass a `text_mask` (Imagen.sample always derives one) and the conditional branch does not depend on
+        the negative prompt at all."""
+        _guided_negative(self, cond_scale, kwargs.get('text_embeds'), negative_texts, negative_text_embeds, negative_text_masks)
         if cond_scale == 1:
             return self.forward(*args, **kwargs)
         kwargs.pop('cond_drop_prob', None)
-        both = self._run(*args, cfg=True, **kwargs)
+        both = self._run(*args, cfg=True, negative_text_embeds=negative_text_embeds, negative_text_mask=negative_text_masks, **kwargs)
         b = both.shape[0] // 2
         logits, null_logits = both[:b], both[b:]
         return null_logits + (logits - null_logits) * cond_scale
@@ -324,7 +364,7 @@ class Unet(nn.Module):
 
     @torch.no_grad()
     def _run(self, x, time, *, lowres_cond_img=None, lowres_noise_times=None, text_embeds=None, text_mask=None, cond_images=None,
-             cond_drop_prob=0., cfg=False, self_cond=None):
+             cond_drop_prob=0., cfg=False, self_cond=None, negative_text_embeds=None, negative_text_mask=None):
         assert not (self.lowres_cond and lowres_cond_img is None), 'low resolution conditioning image must be present'
         assert not (self.lowres_cond and lowres_noise_times is None), 'low resolution conditioning noise time must be present'
         assert not (self.has_cond_image ^ (cond_images is not None)), \
@@ -333,6 +373,8 @@ class Unet(nn.Module):
             raise RuntimeError("the MI355X path implements sampling (eval mode) only; call .eval() first")
         B, _, H, W = x.shape
         assert H == W, 'square images only'
+        check_negative_prompt(negative_text_embeds, negative_text_mask, B,       # before an engine is built or anything is launched
+                              None if text_embeds is None else text_embeds.shape[-1])
         rows = 2 * B if cfg else B
         with_text = bool(self.cond_on_text and text_embeds is not None)
         eng = self.engine(rows, B, H, x.device, with_text=with_text)
@@ -345,7 +387,8 @@ class Unet(nn.Module):
         else:
             keep = torch.rand(B) < (1 - cond_drop_prob)   # ip.py:201-207
         eng.set_conditioning(text_embeds=text_embeds if with_text else None, text_mask=text_mask, keep=keep,
-                             lowres_noise_times=lowres_noise_times)
+                             lowres_noise_times=lowres_noise_times, negative_text_embeds=negative_text_embeds,
+                             negative_text_mask=negative_text_mask)
         if cond_images is not None:
             eng.set_cond_images(cond_images)
         if self.self_cond:

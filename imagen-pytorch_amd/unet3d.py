@@ -19,7 +19,7 @@ from .modules import Holder, PerceiverResamplerP, SinuPosEmbP
 from .modules3d import (Attention3dP, CrossEmbed3dP, Parallel3dP, PixelShuffleUpsample3dP, ResidualP, ResnetBlock3dP,
                         TemporalPixelShuffleUpsampleP, TransformerBlock3dP, conv_frames_p, downsample3d_p, temporal_attn_p,
                         temporal_downsample_p, temporal_peg_p)
-from .unet import DEFAULT_TEXT_EMBED_DIM, _cast_tuple, _unsupported
+from .unet import DEFAULT_TEXT_EMBED_DIM, _cast_tuple, _guided_negative, _unsupported, check_negative_prompt
 
 
 class Unet3D(nn.Module):
@@ -267,12 +267,23 @@ class Unet3D(nn.Module):
     def release_engines(self):
         self._engines.clear()
 
-    def forward_with_cond_scale(self, *args, cond_scale=1., **kwargs):
-        """iv.py:1636-1648 — the cond and null branches run as ONE 2B-row batch."""
+    def forward_with_cond_scale(self, *args, cond_scale=1., negative_text_embeds=None, negative_text_masks=None, negative_texts=None, **kwargs):
+        """iv.py:1636-1648 — the cond and null branches run as ONE 2B-row batch through the kernel plan.
+
+        Extension: negative_text_embeds (+ negative_text_masks, default any(embeds != 0, -1)) puts a second prompt on the null branch — the
+        result is neg + (pos - neg) * cond_scale with both branches evaluated at cond_drop_prob = 0.  A batch-1 negative prompt serves the
+        whole batch.  (`negative_texts` needs an encoder: Imagen.sample takes it; a bare unet has none.)
+
+        Prompt and negative prompt share one token axis, the longer one's.  One consequence for a call WITHOUT `text_mask` whose prompt is
+        the shorter of the two: the positions it is padded by are masked, so they become null_text_embed, where the same call without a
+        negative prompt leaves zero tokens from the prompt's end to max_text_len.  It is the result of passing text_mask = all ones over
+        the prompt's own tokens; pass a `text_mask` (Imagen.sample always derives one) and the conditional branch does not depend on
+        the negative prompt at all."""
+        _guided_negative(self, cond_scale, kwargs.get('text_embeds'), negative_texts, negative_text_embeds, negative_text_masks)
         if cond_scale == 1:
             return self.forward(*args, **kwargs)
         kwargs.pop('cond_drop_prob', None)
-        both = self._run(*args, cfg=True, **kwargs)
+        both = self._run(*args, cfg=True, negative_text_embeds=negative_text_embeds, negative_text_mask=negative_text_masks, **kwargs)
         b = both.shape[0] // 2
         logits, null_logits = both[:b], both[b:]
         return null_logits + (logits - null_logits) * cond_scale
@@ -286,7 +297,8 @@ class Unet3D(nn.Module):
 
     @torch.no_grad()
     def _run(self, x, time, *, lowres_cond_img=None, lowres_noise_times=None, text_embeds=None, text_mask=None, cond_drop_prob=0.,
-             ignore_time=False, cfg=False, cond_images=None, cond_video_frames=None, post_cond_video_frames=None, self_cond=None):
+             ignore_time=False, cfg=False, cond_images=None, cond_video_frames=None, post_cond_video_frames=None, self_cond=None,
+             negative_text_embeds=None, negative_text_mask=None):
         assert not (self.has_cond_image ^ (cond_images is not None)), \
             'you either requested to condition on an image on the unet, but the conditioning image is not supplied, or vice versa'   # iv.py:1722
         if cond_images is not None:
@@ -299,6 +311,8 @@ class Unet3D(nn.Module):
             raise RuntimeError("the MI355X path implements sampling (eval mode) only; call .eval() first")
         B, _, Fr, H, W = x.shape
         assert H == W, 'square frames only'
+        check_negative_prompt(negative_text_embeds, negative_text_mask, B,       # before an engine is built or anything is launched
+                              None if text_embeds is None else text_embeds.shape[-1])
         assert ignore_time or Fr % self.total_temporal_divisor == 0, \
             f'number of input frames {Fr} must be divisible by {self.total_temporal_divisor}'
         rows = 2 * B if cfg else B
@@ -321,7 +335,8 @@ class Unet3D(nn.Module):
         else:
             keep = torch.rand(B) < (1 - cond_drop_prob)
         eng.set_conditioning(text_embeds=text_embeds if with_text else None, text_mask=text_mask, keep=keep,
-                             lowres_noise_times=lowres_noise_times)
+                             lowres_noise_times=lowres_noise_times, negative_text_embeds=negative_text_embeds,
+                             negative_text_mask=negative_text_mask)
         # the engine's image layout is frame-major (b, f, c, h, w): frames of one clip are consecutive NHWC images
         to_fm = lambda t: t.float().permute(0, 2, 1, 3, 4).contiguous()
         out = eng.forward(to_fm(x), time.float().contiguous(), lowres_cond_img=None if lowres_cond_img is None else to_fm(lowres_cond_img))
