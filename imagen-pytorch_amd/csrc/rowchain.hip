@@ -89,20 +89,26 @@ __host__ __device__ inline size_t chain_tiles_bytes(const ImagenRowchainParams& 
   return (size_t)rows * Geo::pitch(g.p0_cols) + (size_t)rows * Geo::pitch(g.p1_cols) + (g.p2_cols ? (size_t)rows * Geo::pitch(g.p2_cols) : 0);
 }
 
+// RESPREP: where the gate and bias rows of the image start.  The K-split partials of the narrow layers go through the row tiles (dead by then),
+// (wk - 1) * T tiles of 4 KB per row block from the head of the LDS; with few input channels that is more than the row tiles hold, and the gate
+// and bias rows, which the owners read AFTER the reduction, have to lie behind it (make_part's wk)
+__host__ __device__ inline size_t resprep_gate_offset(const ImagenRowchainParams& p, int rows) {
+  size_t n = chain_tiles_bytes(p, rows);
+  const int T = p.C >> 5, ks = (p.inner + p.C2) >> 4;
+  if (T < 8) {
+    int wk = 8 / T;
+    if (wk > ks) wk = ks;
+    const size_t need = (size_t)(wk - 1) * T * (rows / 32) * 4096;
+    if (need > n) n = need;
+  }
+  return n;
+}
+
 __host__ __device__ inline size_t chain_lds_bytes(const ImagenRowchainParams& p, int rows) {
   size_t n = chain_tiles_bytes(p, rows);
   if (p.mode != IMAGEN_CHAIN_RESPREP) n += kGainFloats * sizeof(float);
   if (p.mode == IMAGEN_CHAIN_XATTN) n += (size_t)8 * kKvWave;
-  if (p.mode == IMAGEN_CHAIN_RESPREP) {
-    n += (size_t)2 * p.C * sizeof(float);
-    const int T = p.C >> 5, ks = (p.inner + p.C2) >> 4;
-    if (T < 8) {   // the K-split partials of the narrow layers go through the row tiles (dead by then): room for (wk - 1) * T tiles of 4 KB per row block
-      int wk = 8 / T;
-      if (wk > ks) wk = ks;
-      const size_t need = (size_t)(wk - 1) * T * (rows / 32) * 4096;
-      if (need > n) n = need;
-    }
-  }
+  if (p.mode == IMAGEN_CHAIN_RESPREP) n = resprep_gate_offset(p, rows) + (size_t)2 * p.C * sizeof(float);
   return (n + 15) & ~(size_t)15;
 }
 
@@ -137,9 +143,10 @@ __device__ __forceinline__ Part make_part(int T, int ksteps, int wave) {
     if (wk > ksteps) wk = ksteps;
     q.wk = wk;
     q.kpart = wave / T;
-    const int per = ksteps / wk;
-    q.s0 = q.kpart < wk ? q.kpart * per : 0;
-    q.s1 = q.kpart < wk ? q.s0 + per : 0;
+    // slice kpart = steps [kpart * ksteps / wk, (kpart + 1) * ksteps / wk): together exactly the ksteps steps, lengths one apart where wk does
+    // not divide them (RESPREP's 6, 10 or 18 steps over 4 or 8 slices; a floor(ksteps / wk) per slice left the last steps to nobody)
+    q.s0 = q.kpart < wk ? q.kpart * ksteps / wk : 0;
+    q.s1 = q.kpart < wk ? (q.kpart + 1) * ksteps / wk : 0;
   }
   // phase-shifted walk (conv_small.hip, call M: K loop 10.3k -> 6.6k cycles): every row tile streams the same weights, in lockstep when they all
   // start at the head of the slice — each ring refill is then a cold miss for all of them.  Neighbouring tiles of a small grid start at 0, 1/4,
@@ -970,7 +977,7 @@ __device__ __forceinline__ void chain_resprep(const ImagenRowchainParams& p, cha
   const int pitch0 = Geo::pitch(K), pitch1 = Geo::pitch(C);
   char* P0 = smem;
   char* P1 = P0 + (size_t)ROWS * pitch0;
-  float* s_gate = reinterpret_cast<float*>(P1 + (size_t)ROWS * pitch1);
+  float* s_gate = reinterpret_cast<float*>(smem + resprep_gate_offset(p, ROWS));
   float* s_bias = s_gate + C;
   const int r = tid / LPR, li = tid % LPR;
   const int b = row0 / p.rows_per_batch;

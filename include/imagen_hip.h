@@ -498,7 +498,8 @@ typedef struct ImagenMemset32Params { void* dst; uint32_t value; int32_t count; 
  *        o_h = fp16(softmax_j(q^_h . K^[b, h, j]) @ V[b, h])          q^_h = fp16(q_h / max(|q_h|, 1e-12) * q_scale * q_mult), j < J (ATTENTION's contract)
  *        out = fp16(LN(fp16(o W_out^T)) * g1 + x) ;  ssq_out
  *   mode 3, QKV  (ip.py:521-561; replaces (ROWSTAT ->) qkv IGEMM -> KV_PREP of the self-attention rows):
- *        y   = fp16(fp16((x - mean x) * rstd x * g0) [Wq | Wkv]^T)    [rows][heads * 64 + 128];  out[r, : heads * 64] = q
+ *        y   = fp16(fp16((x - mean x) * rstd x * g0) [Wq | Wkv]^T)    [rows][heads * 64 + 128];  out[r, : heads * 64] = q, and ONLY those columns of an
+ *        output row are written: k | v (columns heads * 64 .. heads * 64 + 127 of y) leave the launch as K^ / V^T alone, whatever ld_out leaves room for
  *        K^[b, r0 + n, :] = fp16(k / max(|k|, 1e-12) * k_scale),  V^T[b, :, r0 + n] = v      (KV_PREP's contract, one shared k / v head)
  *   mode 4, RESPREP (ip.py:741, 753-757 + the NEXT block's 683-690; replaces the up path's res_conv IGEMM -> the next Block's ACT_PREP):
  *        out = fp16(concat(x, x2) Wres^T + bias + addend * gate[b, :]) ;   (gate NULL: + addend)  ssq_out[r] = sum_c out^2            the ResnetBlock's `h * gate + res_conv(x)`

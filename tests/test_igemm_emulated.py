@@ -85,6 +85,20 @@ def test_emulated_rowchain_kernels():
 
 
 @pytest.mark.skipif(not os.path.exists(CLANG), reason="host clang of the ROCm toolchain not present")
+def test_emulated_rowchain_contract():
+    """csrc/rowchain.hip per row against the fp64 restatement of its contract and the launch-per-op plans, at the shapes the launcher takes beyond
+    the engine's: uneven and clamped K-splits, one tile per image, 1 .. 292 keys, a late row maximum, strided rows, sentinels around every output
+    (tests/test_rowchain_contract_gpu.py: the whole file, about a minute on the emulation)."""
+    env = dict(os.environ, IMAGEN_LIB_PATH=_lib(""), IMAGEN_EMUL_TESTS="1")
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_rowchain_contract_gpu.py"), "-q", "-m", "gpu", "-p", "no:cacheprovider"],
+                       env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
+    out = r.stdout.decode()
+    assert r.returncode == 0 and "failed" not in out, out[-3000:]
+    passed = int(out.split(" passed")[0].split()[-1])
+    assert passed == 44 and "skipped" not in out.splitlines()[-1], out[-800:]
+
+
+@pytest.mark.skipif(not os.path.exists(CLANG), reason="host clang of the ROCm toolchain not present")
 def test_emulated_elementwise_kernels():
     """csrc/elementwise.hip — every glue kernel on every branch an engine call site selects, per row / per element against fp64, sentinels
     around every output, the launchers' refusals — on the emulation in a child pytest (tests/test_elementwise_kernels_gpu.py; the whole file
