@@ -250,7 +250,8 @@ __device__ __forceinline__ void cl_epilogue(const ImagenIgemmParams& p, const Cl
         gca_k[mi] = op[mi] >= 0 ? gca_k[mi] + p.gca_bk : -3.0e38f;
         mx = fmaxf(mx, gca_k[mi]);
       }
-      mx = __builtin_amdgcn_readlane(cl_half_reduce<true>(mx), 63) ;   // (both half-waves hold the same pixels)
+      // (both half-waves hold the same pixels; readlane is an integer builtin: the float goes through it as its bits)
+      mx = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cl_half_reduce<true>(mx)), 63));
       if (WM > 1) {
         if (l31 == 0 && half == 0 && wn == 0) gm[wm] = mx;
         __syncthreads();

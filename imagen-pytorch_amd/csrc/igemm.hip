@@ -1058,6 +1058,27 @@ int launch_igemm(const ImagenIgemmParams* pp, hipStream_t s) {
   IMAGEN_CHECK(!p.pad_x1 || p.cfg < kNumCfgs, "igemm: pad_x1 (an x padding of its own) is implemented by kernel family 0 only (cfg %d)", p.cfg);
   IMAGEN_CHECK(p.pad_x1 >= 0, "igemm: pad_x1 %d", p.pad_x1);
   IMAGEN_CHECK(!p.gca_part || p.cfg >= kNumCfgs, "igemm: gca_part is implemented by the kernel families 2, 5, 7 and 8 only (cfg %d)", p.cfg);
+  // Alignment of the fp16 operands, for every family (each adds what only it needs): inputs are staged in 16-byte pieces (8 channels) from
+  // x + b * bs + pixel * ld + 8 k; the epilogues load addend / res and store y four channels (8 bytes) at a time, and the plain and post_pa
+  // stores of a Cout % 8 == 0 output go in 16-byte pieces (the generic epilogue of family 0 tests its operands itself before it widens).
+  auto al = [](const void* q, size_t a) { return ((size_t)q & (a - 1)) == 0; };
+  IMAGEN_CHECK(p.bs1 % 8 == 0 && al(p.x1, 16) && (!p.x2 || (p.bs2 % 8 == 0 && al(p.x2, 16))),
+               "igemm: input images must start on 16 bytes (bs1 %d bs2 %d, x1 %p x2 %p)", p.bs1, p.bs2, p.x1, p.x2);
+  if (p.out_mode != IMAGEN_OUT_NCHW_F32) {
+    IMAGEN_CHECK(p.ldy % 4 == 0 && p.bsy % 4 == 0 && al(p.y, 8), "igemm: output pixels must start on 8 bytes (ldy %d bsy %d y %p)", p.ldy, p.bsy, p.y);
+    const bool pieces16 = p.out_mode == IMAGEN_OUT_NHWC && p.Cout % 8 == 0 && !p.addend && !p.res && p.act_out == IMAGEN_ACT_NONE;
+    IMAGEN_CHECK(!pieces16 || (p.ldy % 8 == 0 && p.bsy % 8 == 0 && al(p.y, 16)),
+                 "igemm: a plain output of Cout %% 8 == 0 channels is stored in 16-byte pieces (ldy %d bsy %d y %p)", p.ldy, p.bsy, p.y);
+    IMAGEN_CHECK(!p.addend || (p.ld_add % 4 == 0 && p.bs_add % 4 == 0 && al(p.addend, 8)), "igemm: addend pixels must start on 8 bytes (ld %d bs %d %p)",
+                 p.ld_add, p.bs_add, p.addend);
+    IMAGEN_CHECK(!p.res || (p.ld_res % 4 == 0 && p.bs_res % 4 == 0 && al(p.res, 8)), "igemm: residual pixels must start on 8 bytes (ld %d bs %d %p)",
+                 p.ld_res, p.bs_res, p.res);
+  }
+  // the per-channel fp32 operands are read four floats at a time, at b * stride + a multiple of 4
+  IMAGEN_CHECK(p.pstride % 4 == 0 && al(p.pa, 16) && al(p.ps, 16), "igemm: pa / ps rows must start on 16 bytes (pstride %d, pa %p ps %p)", p.pstride, p.pa, p.ps);
+  IMAGEN_CHECK(!p.addend || (p.gate_stride % 4 == 0 && al(p.gate, 16)), "igemm: gate rows must start on 16 bytes (gate_stride %d, gate %p)", p.gate_stride, p.gate);
+  IMAGEN_CHECK(!p.post_pa || (p.post_pstride % 4 == 0 && al(p.post_pa, 16) && al(p.post_ps, 16)),
+               "igemm: post_pa / post_ps rows must start on 16 bytes (post_pstride %d, %p %p)", p.post_pstride, p.post_pa, p.post_ps);
   const CfgRef r = cfg_ref(p.cfg);
   if (r.fam) return r.fam->launch(pp, r.idx, s);
   switch (p.cfg) {

@@ -504,11 +504,13 @@ def _twice(plan: "Plan", v: Optional[torch.Tensor], C: int, n: int) -> Optional[
 class Align(NamedTuple):
     """The 16-byte facts of one fp16 NHWC operand (8 elements): pixel pitch, image pitch, base address."""
     ld8: bool; bs8: bool; p16: bool   # noqa: E702
+    ok8: bool                         # the 8-byte facts (4 elements) of the same three: what an epilogue's four-channel accesses need
     strides8 = property(lambda a: a.ld8 and a.bs8)
+    all16 = property(lambda a: a.ld8 and a.bs8 and a.p16)
 
 
 def _align(a) -> Optional[Align]:
-    return Align(a.ld % 8 == 0, a.bs % 8 == 0, a.ptr % 16 == 0) if isinstance(a, Act) else None
+    return Align(a.ld % 8 == 0, a.bs % 8 == 0, a.ptr % 16 == 0, a.ld % 4 == 0 and a.bs % 4 == 0 and a.ptr % 8 == 0) if isinstance(a, Act) else None
 
 
 @dataclass(frozen=True)
@@ -536,6 +538,11 @@ class ConvReq:
     plain_ep = property(lambda r: r.act_out == ACT_NONE and r.out_mode == OUT_NHWC and r.addend is None and r.res is None)   # bias + NHWC store
     cout_vec4 = property(lambda r: r.out_mode == OUT_NCHW_F32 or r.Cout % 4 == 0)                     # the fp16 epilogues store four channels at a time
     want_gca = property(lambda r: r.gca and r.plain_ep and not r.want_post)
+    # launch_igemm's alignment predicate, the same for every family: input images start on 16 bytes (the pixel pitch is each family's own
+    # term), output / addend / residual pixels on 8, and on 16 where a plain or post_pa output of Cout % 8 == 0 is stored in 16-byte pieces
+    io_ok = property(lambda r: r.x1.bs8 and r.x1.p16 and (r.x2 is None or (r.x2.bs8 and r.x2.p16))
+                     and (r.y is None or (r.y.ok8 and (r.y.all16 or not (r.plain_ep and r.Cout % 8 == 0))))
+                     and (r.addend is None or r.addend.ok8) and (r.res is None or r.res.ok8))
     full_cout = property(lambda r: (r.want_ssq or r.want_post or r.want_gca) and r.out_mode == OUT_NHWC)   # the epilogue needs all channels of a pixel in one tile
     # the GlobalContext partials are to come out of this launch's epilogue (16x16 tiles): such a layer goes to family 2, the persistent streaming
     # kernels measured slower with them (round 4 call F)
@@ -639,7 +646,10 @@ ROUTES = (_route_small, _route_pro, _route_stream, _route_pw, _route_gemm, _rout
 
 
 def route(req: ConvReq) -> tuple:
-    """(cfg, TH, TW) of the first family of ROUTES that takes the request (_route_tiled, the last, answers or raises)."""
+    """(cfg, TH, TW) of the first family of ROUTES that takes the request (_route_tiled, the last, answers or raises).  An operand whose
+    alignment no family's accesses can take (ConvReq.io_ok: launch_igemm refuses it for all of them) has no route."""
+    if not req.io_ok:
+        raise ValueError(f"no conv family takes operands aligned like this (16-byte input images, 8- / 16-byte output pixels): {req}")
     return next(got for got in (fn(req) for fn in ROUTES) if got is not None)
 
 

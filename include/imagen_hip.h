@@ -86,6 +86,12 @@ enum ImagenOpKind {
  *   y         = v   (NHWC fp16 | pixel-shuffle NHWC fp16 | NCHW fp32);   ssq_out[q] = sum_o fp16(v)^2   (optional)
  *   or, with post_pa:  y = silu(v / max(||v||_2 over o, 1e-12) * post_pa[b,o] + post_ps[b,o])        (the next Block's prologue)
  *
+ * Rounding: `a` is the fp16 operand of the matrix pipe — with a prologue it is fp16(act_in(...)) of an fp32 evaluation (what ACT_PREP stores),
+ * without one the input element itself; acc, v and the norm of post_pa are fp32 and y is rounded once, on the store.
+ * Alignment: input images start on 16 bytes (bs % 8 == 0, 16-byte base; the pixel pitch ld % 8 == 0), output / addend / residual pixels on
+ * 8 bytes (ld % 4 == 0, bs % 4 == 0), and a plain or post_pa NHWC output of Cout % 8 == 0 channels on 16; pa / ps / gate / post_pa / post_ps rows
+ * on 16 bytes (pstride, gate_stride, post_pstride % 4 == 0, 16-byte bases: read four floats at a time); the kernel families add their own.
+ *
  * Weights are pre-packed by imagen_pack_igemm_weights() into MFMA-fragment order.
  */
 enum { IMAGEN_ACT_NONE = 0, IMAGEN_ACT_SILU = 1, IMAGEN_ACT_GELU = 2 };
