@@ -601,6 +601,20 @@ int launch_attention(const ImagenAttentionParams* p, hipStream_t s) {
   IMAGEN_CHECK(p->rows > 0 && p->J > 0 && p->B > 0 && p->heads > 0, "attention: empty problem");
   IMAGEN_CHECK(p->q_rs % 8 == 0 && p->k_rs % 8 == 0 && p->vt_ds % 8 == 0 && p->o_rs % 4 == 0,
                "attention: strides must keep 16B alignment");
+  // what the kernels' other accesses take: 16-byte loads at b*q_bs + h*q_hs, b*k_bs + h*k_hs and b*vt_bs + h*vt_hs + d*vt_ds + key0, 8-byte
+  // stores at b*o_bs + h*o_hs, float4 loads of q_scale, V^T rows of round_up(J, 32) keys.  A stride of 0 (a shared k / v head) is a multiple
+  IMAGEN_CHECK(p->q && p->k && p->vt && p->o, "attention: null pointer (q %p k %p vt %p o %p)", p->q, p->k, p->vt, (const void*)p->o);
+  {
+    const struct { const char* name; long long v; int m; } al[] = {
+        {"q_bs", p->q_bs, 8}, {"q_hs", p->q_hs, 8}, {"k_bs", p->k_bs, 8}, {"k_hs", p->k_hs, 8}, {"vt_bs", p->vt_bs, 8}, {"vt_hs", p->vt_hs, 8},
+        {"o_bs", p->o_bs, 4}, {"o_hs", p->o_hs, 4}};
+    for (const auto& a : al) IMAGEN_CHECK(a.v % a.m == 0, "attention: %s = %lld must be a multiple of %d elements", a.name, a.v, a.m);
+    const struct { const char* name; const void* ptr; int m; } pt[] = {
+        {"q", p->q, 16}, {"k", p->k, 16}, {"vt", p->vt, 16}, {"o", p->o, 8}, {"q_scale", p->q_scale, 16}};
+    for (const auto& a : pt)
+      IMAGEN_CHECK(reinterpret_cast<uintptr_t>(a.ptr) % a.m == 0, "attention: %s = %p must be %d-byte aligned", a.name, a.ptr, a.m);
+  }
+  IMAGEN_CHECK(p->vt_ds >= ((p->J + 31) & ~31), "attention: vt_ds = %d holds fewer than round_up(J = %d, 32) keys", p->vt_ds, p->J);
   IMAGEN_CHECK(p->head_dim == 0 || p->head_dim == 64 || p->head_dim == 32, "attention: head_dim %d (64 or 32)", p->head_dim);
   IMAGEN_CHECK(p->softmax_mode == 0 || p->softmax_mode == 1, "attention: softmax_mode %d", p->softmax_mode);
   if (p->head_dim != 32 && p->rows >= 256) {

@@ -179,7 +179,9 @@ typedef struct ImagenRowstatParams {
  *   o[r] = softmax_j(q[r] . k[j]) @ v   for r in rows, j in [0, J)
  * Addressing: q/o row r of (batch b, head h): base + b*q_bs + h*q_hs + r*q_rs ; k: b*k_bs + h*k_hs + j*k_rs ;
  * vt: b*vt_bs + h*vt_hs + d*vt_ds + j.   head_dim: 64 (0 means 64) or 32 — the reference's UnetConfig default is 32 x 16 heads
- * (configs.py:48-49), every README config uses 64. */
+ * (configs.py:48-49), every README config uses 64.
+ * Required (refused otherwise): q, k, vt 16-byte and o 8-byte aligned, none null; q_scale null or 16-byte aligned; every q / k / vt stride a multiple of 8
+ * elements and every o stride a multiple of 4 (0 is one: a shared k / v head); vt_ds >= round_up(J, 32), keys [J, round_up(J, 32)) of K^ and V^T zero. */
 typedef struct ImagenAttentionParams {
   const void* q; const void* k; const void* vt; void* o;
   int32_t B, heads, rows, J;

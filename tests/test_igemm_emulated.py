@@ -99,6 +99,21 @@ def test_emulated_rowchain_contract():
 
 
 @pytest.mark.skipif(not os.path.exists(CLANG), reason="host clang of the ROCm toolchain not present")
+def test_emulated_attention_contract():
+    """csrc/attention.hip per element against the fp64 restatement of ATTENTION's contract at a derived bound: the four tilings at 1 .. 449 keys and
+    1 .. 513 rows, the engine's self / cross layouts and the shared-head form on strided, guarded operands, fused QNORM, logits at the bound,
+    a late maximum in some rows of a wave, the launcher's alignment predicates (tests/test_attention_contract_gpu.py: the whole file, about a
+    minute on the emulation; no case is hardware-only)."""
+    env = dict(os.environ, IMAGEN_LIB_PATH=_lib(""), IMAGEN_EMUL_TESTS="1")
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_attention_contract_gpu.py"), "-q", "-m", "gpu", "-p", "no:cacheprovider"],
+                       env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
+    out = r.stdout.decode()
+    assert r.returncode == 0 and "failed" not in out, out[-3000:]
+    passed = int(out.split(" passed")[0].split()[-1])
+    assert passed == 127 and "skipped" not in out.splitlines()[-1], out[-800:]
+
+
+@pytest.mark.skipif(not os.path.exists(CLANG), reason="host clang of the ROCm toolchain not present")
 def test_emulated_conv_contract():
     """Every conv / GEMM kernel family per pixel against the fp64 restatement of the IGEMM contract and the launch-per-op plan, on strided operands
     in guarded allocations: channel slices, maps smaller than a tile, ragged all-cout epilogues, the shortest persistent tile ranges, the
