@@ -1,6 +1,5 @@
 """Negative prompts (a second text prompt on the null rows of guidance): the loaders of tests/golden/negprompt_*.pt
-(tools/make_negprompt_golden.py), the fixture models, a guided forward pair on the plan interpreter, and the launch lists of the fixture
-stages in the form of tests/golden/negprompt_parent_launch_list_abi<N>.json.
+(tools/make_negprompt_golden.py), the fixture models, and the launch lists of the fixture stages in the form of tests/golden/negprompt_parent_launch_list_abi<N>.json.
 
 The models: an image cascade 16^2 -> 32^2 of two dim-16 unets, dim_mults (1, 2) — stage 1 is the flag-off `twin` of
 tests/golden/linxattn_unet.pt (weights stored there), stage 2 its low-res-conditioned sibling (negprompt_unet_sr.pt) — under Imagen (DDPM)
@@ -8,35 +7,23 @@ and ElucidatedImagen (Karras), and the tiny Unet3D of tests/golden/sample_tiny_v
 TEST INFRASTRUCTURE, never imported by the product."""
 from __future__ import annotations
 
-import os
-
 import torch
 
-import plan_interp_linxattn as lx
-from plan_interp_selfcond import nerr, unpack_state_dict  # noqa: F401
+import fixtures_linxattn as lx
+from fixtures_common import GOLDEN, load, nerr, unpack_state_dict  # noqa: F401
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 KW_SR = dict(dim=16, cond_dim=16, text_embed_dim=32, dim_mults=(1, 2), num_resnet_blocks=1, layer_attns=(False, True),
              layer_cross_attns=(False, True), max_text_len=16, attn_pool_num_latents=8, attn_heads=2, attn_dim_head=64, lowres_cond=True)
 IMAGE_SIZES = (16, 32)
 VIDEO_SIZE, VIDEO_FRAMES = 16, 4
 T = 4
 
-_cache = {}
-
-
-def _load(name):
-    if name not in _cache:
-        _cache[name] = torch.load(os.path.join(GOLDEN, name), weights_only=False)
-    return _cache[name]
-
-
 def forward_fixture():
-    return _load("negprompt_forward.pt")
+    return load("negprompt_forward.pt")
 
 
 def runs_fixture():
-    return _load("negprompt_runs.pt")
+    return load("negprompt_runs.pt")
 
 
 def base_kwargs():
@@ -48,7 +35,7 @@ def base_unet(device="cpu"):
 
 
 def video_kwargs():
-    return dict(_load("sample_tiny_video.pt")["unets"][0]["kwargs"])
+    return dict(load("sample_tiny_video.pt")["unets"][0]["kwargs"])
 
 
 def image_model(kind, device="cpu", weights=True):
@@ -64,7 +51,7 @@ def image_model(kind, device="cpu", weights=True):
         model = model.to(device)
     if weights:
         model.unets[0].load_state_dict(lx.unet_record("twin")[1])
-        model.unets[1].load_state_dict(unpack_state_dict(_load("negprompt_unet_sr.pt")))
+        model.unets[1].load_state_dict(unpack_state_dict(load("negprompt_unet_sr.pt")))
     return model.eval()
 
 
@@ -81,30 +68,8 @@ def video_model(device="cpu", weights=True):
     if str(device) != "cpu":
         model = model.to(device)
     if weights:
-        model.unets[0].load_state_dict(_load("sample_tiny_video.pt")["unets"][0]["state_dict"])
+        model.unets[0].load_state_dict(load("sample_tiny_video.pt")["unets"][0]["state_dict"])
     return model.eval()
-
-
-def run_pair(u, f, neg=None, neg_mask=None, interp=None):
-    """One guided pair (cond rows, then null rows) of `u` on the inputs f, the null rows on the learned null conditioning or, with `neg`,
-    on that prompt: the dry-run launch lists of engine.UnetEngine executed by the interpreter.  Returns (out_cond, out_null, engine)."""
-    from imagen_pytorch_amd.engine import UnetEngine
-
-    B, S = f["x"].shape[0], f["x"].shape[-1]
-    eng = UnetEngine(u, 2 * B, B, S, "cpu", dry=True)
-    keep = torch.tensor([True] * B + [False] * B)
-    kw = {} if neg is None else dict(negative_text_embeds=neg, negative_text_mask=neg_mask)
-    eng.set_conditioning(text_embeds=f["text_embeds"], text_mask=f["text_mask"], keep=keep, lowres_noise_times=None, **kw)
-    it = (interp or lx.InterpreterLX)()
-    for buf in (eng.x_in, eng.times, eng.lowres_times, eng.out, eng.keep_u8, eng.src_idx, eng.arange_idx, eng.t_const.t):
-        it.mem.register(buf)
-    for plan in eng._last_static:
-        it.run(plan)
-    eng.x_in.copy_(f["x"])
-    eng.times.copy_(f["time"].repeat(2))
-    it.run(eng.step_plan)
-    out = eng.out.float().clone()
-    return out[:B], out[B:], eng
 
 
 def _ops(plan):

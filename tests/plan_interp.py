@@ -9,9 +9,15 @@ those are checked against fp32 torch and the oracle by the `-m gpu` tests.
 
 Weights: `ops.KEEP_REFERENCE_WEIGHTS = True` makes `ops.pack_weight` remember the unpacked (fp16-rounded) weight behind every
 packed buffer, because the packed MFMA-fragment order is a kernel-private detail.
+
+`Interpreter` states the header of the commit it sits in: `DISPATCH` holds one entry per op kind of `_abi.OP_STRUCT`.  The contracts that
+the kernel tests measure their kernels against in fp64 (`temporal_attention_contract`, `linctx_contract`, `linear_xattn_contract`) are
+written once, over plain tensors with a `dtype`; the interpreter calls them in fp32.  `register_engine` / `run_engine` are the driver of a
+dry engine: a guided pair or a single forward.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import Dict
 
@@ -59,6 +65,61 @@ def _act(x, kind):
     if kind == ops.ACT_GELU:
         return F.gelu(x)
     return x
+
+
+def temporal_attention_contract(qkv, null_kv, q_scale, k_scale, bias, *, heads, D, causal, scale, dtype=f32):
+    """TEMPORAL_ATTENTION: o [B, F, P, heads * D] in `dtype` from fp16 rows qkv [B, F, P, heads * D + 2 D] (q | k | v), fp32 null_kv [2, D],
+    q_scale / k_scale [D] and bias [heads, F, F + 1] (column 0 = the null key).  Written over the whole key axis: no frame bound."""
+    B, Fr, P, _ = qkv.shape
+    rows = qkv.to(dtype)
+    q = rows[..., :heads * D].reshape(B, Fr, P, heads, D).permute(0, 2, 3, 1, 4)                       # b p h i d
+    k, v = rows[..., heads * D:heads * D + D].permute(0, 2, 1, 3), rows[..., heads * D + D:].permute(0, 2, 1, 3)   # b p j d
+    nkv = null_kv.to(dtype).reshape(2, D)
+    k = torch.cat((nkv[0].expand(B, P, 1, D), k), dim=2)
+    v = torch.cat((nkv[1].expand(B, P, 1, D), v), dim=2)
+    qh = F.normalize(q, dim=-1, eps=1e-12) * q_scale.to(dtype) * scale
+    kh = F.normalize(k, dim=-1, eps=1e-12) * k_scale.to(dtype)
+    sim = torch.einsum("bphid,bpjd->bphij", qh, kh) + bias.to(dtype)
+    if causal:
+        sim = sim.masked_fill(torch.ones(Fr, Fr + 1, dtype=torch.bool).triu(2), -torch.finfo(sim.dtype).max)
+    o = torch.einsum("bphij,bpjd->bphid", sim.softmax(-1), v)                                          # b p h i d
+    return o.permute(0, 3, 1, 2, 4).reshape(B, Fr, P, heads * D)
+
+
+def linctx_contract(kv, heads, D, dtype=f32):
+    """LINCTX: M [R, heads, D, D] in `dtype` from fp16 rows kv [R, J, 2 * heads * D] (k | v): softmax of k over the J rows, then k^T v."""
+    R, J, _ = kv.shape
+    k = kv[..., :heads * D].to(dtype).reshape(R, J, heads, D)
+    v = kv[..., heads * D:].to(dtype).reshape(R, J, heads, D)
+    return torch.einsum("rjha,rjhb->rhab", k.softmax(dim=1), v)
+
+
+def linear_xattn_contract(q, M, heads, D, dtype=f32):
+    """LINEAR_XATTN: o [R, N, heads * D] in `dtype` from fp16 q [R, N, heads * D] and M [R, heads, D, D]: 8 * softmax of q over D, times M."""
+    R, N, _ = q.shape
+    return (8.0 * torch.einsum("rnha,rhab->rnhb", q.to(dtype).reshape(R, N, heads, D).softmax(dim=-1), M.to(dtype))).reshape(R, N, heads * D)
+
+
+def philox_normal(B, n, *, seed_lo, seed_hi, tag, stream_id, sample_offset):
+    """RANDN's stream in fp32: Philox4x32-10 on the counter (i / 4, tag, stream_id, sample_offset + b) under the key (seed_lo, seed_hi); the
+    four words c of a block give u = (c + 0.5) * 2^-32 and, by Box-Muller, r0 (cos, sin)(2 pi u1), r1 (cos, sin)(2 pi u3) with
+    r0 / r1 = sqrt(-2 log max(u0 / u2, 1e-12)) (csrc/sampler.hip philox_normal4).  n % 4 == 0."""
+    import numpy as np
+
+    assert n % 4 == 0, "randn: n_per_sample must be a multiple of 4"
+    u64, M32 = np.uint64, np.uint64(0xFFFFFFFF)
+    c0 = np.broadcast_to(np.arange(n // 4, dtype=u64), (B, n // 4))
+    c1, c2 = np.full_like(c0, tag), np.full_like(c0, stream_id)
+    c3 = np.broadcast_to(((sample_offset + np.arange(B)) & 0xFFFFFFFF).astype(u64)[:, None], c0.shape)
+    k0, k1 = seed_lo, seed_hi
+    for _ in range(10):
+        p0, p1 = u64(0xD2511F53) * c0, u64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> u64(32)) ^ c1 ^ u64(k0), p1 & M32, (p0 >> u64(32)) ^ c3 ^ u64(k1), p0 & M32
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    u0, u1, u2, u3 = ((torch.from_numpy(c.astype(np.float32)) + 0.5) * 2.3283064365386963e-10 for c in (c0, c1, c2, c3))
+    r0, r1 = (torch.sqrt(-2.0 * torch.log(u.clamp(min=1e-12))) for u in (u0, u2))
+    a0, a1 = 6.283185307179586 * u1, 6.283185307179586 * u3
+    return torch.stack((r0 * a0.cos(), r0 * a0.sin(), r1 * a1.cos(), r1 * a1.sin()), dim=-1).reshape(B, n)
 
 
 class Interpreter:
@@ -511,21 +572,32 @@ class Interpreter:
 
     def temporal_attention(self, p):
         m = self.mem
+        D = p.head_dim or 64
+        assert D in (32, 64), D
         Fr, P, H = p.F, p.P, p.heads
-        rows = m.strided(p.qkv, f16, (p.B, Fr, P, H * 64 + 128), (Fr * P * p.ld, P * p.ld, p.ld, 1)).float()
-        q = rows[..., :H * 64].reshape(p.B, Fr, P, H, 64).permute(0, 2, 3, 1, 4)          # b p h i d
-        k, v = rows[..., H * 64:H * 64 + 64].permute(0, 2, 1, 3), rows[..., H * 64 + 64:].permute(0, 2, 1, 3)   # b p j d
-        nkv = m.view(p.null_kv, f32)[:128].reshape(2, 64)
-        k = torch.cat((nkv[0].expand(p.B, P, 1, 64), k), dim=2)
-        v = torch.cat((nkv[1].expand(p.B, P, 1, 64), v), dim=2)
-        qh = F.normalize(q, dim=-1, eps=1e-12) * m.view(p.q_scale, f32)[:64] * p.scale
-        kh = F.normalize(k, dim=-1, eps=1e-12) * m.view(p.k_scale, f32)[:64]
-        sim = torch.einsum("bphid,bpjd->bphij", qh, kh) + m.view(p.bias, f32)[:H * Fr * (Fr + 1)].reshape(H, Fr, Fr + 1)
-        if p.causal:
-            sim = sim.masked_fill(torch.ones(Fr, Fr + 1, dtype=torch.bool).triu(2), -torch.finfo(sim.dtype).max)
-        o = torch.einsum("bphij,bpjd->bphid", sim.softmax(-1), v)                       # b p h i d
-        o = o.permute(0, 3, 1, 2, 4).reshape(p.B, Fr, P, H * 64)
-        m.strided(p.o, f16, (p.B, Fr, P, H * 64), (Fr * P * p.ld_o, P * p.ld_o, p.ld_o, 1)).copy_(o.half())
+        qkv = m.strided(p.qkv, f16, (p.B, Fr, P, H * D + 2 * D), (Fr * P * p.ld, P * p.ld, p.ld, 1))
+        o = temporal_attention_contract(qkv, m.view(p.null_kv, f32)[:2 * D], m.view(p.q_scale, f32)[:D], m.view(p.k_scale, f32)[:D],
+                                        m.view(p.bias, f32)[:H * Fr * (Fr + 1)].reshape(H, Fr, Fr + 1), heads=H, D=D, causal=p.causal, scale=p.scale)
+        m.strided(p.o, f16, (p.B, Fr, P, H * D), (Fr * P * p.ld_o, P * p.ld_o, p.ld_o, 1)).copy_(o.half())
+
+    # ------------------------------------------------------------------------------------------------ linear cross-attention
+    def linctx(self, p):
+        m = self.mem
+        st = _abi.STRUCTS["ImagenLinCtxJob"]
+        for i in range(p.n):
+            j = st.from_address(p.jobs + i * ctypes.sizeof(st))
+            D, H = j.head_dim, j.heads
+            assert D in (32, 64) and j.R * H <= p.max_bh
+            M = linctx_contract(m.strided(j.kv, f16, (j.R, j.J, 2 * H * D), (j.kv_bs, j.kv_rs, 1)), H, D)
+            m.view(j.M, f32)[:M.numel()].copy_(M.reshape(-1))
+
+    def linear_xattn(self, p):
+        m = self.mem
+        D, H, N = p.head_dim, p.heads, p.rows
+        assert D in (32, 64)
+        q = m.strided(p.q, f16, (p.R, N, H * D), (N * p.ld_q, p.ld_q, 1))
+        o = linear_xattn_contract(q, m.view(p.M, f32)[:p.R * H * D * D].reshape(p.R, H, D, D), H, D)
+        m.strided(p.o, f16, (p.R, N, H * D), (N * p.ld_o, p.ld_o, 1)).copy_(o.half())
 
     # ------------------------------------------------------------------------------------------------ sampler ops (injected noise only)
     def _coef_row(self, coef, step_ptr):
@@ -576,25 +648,33 @@ class Interpreter:
         if not p.no_advance:
             m.view(p.step_ptr, i32)[0] += 1
 
+    def randn(self, p):
+        z = philox_normal(p.B, p.n_per_sample, seed_lo=p.seed_lo, seed_hi=p.seed_hi, tag=p.tag, stream_id=p.stream_id, sample_offset=p.sample_offset)
+        self.mem.view(p.out, f32)[:p.B * p.n_per_sample].copy_(z.reshape(-1))
+
     def lincomb(self, p):
         m = self.mem
         n = p.B * p.n_per_sample
         _, w = self._coef_row(p.coef, p.step_ptr)
         assert float(w[4]) == 0.0, "the interpreter only supports injected noise (pass it as t1)"
-        thr = lambda t, q: t
-        if p.thr_mode == 1:
-            def thr(t, q):
-                s = m.view(q, f32)[: p.B].clamp(min=1.0).reshape(p.B, 1)
+
+        def thr(t, q):
+            if p.thr_mode == 1:
+                s = (m.view(q, f32)[: p.B].clamp(min=1.0) if q else torch.ones(p.B)).reshape(p.B, 1)
                 return (t.reshape(p.B, -1).clamp(-s, s) / s).reshape(-1)
-        elif p.thr_mode == 2:
-            thr = lambda t, q: t.clamp(-1.0, 1.0)
+            return t.clamp(-1.0, 1.0) if p.thr_mode == 2 else t
+
+        assert (p.t1 or not p.thr1_out) and (p.t3 or not p.thr3_out), "thr1_out needs t1, thr3_out needs t3"
+        th1 = thr(m.view(p.t1, f32)[:n], p.q1) if p.t1 else None     # the values that enter the sum: what thr1_out / thr3_out receive
+        th3 = thr(m.view(p.t3, f32)[:n], p.q3) if p.t3 else None
+        thr_outs = [(dst, th.clone()) for dst, th in ((p.thr1_out, th1), (p.thr3_out, th3)) if dst]   # formed BEFORE anything is written
         v = w[0] * m.view(p.t0, f32)[:n]
         if p.t1:
-            v = v + w[1] * thr(m.view(p.t1, f32)[:n], p.q1)
+            v = v + w[1] * th1
         if p.t2:
             v = v + w[2] * m.view(p.t2, f32)[:n]
         if p.t3:
-            v = v + w[3] * thr(m.view(p.t3, f32)[:n], p.q3)
+            v = v + w[3] * th3
         if p.mask:
             v = torch.where(m.view(p.mask, f32)[:n] != 0, v, m.view(p.mask_else, f32)[:n])
         v = v.clone()
@@ -603,6 +683,8 @@ class Interpreter:
             m.view(p.out2, f32)[:n].copy_(w[5] * v)
         if p.final and p.final_out:
             m.view(p.final_out, f32)[:n].copy_((v.clamp(-1.0, 1.0) + 1.0) * 0.5)
+        for dst, th in thr_outs:
+            m.view(dst, f32)[:n].copy_(th)
         if p.advance:
             m.view(p.step_ptr, i32)[0] += 1
 
@@ -613,7 +695,7 @@ class Interpreter:
         n = p.B * p.C * p.Hout * p.Wout
         m.view(p.out, f32)[:n].copy_((p.alpha * (up * 2.0 - 1.0) + p.sigma * m.view(p.noise, f32)[:n].reshape(up.shape)).reshape(-1))
 
-    DISPATCH = {}
+    DISPATCH = {}     # op kind -> method: one entry per kind of _abi.OP_STRUCT (filled below)
 
 
 Interpreter.DISPATCH = {
@@ -626,10 +708,45 @@ Interpreter.DISPATCH = {
     K["IMAGEN_OP_PACK_IMAGE"]: Interpreter.pack_image, K["IMAGEN_OP_ROWS_COPY"]: Interpreter.rows_copy, K["IMAGEN_OP_MEMSET32"]: Interpreter.memset32,
     K["IMAGEN_OP_SELECT_ROWS"]: Interpreter.select_rows, K["IMAGEN_OP_MEAN_ROWS"]: Interpreter.mean_rows,
     K["IMAGEN_OP_CFG_X0"]: Interpreter.cfg_x0, K["IMAGEN_OP_QUANTILE"]: Interpreter.quantile, K["IMAGEN_OP_DDPM_UPDATE"]: Interpreter.ddpm_update,
-    K["IMAGEN_OP_LINCOMB"]: Interpreter.lincomb, K["IMAGEN_OP_LOWRES_PREP"]: Interpreter.lowres_prep,
+    K["IMAGEN_OP_RANDN"]: Interpreter.randn, K["IMAGEN_OP_LINCOMB"]: Interpreter.lincomb, K["IMAGEN_OP_LOWRES_PREP"]: Interpreter.lowres_prep,
     K["IMAGEN_OP_TEMPORAL_PEG"]: Interpreter.temporal_peg, K["IMAGEN_OP_TEMPORAL_ATTENTION"]: Interpreter.temporal_attention,
     K["IMAGEN_OP_ACT_PREP"]: Interpreter.act_prep,
     K["IMAGEN_OP_STEP_SLICE"]: Interpreter.step_slice,
     K["IMAGEN_OP_ROWCHAIN"]: Interpreter.rowchain,
     K["IMAGEN_OP_LINEAR_F32"]: Interpreter.linear_f32,
+    K["IMAGEN_OP_LINCTX"]: Interpreter.linctx, K["IMAGEN_OP_LINEAR_XATTN"]: Interpreter.linear_xattn,
 }
+
+
+# ------------------------------------------------------------------------------------------------ the driver of a dry engine
+
+def register_engine(it, eng):
+    """Register every io buffer of an engine (UnetEngine / UnetEngine3D; the ones it does not have are None, which Mem.register ignores)."""
+    for name in ("x_in", "lowres_in", "cond_in", "self_cond_in", "times", "lowres_times", "out", "out_full", "keep_u8", "src_idx", "arange_idx"):
+        it.mem.register(getattr(eng, name, None))
+    for act in (eng.t_const, eng.cimg):
+        if act is not None:
+            it.mem.register(act.t)
+
+
+def run_engine(eng, x, t, text_embeds=None, text_mask=None, *, lowres_cond_img=None, lowres_noise_times=None, it=None, **cond):
+    """One forward of a dry engine on the images x (B, C, S, S) or clips x (B, C, F, S, S) at times t: a guided pair (cond rows, then null
+    rows) where the engine has 2 B rows, a single forward where it has B.  `cond` goes to set_conditioning (negative_text_embeds, ...).  The
+    static plan(s) of that call, the inputs (frame-major for a clip), the step plan, on a fresh Interpreter or on `it`.  Returns
+    (out_cond, out_null, eng, it) in the layout of x, fp32; out_null is empty without null rows."""
+    B, R = eng.src_batch, eng.R
+    keep = torch.ones(R, dtype=torch.bool)
+    keep[B:] = False
+    eng.set_conditioning(text_embeds=text_embeds, text_mask=text_mask, keep=keep, lowres_noise_times=lowres_noise_times, **cond)
+    it = it or Interpreter()
+    register_engine(it, eng)
+    for plan in eng._last_static:
+        it.run(plan)
+    fm = (lambda v: v.permute(0, 2, 1, 3, 4)) if x.ndim == 5 else (lambda v: v)          # (b, c, f, h, w) <-> the engine's (b, f, c, h, w)
+    eng.x_in.copy_(fm(x))
+    if eng.lowres:
+        eng.lowres_in.copy_(fm(lowres_cond_img))
+    eng.times.copy_(t.repeat(R // B))
+    it.run(eng.step_plan)
+    out = fm(eng.out).float().clone()
+    return out[:B], out[B:], eng, it

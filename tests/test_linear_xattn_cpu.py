@@ -2,8 +2,8 @@
 
   * surface: the constructor rules of ip.py:1306, 1341, 1370, 1395, 1409 (the flag conditions the level's FIRST block, on the down and the up
     side, also where layer_cross_attns is False), strict state_dict loading, configs; `use_linear_attn` and both flags on Unet3D still raise;
-  * the fp32 restatement of LinearCrossAttention.forward (tests/plan_interp_linxattn.py) against the recorded output of the reference's module;
-  * the planner: the dry-run launch lists of the fixture unets executed by the interpreter extended with the two new op contracts, against the
+  * the fp32 restatement of LinearCrossAttention.forward (tests/fixtures_linxattn.py) against the recorded output of the reference's module;
+  * the planner: the dry-run launch lists of the fixture unets executed by the plan interpreter (tests/plan_interp.py), against the
     recorded forwards of the live reference (tests/golden/linxattn_unet*.pt) on both branches, 1e-2 as tests/test_plan_interp.py; the flag-off
     twin's launch list equals the one recorded from the commit before this feature (tests/golden/linxattn_twin_launch_list_abi13.json);
   * the two kernels on the functional emulation (tests/test_linear_xattn_gpu.py's kernel tests in a child pytest);
@@ -21,8 +21,9 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-import plan_interp_linxattn as lx  # noqa: E402
-from plan_interp_linxattn import nerr  # noqa: E402
+import fixtures_linxattn as lx  # noqa: E402
+from fixtures_linxattn import nerr  # noqa: E402
+from plan_interp import Interpreter, register_engine, run_engine  # noqa: E402
 from test_sample_cpu_replay import cpu_backend  # noqa: E402,F401  (the fixture that sends Plan.run / Graph to the interpreter)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -43,14 +44,12 @@ def reference_weights():
         ops.REFERENCE_WEIGHTS.clear()
 
 
-@pytest.fixture()
-def lx_backend(cpu_backend, monkeypatch):
-    """cpu_backend with Plan.run sent to the interpreter that knows LINCTX and LINEAR_XATTN."""
-    from imagen_pytorch_amd import ops
+def run_unet(u, f):
+    """One guided pair of `u` on the forward record f: (out_cond, out_null, engine)."""
+    from imagen_pytorch_amd.engine import UnetEngine
 
-    it = lx.InterpreterLX()
-    monkeypatch.setattr(ops.Plan, "run", lambda self, stream=None: it.run(self))
-    return it
+    B, S = f["x"].shape[0], f["x"].shape[-1]
+    return run_engine(UnetEngine(u, 2 * B, B, S, "cpu", dry=True), f["x"], f["time"], f["text_embeds"], f["text_mask"])[:3]
 
 
 # ------------------------------------------------------------------------------------------------ 1. surface
@@ -137,7 +136,7 @@ def test_linear_unet_plan_on_cpu_matches_reference_fixture(name, reference_weigh
 
     rec, _ = lx.unet_record(name)
     f = rec["forward"]
-    oc, on, eng = lx.run_unet(lx.unet(name), f)
+    oc, on, eng = run_unet(lx.unet(name), f)
     e_c, e_n = nerr(oc, f["out_cond"]), nerr(on, f["out_null"])
     print(f"planner + interpreter [{name}] vs the reference: cond {e_c:.3e} null {e_n:.3e}")
     assert e_c < 1e-2 and e_n < 1e-2, (e_c, e_n)
@@ -164,7 +163,7 @@ def test_flag_off_launch_list_is_the_parent_commits(reference_weights):
 
     rec, _ = lx.unet_record("twin")
     f = rec["forward"]
-    oc, on, eng = lx.run_unet(lx.unet("twin"), f)
+    oc, on, eng = run_unet(lx.unet("twin"), f)
     want = json.load(open(os.path.join(lx.GOLDEN, "linxattn_twin_launch_list_abi13.json")))
     got = {"static": [[int(k), l] for k, _, l in eng._static_plans[f["text_embeds"].shape[1]][0].ops], "step": [[int(k), l] for k, _, l in eng.step_plan.ops]}
     assert got == want
@@ -180,7 +179,7 @@ def test_time_table_plan_equals_per_step_chain_with_linear_sites(reference_weigh
     plan gives the bits of the per-step chain."""
     rec, _ = lx.unet_record("lin64")
     f = rec["forward"]
-    oc, on, eng = lx.run_unet(lx.unet("lin64"), f)
+    oc, on, eng = run_unet(lx.unet("lin64"), f)
     B = f["x"].shape[0]
     coef = torch.zeros(3, 8)
     coef[:, 6] = torch.tensor([0.3, float(f["time"][0]), -0.8])
@@ -189,8 +188,9 @@ def test_time_table_plan_equals_per_step_chain_with_linear_sites(reference_weigh
     assert fast is not None
     labels = [l for _, _, l in fast.ops]
     assert labels.index("time_table_rows") < labels.index("ctx.dyn.linear_rows") < labels.index("linctx")
-    it = lx.InterpreterLX()
-    for buf in (eng.x_in, eng.times, eng.lowres_times, eng.out, eng.keep_u8, eng.src_idx, eng.arange_idx, eng.t_const.t, coef, step):
+    it = Interpreter()
+    register_engine(it, eng)
+    for buf in (coef, step):
         it.mem.register(buf)
     it.run(eng._tt_plan)
     eng.times.copy_(f["time"][:1].repeat(2 * B))        # both images at the time of table row 1
@@ -220,7 +220,7 @@ def test_emulated_kernels():
 # ------------------------------------------------------------------------------------------------ 5. drivers
 
 @pytest.mark.parametrize("kind,bar", [("ddpm", 2e-2), ("edm", 3e-2)])
-def test_sample_driver_replay(lx_backend, kind, bar):
+def test_sample_driver_replay(cpu_backend, kind, bar):
     """Imagen.sample / ElucidatedImagen.sample over the lin64 unet through the real driver (time table, graph objects) and eager, against
     the recorded runs of the live reference with the same draws."""
     g = lx.sample_fixture()

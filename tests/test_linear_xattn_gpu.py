@@ -25,8 +25,9 @@ from conftest import gpu_device, record_parity
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-import plan_interp_linxattn as lx  # noqa: E402
-from plan_interp_linxattn import nerr  # noqa: E402
+import fixtures_linxattn as lx  # noqa: E402
+from fixtures_linxattn import nerr  # noqa: E402
+from plan_interp import linctx_contract, linear_xattn_contract  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -83,7 +84,7 @@ def _launch_xattn(q, M, heads, D):
 def test_linear_xattn_kernel_vs_fp64(xattn_inputs, heads, D, N):
     q, M = xattn_inputs[(heads, D, N)]
     o = _launch_xattn(q, M, heads, D)
-    ref = lx.linear_xattn_fp64(q, M, heads, D)
+    ref = linear_xattn_contract(q, M, heads, D, dtype=torch.float64)
     e = nerr64(o, ref)
     per_image = [nerr64(o[r], ref[r]) for r in range(3)]
     print(f"LINEAR_XATTN heads {heads} x {D}, N {N}: {e:.2e} (per image {['%.2e' % v for v in per_image]})")
@@ -101,7 +102,7 @@ def test_linear_xattn_kernel_saturated_softmax():
     q[1, 1] = -60.0
     M = torch.randn(3, heads, D, D, generator=g)
     o = _launch_xattn(q, M, heads, D)
-    e = nerr64(o, lx.linear_xattn_fp64(q, M, heads, D))
+    e = nerr64(o, linear_xattn_contract(q, M, heads, D, dtype=torch.float64))
     print(f"LINEAR_XATTN saturated softmax: {e:.2e}")
     assert torch.isfinite(o).all() and e <= XATTN_BAR, e
 
@@ -147,7 +148,7 @@ def test_linctx_kernel_vs_fp64(J):
     _run(plan)
     worst = 0.0
     for heads, D, kv, M, Mv in cases:
-        ref = lx.linctx_fp64(kv, heads, D)
+        ref = linctx_contract(kv, heads, D, dtype=torch.float64)
         got = Mv.cpu()
         e = nerr64(got, ref)
         uniform = nerr64(got[:, 0, 5, :], kv[..., heads * D:heads * D + D].double().mean(dim=1))

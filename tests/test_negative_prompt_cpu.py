@@ -35,21 +35,12 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-import plan_interp_negprompt as npf  # noqa: E402
-from plan_interp_negprompt import nerr  # noqa: E402
+import fixtures_negprompt as npf  # noqa: E402
+from fixtures_negprompt import nerr  # noqa: E402
+from plan_interp import run_engine  # noqa: E402
 from test_sample_cpu_replay import cpu_backend  # noqa: E402,F401  (the fixture that sends Plan.run / Graph to the interpreter)
 
 BARS = {"ddpm": 2e-2, "edm": 3e-2, "video": 2e-2}
-
-
-@pytest.fixture()
-def np_backend(cpu_backend, monkeypatch):
-    """cpu_backend with Plan.run sent to the interpreter that states every op of the current ABI."""
-    from imagen_pytorch_amd import ops
-
-    it = npf.lx.InterpreterLX()
-    monkeypatch.setattr(ops.Plan, "run", lambda self, stream=None: it.run(self))
-    return it
 
 
 @pytest.fixture()
@@ -289,7 +280,7 @@ def test_merged_requests_with_and_without_a_negative_prompt(cpu_backend, monkeyp
     assert eng.keep_u8.tolist() == [1] * 6 and eng.src_idx.tolist() == [0, 1, 2, 3, 4, 5]
 
 
-def test_pipelined_batches_take_negative_prompts(np_backend):
+def test_pipelined_batches_take_negative_prompts(cpu_backend):
     """sample_pipelined: per batch or common, each batch bit-identical to its own sample() call (one stage step each, on the interpreter)."""
     g = npf.runs_fixture()
     run = g["runs"]["ddpm"]
@@ -305,7 +296,7 @@ def test_pipelined_batches_take_negative_prompts(np_backend):
 
 
 @pytest.mark.parametrize("scales", [(3., 1.), (1., 3.)])
-def test_pipelined_cascade_with_an_unguided_stage(np_backend, scales):
+def test_pipelined_cascade_with_an_unguided_stage(cpu_backend, scales):
     """A cascade in which ONE stage runs at cond_scale 1 takes a negative prompt (that stage has no null rows): sample_pipelined, whose
     workers run one stage per sample() call, is bit-identical to sample() there too, and encodes negative_texts once per batch."""
     g = npf.runs_fixture()
@@ -382,6 +373,15 @@ def test_sample_sharded_slices_the_negative_prompt(monkeypatch):
 
 # ------------------------------------------------------------------------------------------------ 4. planner
 
+def run_pair(u, f, **neg):
+    """One guided pair (cond rows, then null rows) of `u` on the inputs f, the null rows on the learned null conditioning or, with `neg`
+    (negative_text_embeds, negative_text_mask), on that prompt: (out_cond, out_null, engine)."""
+    from imagen_pytorch_amd.engine import UnetEngine
+
+    B, S = f["x"].shape[0], f["x"].shape[-1]
+    return run_engine(UnetEngine(u, 2 * B, B, S, "cpu", dry=True), f["x"], f["time"], f["text_embeds"], f["text_mask"], **neg)[:3]
+
+
 @pytest.mark.parametrize("tag", ["a", "b"])
 def test_negative_prompt_plan_on_cpu_matches_reference_forwards(tag):
     from imagen_pytorch_amd import ops
@@ -392,13 +392,13 @@ def test_negative_prompt_plan_on_cpu_matches_reference_forwards(tag):
         c = f["cases"][tag]
         inp = dict(x=f["x"], time=f["time"], text_embeds=c["text_embeds"], text_mask=c["text_mask"])
         u = npf.base_unet()
-        oc, on, _ = npf.run_pair(u, inp)
+        oc, on, _ = run_pair(u, inp)
         o_c, o_n = nerr(oc, c["out_cond"]), nerr(on, c["out_null"])
         guided = nerr(on + (oc - on) * f["cond_scale"], c["out_cfg"])
         bar = 1.5 * max(o_c, o_n)
-        pc, pn, eng = npf.run_pair(u, inp, neg=c["negative_text_embeds"], neg_mask=c["negative_text_mask"])
+        pc, pn, eng = run_pair(u, inp, negative_text_embeds=c["negative_text_embeds"], negative_text_mask=c["negative_text_mask"])
         e_c, e_n = nerr(pc, c["out_cond"]), nerr(pn, c["out_neg"])
-        qc, qn, _ = npf.run_pair(u, inp, neg=c["negative_text_embeds"][:1], neg_mask=c["negative_text_mask"][:1])
+        qc, qn, _ = run_pair(u, inp, negative_text_embeds=c["negative_text_embeds"][:1], negative_text_mask=c["negative_text_mask"][:1])
         e1_c, e1_n = nerr(qc, c["out_cond"]), nerr(qn, c["out_neg_b1"])
         far = min(nerr(pn, c["out_null"]), nerr(qn, c["out_null"]))
         print(f"negative prompt forward ({tag}): ordinary pair cond {o_c:.3e} null {o_n:.3e} (guided {guided:.3e}), bar {bar:.3e}; with a batch-2 negative "
@@ -413,7 +413,7 @@ def test_negative_prompt_plan_on_cpu_matches_reference_forwards(tag):
         ops.REFERENCE_WEIGHTS.clear()
 
 
-def test_unet_guided_forward_and_engine_cache(np_backend):
+def test_unet_guided_forward_and_engine_cache(cpu_backend):
     """Unet.forward_with_cond_scale with the keywords: the combination of the two recorded forwards; the unet keeps ONE engine for the
     guided shape, with or without a negative prompt, and the ordinary call after it is the ordinary call before it, bit for bit."""
     f = npf.forward_fixture()
@@ -448,7 +448,7 @@ def _replay(kind, model, g, extra):
 
 
 @pytest.mark.parametrize("kind", ["ddpm", "edm"])
-def test_image_sample_driver_with_negative_prompt(np_backend, kind):
+def test_image_sample_driver_with_negative_prompt(cpu_backend, kind):
     """(c) Imagen.sample / (d) ElucidatedImagen.sample, two stages, through the real driver (time table, graph objects) and eager."""
     g = npf.runs_fixture()
     model = npf.image_model(kind)
@@ -471,7 +471,7 @@ def test_image_sample_driver_with_negative_prompt(np_backend, kind):
     assert len(model._stages) == 2, "one stage (engine, graphs) per (rows, size), with or without a negative prompt"
 
 
-def test_video_sample_driver_with_negative_prompt(np_backend):
+def test_video_sample_driver_with_negative_prompt(cpu_backend):
     """(e) a video DDPM run of 4 frames, one negative prompt per sample, longer than the prompts."""
     g = npf.runs_fixture()
     model = npf.video_model()

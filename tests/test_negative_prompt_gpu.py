@@ -29,8 +29,8 @@ from conftest import gpu_device, record_parity
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-import plan_interp_negprompt as npf  # noqa: E402
-from plan_interp_negprompt import nerr  # noqa: E402
+import fixtures_negprompt as npf  # noqa: E402
+from fixtures_negprompt import nerr  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 BARS = {"ddpm": 2e-2, "edm": 3e-2, "video": 2e-2}

@@ -25,36 +25,35 @@ def nerr(a, b):
     return float((a.float() - b.float()).norm() / b.float().norm())
 
 
+def test_interpreter_states_every_op_kind_of_the_abi():
+    """One contract per op kind of include/imagen_hip.h (_abi.OP_STRUCT mirrors its enum): an op kind added to the header without a
+    contract fails here, not deep inside a replay."""
+    from imagen_pytorch_amd import _abi
+    from plan_interp import Interpreter
+
+    names = {v: k for k, v in _abi.ENUMS.items() if k.startswith("IMAGEN_OP_")}
+    missing = sorted(names.get(k, k) for k in set(_abi.OP_STRUCT) - set(Interpreter.DISPATCH))
+    extra = sorted(names.get(k, k) for k in set(Interpreter.DISPATCH) - set(_abi.OP_STRUCT))
+    assert set(Interpreter.DISPATCH) == set(_abi.OP_STRUCT), (missing, extra)
+
+
 @pytest.mark.parametrize("name", ["unet_tiny_base.pt", "unet_tiny_sr.pt"])
 @pytest.mark.parametrize("cfg_rows", [False, True])
 def test_unet_plan_on_cpu_matches_reference_fixture(name, cfg_rows, reference_weights):
     from imagen_pytorch_amd import Unet
     from imagen_pytorch_amd.engine import UnetEngine
-    from plan_interp import Interpreter
+    from plan_interp import run_engine
 
     g = torch.load(os.path.join(GOLDEN, name), weights_only=False)
     u = Unet(**g["kwargs"]).eval()
     u.load_state_dict(g["state_dict"])
     B, S = g["x"].shape[0], g["x"].shape[-1]
     rows = 2 * B if cfg_rows else B
-    eng = UnetEngine(u, rows, B, S, "cpu", dry=True)
-    keep = torch.ones(rows, dtype=torch.bool)
-    keep[B:] = False
-    eng.set_conditioning(text_embeds=g["text_embeds"], text_mask=g["text_mask"], keep=keep, lowres_noise_times=g["extra"].get("lowres_noise_times"))
-    it = Interpreter()
-    for t in (eng.x_in, eng.lowres_in, eng.times, eng.lowres_times, eng.out, eng.keep_u8, eng.src_idx, eng.arange_idx, eng.t_const.t):
-        it.mem.register(t)
-    it.run(eng._static_plans[g["text_embeds"].shape[1]][0])
-    eng.x_in.copy_(g["x"])
-    if eng.lowres:
-        eng.lowres_in.copy_(g["extra"]["lowres_cond_img"])
-    eng.times.copy_(g["time"].repeat(rows // B))
-    it.run(eng.step_plan)
-    out = eng.out
-    e_cond = nerr(out[:B], g["out_cond"])
+    out_c, out_n, eng, it = run_engine(UnetEngine(u, rows, B, S, "cpu", dry=True), g["x"], g["time"], g["text_embeds"], g["text_mask"], **g["extra"])
+    e_cond = nerr(out_c, g["out_cond"])
     assert e_cond < 1e-2, e_cond          # fp16 storage of every activation, as on the GPU (UNET_TOL of tests/test_model_gpu.py)
     if cfg_rows:
-        e_null = nerr(out[B:], g["out_null"])
+        e_null = nerr(out_n, g["out_null"])
         assert e_null < 1e-2, e_null
     assert len(it.trace) == len(eng.step_plan) + len(eng._static_plans[g["text_embeds"].shape[1]][0])
 
@@ -82,7 +81,7 @@ def test_unet3d_plan_on_cpu_matches_reference_fixture(tag, mode, reference_weigh
     restatement of their contract; they have not run on a GPU yet.)"""
     from imagen_pytorch_amd import Unet3D
     from imagen_pytorch_amd.engine3d import UnetEngine3D
-    from plan_interp import Interpreter
+    from plan_interp import run_engine
 
     g = torch.load(os.path.join(GOLDEN, "unet3d_tiny.pt"), weights_only=False)["runs"][tag]
     u = Unet3D(**g["kwargs"]).eval()
@@ -90,25 +89,12 @@ def test_unet3d_plan_on_cpu_matches_reference_fixture(tag, mode, reference_weigh
     B, _, Fr, S, _ = g["x"].shape
     rows = 2 * B if mode == "cfg" else B
     eng = UnetEngine3D(u, rows, B, Fr, S, "cpu", ignore_time=mode == "ignore_time", dry=True)
-    keep = torch.ones(rows, dtype=torch.bool)
-    keep[B:] = False
-    eng.set_conditioning(text_embeds=g["text_embeds"], text_mask=g["text_mask"], keep=keep, lowres_noise_times=g["extra"].get("lowres_noise_times"))
-    it = Interpreter()
-    for t in (eng.x_in, eng.lowres_in, eng.times, eng.lowres_times, eng.out, eng.keep_u8, eng.src_idx, eng.arange_idx, eng.t_const.t):
-        it.mem.register(t)
-    it.run(eng._static_plans[g["text_embeds"].shape[1]][0])
-    fm = lambda t: t.permute(0, 2, 1, 3, 4).contiguous()
-    eng.x_in.copy_(fm(g["x"]))
-    if eng.lowres:
-        eng.lowres_in.copy_(fm(g["extra"]["lowres_cond_img"]))
-    eng.times.copy_(g["time"].repeat(rows // B))
-    it.run(eng.step_plan)
-    out = fm(eng.out)                                     # (rows, c, f, h, w)
+    out_c, out_n, _, _ = run_engine(eng, g["x"], g["time"], g["text_embeds"], g["text_mask"], **g["extra"])      # (B, c, f, h, w) each
     ref = g["out_notime"] if mode == "ignore_time" else g["out_cond"]
-    e = nerr(out[:B], ref)
+    e = nerr(out_c, ref)
     assert e < 5e-3, e
     if mode == "cfg":
-        e_null = nerr(out[B:], g["out_null"])
+        e_null = nerr(out_n, g["out_null"])
         assert e_null < 5e-3, e_null
 
 
@@ -121,7 +107,7 @@ def test_unet3d_plan_with_prompt_frames_vs_oracle(tag, prompts, reference_weight
     from imagen_pytorch_amd import Unet3D
     from imagen_pytorch_amd.engine3d import UnetEngine3D
     from oracle import unet3d_oracle as u3
-    from plan_interp import Interpreter
+    from plan_interp import Interpreter, register_engine
 
     g = torch.load(os.path.join(GOLDEN, "unet3d_tiny.pt"), weights_only=False)["runs"][tag]
     u = Unet3D(**g["kwargs"]).eval()
@@ -138,8 +124,7 @@ def test_unet3d_plan_with_prompt_frames_vs_oracle(tag, prompts, reference_weight
     eng.set_conditioning(text_embeds=g["text_embeds"], text_mask=g["text_mask"], keep=keep, lowres_noise_times=g["extra"].get("lowres_noise_times"))
     eng.set_cond_video_frames(pre, post)
     it = Interpreter()
-    for t in (eng.x_in, eng.lowres_in, eng.times, eng.lowres_times, eng.out, eng.out_full, eng.keep_u8, eng.src_idx, eng.arange_idx, eng.t_const.t):
-        it.mem.register(t)
+    register_engine(it, eng)
     it.run(eng._static_plans[g["text_embeds"].shape[1]][0])
     fm = lambda t: t.permute(0, 2, 1, 3, 4).contiguous()
     eng.x_in.copy_(fm(g["x"]))
@@ -163,7 +148,7 @@ def test_unet3d_plan_with_cond_images_vs_oracle(tag, reference_weights):
     from imagen_pytorch_amd import Unet3D
     from imagen_pytorch_amd.engine3d import UnetEngine3D
     from oracle import unet3d_oracle as u3
-    from plan_interp import Interpreter
+    from plan_interp import Interpreter, register_engine
 
     g = torch.load(os.path.join(GOLDEN, "unet3d_tiny.pt"), weights_only=False)["runs"][tag]
     kw = {**g["kwargs"], "cond_images_channels": 5}
@@ -187,8 +172,7 @@ def test_unet3d_plan_with_cond_images_vs_oracle(tag, reference_weights):
         eng.set_cond_video_frames(pre, None)
     eng.set_cond_images(ci)
     it = Interpreter()
-    for t in (eng.x_in, eng.lowres_in, eng.times, eng.lowres_times, eng.out, eng.out_full, eng.keep_u8, eng.src_idx, eng.arange_idx, eng.t_const.t):
-        it.mem.register(t)
+    register_engine(it, eng)
     it.run(eng._static_plans[g["text_embeds"].shape[1]][0])
     fm = lambda t: t.permute(0, 2, 1, 3, 4).contiguous()
     eng.x_in.copy_(fm(g["x"]))
@@ -215,7 +199,7 @@ def test_unet3d_plan_readme_structure_vs_oracle(reference_weights):
     from imagen_pytorch_amd.engine3d import UnetEngine3D
     from oracle import unet3d_oracle as u3
     from oracle.make_golden import derandomise_unet3d
-    from plan_interp import Interpreter
+    from plan_interp import run_engine
 
     kw = dict(dim=16, dim_mults=(1, 2, 4, 8), temporal_strides=(1, 1, 2, 2), layer_attns=(False, False, False, True), text_embed_dim=32,
               cond_dim=32, max_text_len=16, attn_pool_num_latents=8, attn_heads=2)
@@ -225,23 +209,13 @@ def test_unet3d_plan_readme_structure_vs_oracle(reference_weights):
     B, Fr, S = 1, 8, 16
     x, t = torch.randn(B, 3, Fr, S, S), torch.tensor([0.3])
     te = torch.randn(B, 9, 32)
-    eng = UnetEngine3D(u, 2 * B, B, Fr, S, "cpu", dry=True)
-    keep = torch.tensor([True, False])
-    eng.set_conditioning(text_embeds=te, text_mask=None, keep=keep, lowres_noise_times=None)
-    it = Interpreter()
-    for buf in (eng.x_in, eng.times, eng.lowres_times, eng.out, eng.keep_u8, eng.src_idx, eng.arange_idx, eng.t_const.t):
-        it.mem.register(buf)
-    it.run(eng._static_plans[9][0])
-    eng.x_in.copy_(x.permute(0, 2, 1, 3, 4))
-    eng.times.copy_(t.repeat(2))
-    it.run(eng.step_plan)
-    out = eng.out.permute(0, 2, 1, 3, 4)
+    out_c, out_n, eng, _ = run_engine(UnetEngine3D(u, 2 * B, B, Fr, S, "cpu", dry=True), x, t, te)
     sd = u.state_dict()
     with torch.no_grad():
         ref_c = u3.unet3d_forward(sd, kw, x, t, text_embeds=te)
         ref_n = u3.unet3d_forward(sd, kw, x, t, text_embeds=te, cond_drop_prob=1.0)
     assert ref_c.abs().mean() > 0.05
-    e_c, e_n = nerr(out[:B], ref_c), nerr(out[B:], ref_n)
+    e_c, e_n = nerr(out_c, ref_c), nerr(out_n, ref_n)
     assert e_c < 5e-3 and e_n < 5e-3, (e_c, e_n)
     # the output stage reads its input twice against split-precision weights (engine3d.SPLIT_OUTPUT_STAGE): final_conv and block1 of final_res_block
     split = {label for _, p, label in eng.step_plan.ops if label in ("final_conv", "final_res_block.block1") and p.x2 == p.x1 and p.C2 == p.C1 > 0}
@@ -256,7 +230,7 @@ def test_split_output_stage_does_not_worsen_a_single_video_forward(reference_wei
     from imagen_pytorch_amd import Unet3D, engine3d
     from imagen_pytorch_amd.engine3d import UnetEngine3D
     from oracle import unet3d_oracle as u3
-    from plan_interp import Interpreter
+    from plan_interp import run_engine
 
     g = torch.load(os.path.join(GOLDEN, "sample_tiny_video.pt"), weights_only=False)
     spec = g["unets"][0]
@@ -272,20 +246,10 @@ def test_split_output_stage_does_not_worsen_a_single_video_forward(reference_wei
         monkeypatch.setattr(engine3d, "SPLIT_OUTPUT_STAGE", split)
         u = Unet3D(**kw).eval()
         u.load_state_dict(sd)
-        eng = UnetEngine3D(u, 2 * B, B, Fr, S, "cpu", dry=True)
-        keep = torch.tensor([True] * B + [False] * B)
-        eng.set_conditioning(text_embeds=te, text_mask=None, keep=keep, lowres_noise_times=None)
-        it = Interpreter()
-        for buf in (eng.x_in, eng.times, eng.lowres_times, eng.out, eng.keep_u8, eng.src_idx, eng.arange_idx, eng.t_const.t):
-            it.mem.register(buf)
-        it.run(eng._static_plans[te.shape[1]][0])
-        eng.x_in.copy_(x.permute(0, 2, 1, 3, 4))
-        eng.times.copy_(t.repeat(2))
-        it.run(eng.step_plan)
-        out = eng.out.permute(0, 2, 1, 3, 4)
+        out_c, out_n, eng, _ = run_engine(UnetEngine3D(u, 2 * B, B, Fr, S, "cpu", dry=True), x, t, te)
         n_split = sum(1 for _, p, label in eng.step_plan.ops if label in ("final_conv", "final_res_block.block1") and p.x2 == p.x1 and p.C2 == p.C1 > 0)
         assert n_split == (2 if split else 0), (split, n_split)
-        errs[split] = (nerr(out[:B], ref_c), nerr(out[B:], ref_n))
+        errs[split] = (nerr(out_c, ref_c), nerr(out_n, ref_n))
     assert max(errs[1]) < 5e-3, errs
     assert errs[1][0] <= errs[0][0] * 1.02 and errs[1][1] <= errs[0][1] * 1.02, errs
 
@@ -296,26 +260,18 @@ def test_unet_plan_without_text_mask(reference_weights):
     from imagen_pytorch_amd import Unet
     from imagen_pytorch_amd.engine import UnetEngine
     from oracle import unet_oracle as uo
-    from plan_interp import Interpreter
+    from plan_interp import run_engine
 
     g = torch.load(os.path.join(GOLDEN, "unet_tiny_base.pt"), weights_only=False)
     u = Unet(**g["kwargs"]).eval()
     u.load_state_dict(g["state_dict"])
     B, S = g["x"].shape[0], g["x"].shape[-1]
     assert g["text_embeds"].shape[1] < g["kwargs"]["max_text_len"]
-    eng = UnetEngine(u, B, B, S, "cpu", dry=True)
-    eng.set_conditioning(text_embeds=g["text_embeds"], text_mask=None, keep=torch.ones(B, dtype=torch.bool), lowres_noise_times=None)
-    it = Interpreter()
-    for t in (eng.x_in, eng.times, eng.lowres_times, eng.out, eng.keep_u8, eng.src_idx, eng.arange_idx, eng.t_const.t):
-        it.mem.register(t)
-    it.run(eng._static_plans[g["text_embeds"].shape[1]][0])
-    eng.x_in.copy_(g["x"])
-    eng.times.copy_(g["time"])
-    it.run(eng.step_plan)
+    out, _, _, _ = run_engine(UnetEngine(u, B, B, S, "cpu", dry=True), g["x"], g["time"], g["text_embeds"], None)
     with torch.no_grad():
         ref = uo.unet_forward(g["state_dict"], g["kwargs"], g["x"], g["time"], text_embeds=g["text_embeds"], text_mask=None)
-    assert nerr(eng.out, ref) < 5e-3
-    assert nerr(eng.out, g["out_cond"]) > 2e-2     # the masked run of the fixture is a different function
+    assert nerr(out, ref) < 5e-3
+    assert nerr(out, g["out_cond"]) > 2e-2     # the masked run of the fixture is a different function
 
 
 @pytest.mark.parametrize("name", list(__import__("unet_config_sweep").SWEEP))
@@ -325,7 +281,7 @@ def test_unet_plan_config_sweep(name, reference_weights):
     from imagen_pytorch_amd import Unet
     from imagen_pytorch_amd.engine import UnetEngine
     from oracle import unet_oracle as uo
-    from plan_interp import Interpreter
+    from plan_interp import Interpreter, register_engine
     from unet_config_sweep import SWEEP, cond_images_for, self_cond_for
 
     kw = SWEEP[name]
@@ -344,13 +300,9 @@ def test_unet_plan_config_sweep(name, reference_weights):
     keep[B:] = False
     eng.set_conditioning(text_embeds=te, text_mask=None, keep=keep, lowres_noise_times=extra.get("lowres_noise_times"))
     it = Interpreter()
-    for buf in (eng.x_in, eng.lowres_in, eng.times, eng.lowres_times, eng.out, eng.keep_u8, eng.src_idx, eng.arange_idx, eng.t_const.t):
-        it.mem.register(buf)
+    register_engine(it, eng)
     it.run(eng._static_plans[te.shape[1] if with_text else 0][0])
     cond_images, self_cond = cond_images_for(kw, B), self_cond_for(kw, B)
-    for buf in (eng.cond_in, eng.self_cond_in, eng.cimg.t if eng.cimg is not None else None):
-        if buf is not None:
-            it.mem.register(buf)
     if cond_images is not None:
         eng.set_cond_images(cond_images)
         if eng._cond_pack is not None:       # (with self-conditioning the step plan packs both)
@@ -467,7 +419,7 @@ def test_time_table_plan_equals_per_step_chain(name, reference_weights):
     plan exactly what the per-step conditioning chain computes (same op contracts on more rows), for several rows of a coefficient table."""
     from imagen_pytorch_amd import Unet
     from imagen_pytorch_amd.engine import UnetEngine
-    from plan_interp import Interpreter
+    from plan_interp import Interpreter, register_engine
     from unet_config_sweep import SWEEP, cond_images_for, self_cond_for
 
     kw = SWEEP[name]
@@ -485,9 +437,7 @@ def test_time_table_plan_equals_per_step_chain(name, reference_weights):
     keep[B:] = False
     eng.set_conditioning(text_embeds=te, text_mask=None, keep=keep, lowres_noise_times=lowres.get("lowres_noise_times"))
     it = Interpreter()
-    for buf in (eng.x_in, eng.lowres_in, eng.times, eng.lowres_times, eng.out, eng.keep_u8, eng.src_idx, eng.arange_idx, eng.t_const.t, eng.self_cond_in):
-        if buf is not None:
-            it.mem.register(buf)
+    register_engine(it, eng)
     it.run(eng._static_plans[te.shape[1] if with_text else 0][0])
     if eng.self_cond_in is not None:
         eng.set_self_cond(self_cond_for(kw, B))
@@ -591,7 +541,7 @@ def test_sampler_stage_plan_on_cpu(run, reference_weights, monkeypatch):
     import torch.nn.functional as F
 
     from imagen_pytorch_amd import Imagen, Unet
-    from plan_interp import Interpreter
+    from plan_interp import Interpreter, register_engine
 
     _dry_engines(monkeypatch)
     if run == "plain":
@@ -613,8 +563,7 @@ def test_sampler_stage_plan_on_cpu(run, reference_weights, monkeypatch):
     te = g["text_embeds"]
     eng.set_conditioning(text_embeds=te, text_mask=torch.any(te != 0., dim=-1), keep=keep, lowres_noise_times=None)
     it = Interpreter()
-    for buf in (eng.x_in, eng.times, eng.lowres_times, eng.out, eng.keep_u8, eng.src_idx, eng.arange_idx, eng.t_const.t):
-        it.mem.register(buf)
+    register_engine(it, eng)
     it.run(eng._static_plans[te.shape[1]][0])
     if eng._tt_plan is not None:               # the timestep-only conditioning of all steps in one batched pass (engine.enable_time_table)
         assert run != "inpaint" and any(l == "time_table_rows" for _, _, l in st['plan'].ops)
@@ -643,7 +592,7 @@ def test_video_sampler_stage_plans_on_cpu(tds, reference_weights, monkeypatch):
     import torch.nn.functional as F
 
     from imagen_pytorch_amd import Imagen, Unet3D, engine3d
-    from plan_interp import Interpreter
+    from plan_interp import Interpreter, register_engine
 
     monkeypatch.setattr(engine3d, "UnetEngine3D", functools.partial(engine3d.UnetEngine3D, dry=True))
     g = torch.load(os.path.join(GOLDEN, "sample_tiny_video.pt"), weights_only=False)
@@ -665,8 +614,7 @@ def test_video_sampler_stage_plans_on_cpu(tds, reference_weights, monkeypatch):
         assert st['video'] and tuple(eng.x_in.shape) == (B, Fr, 3, S, S)
         lowres_logsnr = None
         it = Interpreter()
-        for buf in (eng.x_in, eng.lowres_in, eng.times, eng.lowres_times, eng.out, eng.keep_u8, eng.src_idx, eng.arange_idx, eng.t_const.t):
-            it.mem.register(buf)
+        register_engine(it, eng)
         if idx > 0:   # what Imagen._sample does with LOWRES_PREP (ip.py:2443-2449): nearest resize per frame, normalise, augment at level 0.2
             a, s, lsnr = imagen.lowres_noise_schedule.q_sample_coefficients(imagen.lowres_sample_noise_level)
             if prev.shape[1] != Fr:                         # the frame-axis part of resize_video_to, as Imagen._sample does it
@@ -692,7 +640,7 @@ def test_elucidated_stage_plan_on_cpu(reference_weights, monkeypatch):
     """ElucidatedImagen stage 1 (Karras schedule, churn, preconditioning through CFG_X0, dynamic threshold, Heun correction as LINCOMB
     ops over device tables): the two plans of ElucidatedImagen._stage replayed on the CPU vs the reference's recorded run."""
     from imagen_pytorch_amd import ElucidatedImagen, Unet
-    from plan_interp import Interpreter
+    from plan_interp import Interpreter, register_engine
 
     _dry_engines(monkeypatch)
     g = torch.load(os.path.join(GOLDEN, "sample_tiny_elucidated.pt"), weights_only=False)
@@ -711,7 +659,8 @@ def test_elucidated_stage_plan_on_cpu(reference_weights, monkeypatch):
     keep[B:] = False
     eng.set_conditioning(text_embeds=te, text_mask=torch.any(te != 0., dim=-1), keep=keep, lowres_noise_times=None)
     it = Interpreter()
-    for buf in (eng.x_in, eng.times, eng.lowres_times, eng.out, eng.keep_u8, eng.src_idx, eng.arange_idx, eng.t_const.t, x, st['final']):
+    register_engine(it, eng)
+    for buf in (x, st['final']):
         it.mem.register(buf)
     it.run(eng._static_plans[te.shape[1]][0])
     assert eng._tt_plan is not None and sum(l == "time_table_rows" for _, _, l in st['plan'].ops) == 2   # both evaluations of a Heun step

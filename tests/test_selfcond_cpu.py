@@ -3,8 +3,8 @@
   * an fp32 restatement of the reference's Karras loop WITH self-conditioning (el.py:451, 496, 518, 538), written out here over
     oracle/unet_oracle.py, against the recorded run of the live reference (tests/golden/selfcond_image_runs.pt) and, where its tree is
     present, against the live reference itself with the recorded draws injected — tolerances of tests/test_oracle_golden.py's Elucidated test;
-  * the real drivers (ElucidatedImagen.sample, Imagen.sample) replayed through the plan interpreter extended for ABI 13
-    (tests/plan_interp_selfcond.py) against the recorded runs — bars of tests/test_sample_cpu_replay.py's Elucidated / video replays.
+  * the real drivers (ElucidatedImagen.sample, Imagen.sample) replayed through the plan interpreter (tests/plan_interp.py: LINCOMB with
+    its thr1_out / thr3_out) against the recorded runs — bars of tests/test_sample_cpu_replay.py's Elucidated / video replays.
     Measured here: image plain 3.3e-3 / 5.4e-3 (stage 1 / stage 2 alone), skip 1.3e-3 / 7.0e-3, inpaint 1.8e-3 / 2.9e-3; video DDPM 1.2e-3,
     video EDM 3.0e-3; Unet3D forward with a clip 6.7e-4 (cond) / 1.9e-3 (CFG), without 2.4e-3; the restatement itself sits at 1.3e-5 / 5.4e-5 /
     9.1e-5 (plain: stage 1, stage 2 alone, chained; max abs), 6.0e-6 / 3.5e-5 / 1.6e-4 (skip), 6.3e-5 / 5.6e-5 / 3.1e-4 (inpaint);
@@ -23,22 +23,12 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-import plan_interp_selfcond as sc  # noqa: E402
-from plan_interp_selfcond import nerr  # noqa: E402
+import fixtures_selfcond as sc  # noqa: E402
+from fixtures_selfcond import nerr  # noqa: E402
 from test_sample_cpu_replay import cpu_backend  # noqa: E402,F401  (the fixture that sends Plan.run / Graph to the interpreter)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLANG = "/opt/rocm/lib/llvm/bin/clang++"
-
-
-@pytest.fixture()
-def sc_backend(cpu_backend, monkeypatch):
-    """cpu_backend with Plan.run sent to an interpreter that states LINCOMB as ABI 13 does."""
-    from imagen_pytorch_amd import ops
-
-    it = sc.InterpreterSC()
-    monkeypatch.setattr(ops.Plan, "run", lambda self, stream=None: it.run(self))
-    return it
 
 
 # ------------------------------------------------------------------------------------------------ 1. restatement
@@ -163,7 +153,7 @@ def test_restated_karras_loop_matches_live_reference():
 # ------------------------------------------------------------------------------------------------ 2. driver replay
 
 @pytest.mark.parametrize("tag", ["plain", "skip", "inpaint"])
-def test_elucidated_self_cond_sample_driver(sc_backend, tag):
+def test_elucidated_self_cond_sample_driver(cpu_backend, tag):
     """ElucidatedImagen.sample over Unet(self_cond=True) stages through the real driver, graph objects and eager, against fixture (b); a
     second call on the cached stage gives the same images (self_cond_in is zeroed again).  Bar: 3e-2
     (tests/test_sample_cpu_replay.py::test_elucidated_sample_driver / test_elucidated_sample_options_driver)."""
@@ -185,7 +175,7 @@ def test_elucidated_self_cond_sample_driver(sc_backend, tag):
 
 
 @pytest.mark.parametrize("kind,bar", [("ddpm", 2e-2), ("edm", 5e-2)])
-def test_video_self_cond_sample_driver(sc_backend, kind, bar):
+def test_video_self_cond_sample_driver(cpu_backend, kind, bar):
     """Imagen.sample / ElucidatedImagen.sample over a Unet3D(self_cond=True) stage against fixture (c).  Bars: 2e-2
     (test_sample_cpu_replay.py's video DDPM replays) and 5e-2 (::test_video_elucidated_sample_driver)."""
     g, _ = sc.video_fixture()
@@ -201,7 +191,7 @@ def test_video_self_cond_sample_driver(sc_backend, kind, bar):
     assert e < bar, (kind, e)
 
 
-def test_unet3d_self_cond_forward_on_cpu(sc_backend):
+def test_unet3d_self_cond_forward_on_cpu(cpu_backend):
     """Unet3D(self_cond=True).forward through the interpreter against fixture (a), with and without a clip.  Bar of the video forwards: 1e-2
     (2e-2 under CFG), tests/test_video_gpu.py::test_unet3d_forward_vs_reference_fixture."""
     g, _ = sc.video_fixture()
@@ -253,7 +243,7 @@ def test_unet3d_self_cond_state_dict_loads_strictly():
         Unet3D(**{**spec["kwargs"], "pixel_shuffle_upsample": False})
 
 
-def test_unet3d_self_cond_refusals(sc_backend):
+def test_unet3d_self_cond_refusals(cpu_backend):
     """What Unet3D(self_cond=True) does not take raises NotImplementedError where it is asked for: a conditioning image at construction,
     prompt frames when the stage (or the engine of a bare forward) is built."""
     from imagen_pytorch_amd import Unet3D

@@ -23,8 +23,8 @@ from conftest import gpu_device, record_parity
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-import plan_interp_selfcond as sc  # noqa: E402
-from plan_interp_selfcond import nerr  # noqa: E402
+import fixtures_selfcond as sc  # noqa: E402
+from fixtures_selfcond import nerr  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 

@@ -18,8 +18,9 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-import plan_interp_longclip as lc  # noqa: E402
-from plan_interp_longclip import nerr  # noqa: E402
+import fixtures_longclip as lc  # noqa: E402
+from fixtures_longclip import nerr  # noqa: E402
+from plan_interp import run_engine  # noqa: E402
 from test_sample_cpu_replay import cpu_backend  # noqa: E402,F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -56,8 +57,11 @@ _figures = {}
 
 def _forward(name):
     if name not in _figures:
+        from imagen_pytorch_amd.engine3d import UnetEngine3D
+
         f, _, _ = lc.unet_record(name)
-        oc, on, eng = lc.run_unet3d(lc.unet(name), f["x"], f["time"], f["text_embeds"], f["text_mask"], interp=lc.InterpreterLong)
+        B, _, Fr, S, _ = f["x"].shape
+        oc, on, eng, _ = run_engine(UnetEngine3D(lc.unet(name), 2 * B, B, Fr, S, "cpu", dry=True), f["x"], f["time"], f["text_embeds"], f["text_mask"])
         _figures[name] = (nerr(oc, f["out_cond"]), nerr(on, f["out_null"]), eng)
     return _figures[name]
 
@@ -76,11 +80,7 @@ def test_long_unet3d_plan_on_cpu_matches_reference_fixture(name, reference_weigh
 
 
 @pytest.mark.parametrize("kind,bar", [("ddpm", 2e-2), ("edm", 5e-2)])
-def test_long_sample_driver_replay(cpu_backend, monkeypatch, kind, bar):
-    from imagen_pytorch_amd import ops
-
-    it = lc.InterpreterLong()
-    monkeypatch.setattr(ops.Plan, "run", lambda self, stream=None: it.run(self))
+def test_long_sample_driver_replay(cpu_backend, kind, bar):
     g = lc.sample_fixture()
     run = g[kind]
     model = lc.sample_model(kind)

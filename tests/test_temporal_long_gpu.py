@@ -1,5 +1,5 @@
 """MI355X: TEMPORAL_ATTENTION on clips of 33 .. 128 frames (ABI 15, csrc/temporal.hip temporal_attention_long_kernel) — the kernel against the
-fp64 restatement of the contract (tests/plan_interp_longclip.py) on identical fp16-rounded inputs, the launcher's bounds, and Unet3D forwards
+fp64 statement of the contract (tests/plan_interp.py) on identical fp16-rounded inputs, the launcher's bounds, and Unet3D forwards
 and both samplers at 36 frames against recorded runs of the live reference (tests/golden/longclip_*.pt, tools/make_longclip_golden.py).
 
 The kernel and launcher tests also run on the CPU emulation of the kernel library (tests/test_temporal_long_cpu.py), before hardware.
@@ -21,8 +21,9 @@ from conftest import gpu_device, record_parity
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-import plan_interp_longclip as lc  # noqa: E402
-from plan_interp_longclip import nerr  # noqa: E402
+import fixtures_longclip as lc  # noqa: E402
+from fixtures_longclip import nerr  # noqa: E402
+from plan_interp import temporal_attention_contract  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 OP_BAR = 1e-3
@@ -68,7 +69,8 @@ def _launch(dev, c, causal, qkv=None):
 
 
 def _ref(c, causal):
-    return lc.temporal_attention_fp64(c["qkv"], c["null_kv"], c["q_scale"], c["k_scale"], c["bias"], heads=c["heads"], D=c["D"], causal=causal, scale=8.0)
+    return temporal_attention_contract(c["qkv"], c["null_kv"], c["q_scale"], c["k_scale"], c["bias"], heads=c["heads"], D=c["D"], causal=causal, scale=8.0,
+                                       dtype=torch.float64)
 
 
 def _errs(got, ref):

@@ -2,7 +2,7 @@
 `ImagenConfig(video=True)` gives every unet of a config that leaves the head settings alone (ABI 12: ImagenTemporalAttentionParams.head_dim).
 
 Constructor and config surface, the state_dict / oracle against the live reference (where its tree is present), the planner's launch lists on
-the CPU plan interpreter (tests/plan_interp_hd.py) against the oracle, and the two kernels of csrc/temporal.hip at D = 32 on the CPU emulation
+the CPU plan interpreter (tests/plan_interp.py) against the oracle, and the two kernels of csrc/temporal.hip at D = 32 on the CPU emulation
 of the kernel library (the kernel-level tests of tests/test_video_headdim32_gpu.py in a child pytest)."""
 import os
 import subprocess
@@ -153,15 +153,16 @@ def test_unet3d_plan_at_head_dim_32_vs_oracle(reference_weights):
     attention site of the video planner), cond and null rows, replayed by the plan interpreter against the fp32 oracle — the bound of
     tests/test_plan_interp.py's video cases."""
     from imagen_pytorch_amd import Unet3D, _abi
+    from imagen_pytorch_amd.engine3d import UnetEngine3D
     from oracle import unet3d_oracle as u3
-    from plan_interp_hd import run_unet3d
+    from plan_interp import run_engine
 
     torch.manual_seed(3)
     u = Unet3D(**TINY_HD32).eval()
     _derandomise_unet3d(u)
     B, Fr, S = 1, 8, 16
     x, t, te = torch.randn(B, 3, Fr, S, S), torch.tensor([0.3]), torch.randn(B, 9, 32)
-    out_c, out_n, eng = run_unet3d(u, x, t, te)
+    out_c, out_n, eng, _ = run_engine(UnetEngine3D(u, 2 * B, B, Fr, S, "cpu", dry=True), x, t, te)
     sd = u.state_dict()
     with torch.no_grad():
         ref_c = u3.unet3d_forward(sd, TINY_HD32, x, t, text_embeds=te)
@@ -176,19 +177,50 @@ def test_unet3d_plan_at_head_dim_32_vs_oracle(reference_weights):
     assert hd <= {32}, hd            # every other attention site threads the head dim through as well
 
 
+def _interpreter_abi11():
+    """The interpreter with TEMPORAL_ATTENTION as the header stated it before ABI 12: 64-wide heads, no head_dim field read."""
+    import torch.nn.functional as F
+
+    from plan_interp import Interpreter, K, f16, f32
+
+    class InterpreterABI11(Interpreter):
+        def temporal_attention(self, p):
+            m = self.mem
+            Fr, P, H = p.F, p.P, p.heads
+            rows = m.strided(p.qkv, f16, (p.B, Fr, P, H * 64 + 128), (Fr * P * p.ld, P * p.ld, p.ld, 1)).float()
+            q = rows[..., :H * 64].reshape(p.B, Fr, P, H, 64).permute(0, 2, 3, 1, 4)          # b p h i d
+            k, v = rows[..., H * 64:H * 64 + 64].permute(0, 2, 1, 3), rows[..., H * 64 + 64:].permute(0, 2, 1, 3)   # b p j d
+            nkv = m.view(p.null_kv, f32)[:128].reshape(2, 64)
+            k = torch.cat((nkv[0].expand(p.B, P, 1, 64), k), dim=2)
+            v = torch.cat((nkv[1].expand(p.B, P, 1, 64), v), dim=2)
+            qh = F.normalize(q, dim=-1, eps=1e-12) * m.view(p.q_scale, f32)[:64] * p.scale
+            kh = F.normalize(k, dim=-1, eps=1e-12) * m.view(p.k_scale, f32)[:64]
+            sim = torch.einsum("bphid,bpjd->bphij", qh, kh) + m.view(p.bias, f32)[:H * Fr * (Fr + 1)].reshape(H, Fr, Fr + 1)
+            if p.causal:
+                sim = sim.masked_fill(torch.ones(Fr, Fr + 1, dtype=torch.bool).triu(2), -torch.finfo(sim.dtype).max)
+            o = torch.einsum("bphij,bpjd->bphid", sim.softmax(-1), v)                       # b p h i d
+            o = o.permute(0, 3, 1, 2, 4).reshape(p.B, Fr, P, H * 64)
+            m.strided(p.o, f16, (p.B, Fr, P, H * 64), (Fr * P * p.ld_o, P * p.ld_o, p.ld_o, 1)).copy_(o.half())
+
+    InterpreterABI11.DISPATCH = {**Interpreter.DISPATCH, K["IMAGEN_OP_TEMPORAL_ATTENTION"]: InterpreterABI11.temporal_attention}
+    return InterpreterABI11
+
+
 def test_head_dim_64_plan_is_bit_identical_under_the_restated_interpreter(reference_weights):
-    """The subclass is a strict generalisation: an existing head-dim-64 video plan (the 'base' clip of tests/golden/unet3d_tiny.pt) gives the same
-    bits through tests/plan_interp.py and tests/plan_interp_hd.py, and its TEMPORAL_ATTENTION params carry head_dim = 0 as before ABI 12."""
+    """The head-dim-generic contract is a strict generalisation: an existing head-dim-64 video plan (the 'base' clip of
+    tests/golden/unet3d_tiny.pt) gives the same bits through the 64-wide statement of before ABI 12 (kept above) and through
+    tests/plan_interp.py, and its TEMPORAL_ATTENTION params carry head_dim = 0 as before ABI 12."""
     from imagen_pytorch_amd import Unet3D, _abi
-    from plan_interp import Interpreter
-    from plan_interp_hd import InterpreterHD, run_unet3d
+    from imagen_pytorch_amd.engine3d import UnetEngine3D
+    from plan_interp import Interpreter, run_engine
 
     g = torch.load(os.path.join(GOLDEN, "unet3d_tiny.pt"), weights_only=False)["runs"]["base"]
+    B, _, Fr, S, _ = g["x"].shape
     outs = []
-    for interp in (Interpreter, InterpreterHD):
+    for interp in (_interpreter_abi11(), Interpreter):
         u = Unet3D(**g["kwargs"]).eval()
         u.load_state_dict(g["state_dict"])
-        c, n, eng = run_unet3d(u, g["x"], g["time"], g["text_embeds"], g["text_mask"], interp=interp)
+        c, n, eng, _ = run_engine(UnetEngine3D(u, 2 * B, B, Fr, S, "cpu", dry=True), g["x"], g["time"], g["text_embeds"], g["text_mask"], it=interp())
         outs.append((c, n))
         ta = [p for k, p, _ in eng.step_plan.ops if k == _abi.ENUMS["IMAGEN_OP_TEMPORAL_ATTENTION"]]
         assert ta and all(p.head_dim == 0 for p in ta)

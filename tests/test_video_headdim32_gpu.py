@@ -227,7 +227,7 @@ def c5_hd32_case(seed=0):
 def test_unet3d_forward_vs_oracle_c5_head_dim_32():
     """The C5 shape with the config-default heads — Unet3D(dim=64, dim_mults=(1, 2, 4, 8), attn_dim_head=32, attn_heads=16), one 16 x 64 x 64
     clip, seed 0, cond and null rows — against the fp32 CPU oracle at the project's 1.0e-3 bar.  Priced on the CPU plan interpreter first
-    (tests/plan_interp_hd.py, which predicts hardware to 1-2 % on cond rows): cond 9.28e-4, null 9.07e-4."""
+    (tests/plan_interp.py, which predicts hardware to 1-2 % on cond rows): cond 9.28e-4, null 9.07e-4."""
     from oracle import unet3d_oracle as u3
 
     dev = gpu_device()

@@ -29,7 +29,7 @@ import torch  # noqa: E402
 from make_selfcond_golden import edm_tags, pack_unet, round_to_half  # noqa: E402
 from oracle.make_golden import ELUCIDATED_HP, _derandomise, _record_draws  # noqa: E402
 from oracle.ref_shim import load_reference  # noqa: E402
-from plan_interp_selfcond import nerr  # noqa: E402
+from fixtures_common import nerr  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 DISCRIMINATION = 10.0

@@ -117,7 +117,7 @@ def make_models(iv):
 
 
 def make_forwards(unets):
-    from plan_interp_selfcond import nerr
+    from fixtures_common import nerr
 
     torch.manual_seed(79)
     B = 2
@@ -147,7 +147,7 @@ def make_forwards(unets):
 def make_sample(ip, el, unet):
     from make_selfcond_golden import edm_tags
     from oracle.make_golden import ELUCIDATED_HP, _record_draws
-    from plan_interp_selfcond import nerr
+    from fixtures_common import nerr
 
     torch.manual_seed(83)
     te = torch.randn(2, 9, 32)
@@ -190,7 +190,7 @@ if __name__ == "__main__":
 
     ip, iv, el = load_reference("imagen_pytorch"), load_reference("imagen_video"), load_reference("elucidated_imagen")
     if "--sample" in sys.argv:
-        import plan_interp_longclip as lc
+        import fixtures_longclip as lc
 
         _, kw, sd = lc.unet_record("long")
         u = iv.Unet3D(**kw).eval()

@@ -31,7 +31,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import torch  # noqa: E402
 
-import plan_interp_negprompt as npf  # noqa: E402
+import fixtures_negprompt as npf  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 DISCRIMINATION = 10.0
@@ -200,7 +200,7 @@ def main():
     from oracle.ref_shim import load_reference
 
     ip, iv, el = load_reference("imagen_pytorch"), load_reference("imagen_video"), load_reference("elucidated_imagen")
-    import plan_interp_linxattn as lx
+    import fixtures_linxattn as lx
 
     rec, sd = lx.unet_record("twin")
     base = ip.Unet(**rec["kwargs"]).eval()

@@ -29,7 +29,7 @@ import torch  # noqa: E402
 
 from oracle.make_golden import ELUCIDATED_HP, TINY_3D, TINY_BASE, TINY_SR, _derandomise, _record_draws, derandomise_unet3d  # noqa: E402
 from oracle.ref_shim import load_reference  # noqa: E402
-from plan_interp_selfcond import nerr, unpack_state_dict  # noqa: E402  (the fixtures' reader: written and read back by one function)
+from fixtures_common import nerr, unpack_state_dict  # noqa: E402  (the fixtures' reader: written and read back by one function)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 DISCRIMINATION = 10.0

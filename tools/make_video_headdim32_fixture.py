@@ -6,32 +6,22 @@
 
 Only tensors and constructor kwargs are stored.  The weights are rounded to fp16 BEFORE the reference runs and stored as fp16, so the fixture
 holds exactly the weights the recorded outputs were computed from at half the size; each stage's state_dict is ONE flat fp16 tensor plus the
-ordered (key, shape) index (900 small tensors cost a quarter of a megabyte in container overhead): unpack_state_dict() below restores it."""
+ordered (key, shape) index (900 small tensors cost a quarter of a megabyte in container overhead): tests/fixtures_common.py unpack_state_dict()
+restores it."""
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch  # noqa: E402
 
+from fixtures_common import unpack_state_dict  # noqa: E402
 from oracle.make_golden import TINY_3D, _record_draws, derandomise_unet3d  # noqa: E402
 from oracle.ref_shim import load_reference  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden", "sample_tiny_video_hd32.pt")
 HEADS = dict(attn_heads=2, attn_dim_head=32, cond_dim=16)   # (cond_dim 16: the fixture stays under the 1 MiB limit of a committed file)
-
-
-def unpack_state_dict(spec):
-    """{key: fp32 tensor} in state_dict order from a stage record of the fixture."""
-    sd, at = {}, 0
-    for key, shape in spec["index"]:
-        n = 1
-        for d in shape:
-            n *= d
-        sd[key] = spec["flat"][at:at + n].float().reshape(shape)
-        at += n
-    assert at == spec["flat"].numel()
-    return sd
 
 
 def main(seed=29, T=2, frames=4):

@@ -2,8 +2,8 @@
 
 A whole-denoiser distance to the oracle says THAT the HIP path and the fp32 restatement differ, a level tap says roughly WHERE; neither
 separates one kernel's internal rounding from the noise it inherits.  This tool executes a denoiser plan launch by launch twice — by the
-kernel library (MI355X, or the CPU emulation with --emul) and by the CPU plan interpreter (every op restated from its contract in
-include/imagen_hip.h: fp16 storage, fp32 arithmetic) — FROM IDENTICAL INPUTS: after each launch the interpreter-side copies of the buffers
+kernel library (MI355X, or the CPU emulation with --emul) and by the CPU plan interpreter (every op kind of include/imagen_hip.h restated
+from its contract, so it covers whatever launch a plan holds: fp16 storage, fp32 arithmetic) — FROM IDENTICAL INPUTS: after each launch the interpreter-side copies of the buffers
 that launch wrote are overwritten with the kernel's results.  Two fp32 computations of the same quantity round to the same fp16 value
 almost everywhere, so a launch whose kernel follows its contract shows ~1e-5 .. 2e-4 here; one that rounds something its contract keeps in
 fp32 shows its own error, alone, and `coherence` says whether that error is one vector repeated over the rows (a bias that survives

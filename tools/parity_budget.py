@@ -1,8 +1,9 @@
 """CPU experiment (test infrastructure): where does the whole-Unet distance to the fp32 oracle come from?
 
-Runs the Unet planner's launch list through the plan interpreter (tests/plan_interp.py: every op restated from its contract, fp16
-storage, fp32 arithmetic — the rounding points of the HIP path without its kernels) against the oracle, with switches that keep chosen
-tensors at higher precision:
+Runs the Unet planner's launch list through the plan interpreter (tests/plan_interp.py: every op kind of include/imagen_hip.h restated
+from its contract, fp16 storage, fp32 arithmetic — the rounding points of the HIP path without its kernels; so any plan the planners
+emit can be replayed, head-dim-32 temporal attention included; a linear cross-attention unet still has no oracle to be priced against)
+against the oracle, with switches that keep chosen tensors at higher precision:
 
   --exact-weights REGEX   the conv / GEMM launches whose label matches read the UNROUNDED fp32 weight (what a split-precision weight gives a
                           launch: ops.pack_weight(split=True)) — prices a planner policy before it is written.  Round 5, BASELINE C5:
@@ -10,7 +11,7 @@ tensors at higher precision:
                           launch) 0.863e-3; '^(to_time|time_mlps)' nothing.  Deltas under ~3 % are inside what another realisation of the
                           rounding noise does to the figure.
 
-    python tools/parity_budget.py [--config u1|u2|hd32|memeff|c5] [--size 64] [--seeds 0 1 2] [--exact-weights REGEX]
+    python tools/parity_budget.py [--config u1|u2|hd32|memeff|c5|c5hd32] [--size 64] [--seeds 0 1 2] [--exact-weights REGEX]
 """
 from __future__ import annotations
 
@@ -32,6 +33,7 @@ MEMEFF = dict(dim=32, cond_dim=64, dim_mults=(1, 2, 4), num_resnet_blocks=(1, 2,
               layer_cross_attns=(False, True, True), memory_efficient=True, lowres_cond=True, attn_heads=4)
 HD32 = dict(README_U1, attn_dim_head=32, attn_heads=16)
 CONFIGS = dict(u1=README_U1, u2=README_U2, memeff=MEMEFF, hd32=HD32)
+C5_HEADS = dict(c5={}, c5hd32=dict(attn_dim_head=32, attn_heads=16))      # (c5hd32: the config-default heads of Unet3DConfig)
 
 
 def nerr(a, b):
@@ -55,21 +57,9 @@ def case(kw, S, B, seed=0):
 
 def run_interp(u, x, t, te, mask, extra, S, B, interp_cls):
     from imagen_pytorch_amd.engine import UnetEngine
-    rows = 2 * B
-    eng = UnetEngine(u, rows, B, S, "cpu", dry=True)
-    keep = torch.ones(rows, dtype=torch.bool)
-    keep[B:] = False
-    eng.set_conditioning(text_embeds=te, text_mask=mask, keep=keep, lowres_noise_times=extra.get("lowres_noise_times"))
-    it = interp_cls()
-    for tt in (eng.x_in, eng.lowres_in, eng.times, eng.lowres_times, eng.out, eng.keep_u8, eng.src_idx, eng.arange_idx, eng.t_const.t):
-        it.mem.register(tt)
-    it.run(eng._static_plans[te.shape[1]][0])
-    eng.x_in.copy_(x)
-    if eng.lowres:
-        eng.lowres_in.copy_(extra["lowres_cond_img"])
-    eng.times.copy_(t.repeat(rows // B))
-    it.run(eng.step_plan)
-    return eng.out.clone(), eng
+    from plan_interp import run_engine
+    out_c, out_n, eng, _ = run_engine(UnetEngine(u, 2 * B, B, S, "cpu", dry=True), x, t, te, mask, it=interp_cls(), **extra)
+    return torch.cat((out_c, out_n)), eng
 
 
 def exact_weight_interpreter(regex: str):
@@ -112,15 +102,16 @@ def exact_weight_interpreter(regex: str):
     return Exact
 
 
-def c5_case(interp_cls):
+def c5_case(interp_cls, name="c5"):
     """BASELINE C5's denoiser (Unet3D(dim 64), one 16 x 64 x 64 clip, the sampler's 2-row plan) through the interpreter, against the oracle: the
-    case of tests/test_video_gpu.py::test_unet3d_forward_vs_oracle_c5."""
+    case of tests/test_video_gpu.py::test_unet3d_forward_vs_oracle_c5 (c5hd32: ..._c5_head_dim_32)."""
     from imagen_pytorch_amd import Unet3D
     from imagen_pytorch_amd.engine3d import UnetEngine3D
     from oracle import unet3d_oracle as u3
+    from plan_interp import run_engine
     from test_video_gpu import _derandomise_unet3d as derandomise_unet3d   # (the C5 test's own weights: dirac + dense temporal convs)
 
-    kw = dict(dim=64, dim_mults=(1, 2, 4, 8))
+    kw = dict(dim=64, dim_mults=(1, 2, 4, 8), **C5_HEADS[name])
     torch.manual_seed(0)
     u = Unet3D(**kw).eval()
     derandomise_unet3d(u)
@@ -132,17 +123,8 @@ def c5_case(interp_cls):
     with torch.no_grad():
         ref = u3.unet3d_forward(sd, kw, x, t, text_embeds=te, text_mask=mask)
         ref_null = u3.unet3d_forward(sd, kw, x, t, text_embeds=te, text_mask=mask, cond_drop_prob=1.0)
-    eng = UnetEngine3D(u, 2, 1, 16, 64, "cpu", dry=True)
-    eng.set_conditioning(text_embeds=te, text_mask=mask, keep=torch.tensor([True, False]), lowres_noise_times=None)
-    it = interp_cls()
-    for buf in (eng.x_in, eng.times, eng.lowres_times, eng.out, eng.keep_u8, eng.src_idx, eng.arange_idx, eng.t_const.t):
-        it.mem.register(buf)
-    it.run(eng._static_plans[24][0])
-    eng.x_in.copy_(x.permute(0, 2, 1, 3, 4))
-    eng.times.copy_(t.repeat(2))
-    it.run(eng.step_plan)
-    out = eng.out.permute(0, 2, 1, 3, 4)
-    print(f"c5 Unet3D(dim 64) 16x64x64, plan through the interpreter: cond {nerr(out[:1], ref):.3e} null {nerr(out[1:], ref_null):.3e}  ({len(eng.step_plan.ops)} launches)", flush=True)
+    out_c, out_n, eng, _ = run_engine(UnetEngine3D(u, 2, 1, 16, 64, "cpu", dry=True), x, t, te, mask, it=interp_cls())
+    print(f"{name} Unet3D(dim 64) 16x64x64, plan through the interpreter: cond {nerr(out_c, ref):.3e} null {nerr(out_n, ref_null):.3e}  ({len(eng.step_plan.ops)} launches)", flush=True)
 
 
 def main():
@@ -159,8 +141,8 @@ def main():
     ops.KEEP_REFERENCE_WEIGHTS = True
     if args.exact_weights:
         Interpreter = exact_weight_interpreter(args.exact_weights)
-    if args.config == "c5":
-        c5_case(Interpreter)
+    if args.config in C5_HEADS:
+        c5_case(Interpreter, args.config)
         return
     kw, S, B = CONFIGS[args.config], args.size, args.batch
     for seed in args.seeds:
