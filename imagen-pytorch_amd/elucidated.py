@@ -20,6 +20,7 @@ step's; both go straight into the engine's `self_cond_in`, which every evaluatio
 """
 from __future__ import annotations
 
+import functools
 import math
 from collections import namedtuple
 from typing import Callable, List, Optional
@@ -36,6 +37,8 @@ Hparams = namedtuple('Hparams', Hparams_fields)
 
 
 class ElucidatedImagen(Imagen):
+    _lowres_time_raw = True    # el.py:700, 728: the raw augmentation level conditions the unet at sample time
+
     def __init__(
         self,
         unets,
@@ -82,7 +85,6 @@ class ElucidatedImagen(Imagen):
         hparams = [num_sample_steps, sigma_min, sigma_max, sigma_data, rho, P_mean, P_std, S_churn, S_tmin, S_tmax, S_noise]
         hparams = [_cast_tuple(hp, num_unets) for hp in hparams]
         self.hparams = [Hparams(*unet_hp) for unet_hp in zip(*hparams)]    # el.py:233-236
-        self._lowres_time_raw = True    # el.py:700, 728: the raw augmentation level conditions the unet at sample time
 
     # ---- schedule (el.py:373-391, 428-436) -------------------------------------------------------------------------------
     @staticmethod
@@ -143,57 +145,43 @@ class ElucidatedImagen(Imagen):
 
     # ---- per-stage plans --------------------------------------------------------------------------------------------------
     def _build_stage(self, idx: int, B: int, device, *, cond_scale: float, with_text: bool, inject_noise: bool, sample_offset: int,
-                     resample_times: int = 0, frames: int = 0, prompt_frames: tuple = (0, 0)):
+                     resample_times: int = 0, frames: int = 0, prompt_frames: tuple = (0, 0), sigma_overrides: Optional[dict] = None):
         unet = self.unets[idx]
-        S = self.image_sizes[idx]
         hp = self.hparams[idx]
-        over = getattr(self._tls, 'sigma_overrides', None)          # sample(sigma_min=, sigma_max=), el.py:425-426, 647-648
-        if over is not None:
-            hp = hp._replace(**{k: v[idx] for k, v in over.items() if v[idx] is not None})
+        if sigma_overrides is not None:                  # sample(sigma_min=, sigma_max=), el.py:425-426, 647-648
+            hp = hp._replace(**{k: v[idx] for k, v in sigma_overrides.items() if v[idx] is not None})
         cfg = cond_scale != 1.
         R = resample_times
-        key = ("edm", idx, B, S, str(device), float(cond_scale), with_text, inject_noise, sample_offset, self.dynamic_thresholding[idx],
-               self.dynamic_thresholding_percentile, tuple(hp), frames, prompt_frames, R, self._lane)
-        st = self._stages.get(key)
-        if st is not None and not st['eng'].stale():
+        key = ("edm", idx, B, self.image_sizes[idx], str(device), float(cond_scale), with_text, inject_noise, sample_offset,
+               self.dynamic_thresholding[idx], self.dynamic_thresholding_percentile, tuple(hp), frames, prompt_frames, R, self._lane)
+        tables = []
+
+        def coef():
+            init_sigma, tabs = self._tables(hp, max(R, 1))
+            tables[:] = [init_sigma] + [t.to(device) for t in tabs]
+            return tables[1]
+
+        # (the time table of an image stage has this sampler's 2T evaluation rows: both denoiser evaluations of a step read it)
+        st, built = self._new_stage(key, idx, B, device, cfg=cfg, with_text=with_text, inject_noise=inject_noise, sample_offset=sample_offset,
+                                    resample_times=R, frames=frames, prompt_frames=prompt_frames, coef=coef)
+        if not built:
             return st
-        rows = 2 * B if cfg else B
-        video = isinstance(unet, Unet3D)
-        if video:      # as in Imagen._stage: the state is the engine's frame-major clip, every update below is elementwise per sample
-            assert frames > 0, 'video_frames must be passed in on sample time if training on video'
-            from . import engine3d
-            eng = engine3d.UnetEngine3D(unet, rows, B, frames, S, device, with_text=with_text, pre_frames=prompt_frames[0],
-                                        post_frames=prompt_frames[1])
-        else:
-            from . import engine
-            eng = engine.UnetEngine(unet, rows, B, S, device, with_text=with_text)
-        n = eng.x_in[0].numel()
-        dev = device
+        eng, n, dev, step_ptr, seed_dev, step_plan, noise, final = (st['eng'], st['n'], device, st['step_ptr'], st['seed_dev'], st['step_plan'],
+                                                                    st['noise'], st['final'])
         # self-conditioning (el.py:496, 518, 538): every evaluation packs `sc`; the Euler op leaves the first evaluation's clamped output in
         # it for the Heun evaluation, the Heun op the second one's for the next step (or the next resample of the same timestep)
         sc = eng.self_cond_in if getattr(unet, 'self_cond', False) else None
         assert sc is None or sc.numel() == B * n
-        init_sigma, (coef, w_hat, w_euler, w_heun, w_renoise) = self._tables(hp, max(R, 1))
-        coef, w_hat, w_euler, w_heun, w_renoise = (t.to(dev) for t in (coef, w_hat, w_euler, w_heun, w_renoise))
+        init_sigma, coef, w_hat, w_euler, w_heun, w_renoise = tables
         if inject_noise:   # the churn noise comes in through t1 (weight col 1) instead of the in-kernel Philox stream (col 4)
             for w in (w_hat, w_renoise):
                 w[:, 1] = w[:, 4]
                 w[:, 4] = 0
-        step_ptr = torch.zeros(1, dtype=torch.int32, device=dev)
-        seed_dev = torch.zeros(2, dtype=torch.int32, device=dev)
-        eng.bind_step_counter(coef, step_ptr)
-        # image stages without inpainting resampling: the timestep-only conditioning chain of both denoiser evaluations of a step comes out
-        # of the per-request table (engine.enable_time_table; the table has this sampler's 2T evaluation rows)
-        from . import imagen as _imagen
-        step_plan = eng.step_plan
-        if _imagen.TIME_TABLE and not R and hasattr(eng, "enable_time_table"):
-            step_plan = eng.enable_time_table(coef, step_ptr) or step_plan
         mk = lambda: torch.empty_like(eng.x_in)
-        x, xhat, xnext, x0a, x0b, absx0, final = mk(), mk(), mk(), mk(), mk(), mk(), mk()
+        x, xhat, xnext, x0a, x0b, absx0 = mk(), mk(), mk(), mk(), mk(), mk()
         qa, qb = torch.empty(B, device=dev), torch.empty(B, device=dev)
         W = ops.ENUMS["IMAGEN_QUANTILE_SCRATCH_WORDS"]
         scr_a, scr_b = (torch.empty(B * W, dtype=torch.int32, device=dev) for _ in range(2))
-        noise = mk() if inject_noise else None
         dyn = bool(self.dynamic_thresholding[idx])
         thr = 1 if dyn else 2                      # clamp=True (el.py:399): dynamic threshold, else clamp to [-1, 1]
         q = float(self.dynamic_thresholding_percentile)
@@ -202,14 +190,10 @@ class ElucidatedImagen(Imagen):
         w_one = torch.zeros(1, 8, device=dev)
         w_one[0, 0] = 1.0
         zero_ptr = torch.zeros(1, dtype=torch.int32, device=dev)
-        extra = {}
-        if R:   # inpainting (el.py:459-470, 497-498): x_hat = where(mask, known, x) + added noise — the known pixels go into x first
-            extra = dict(known=torch.zeros_like(eng.x_in), mask=torch.zeros_like(eng.x_in),
-                         noise_renoise=mk() if inject_noise else None)
 
         def first_eval(plan):
-            if R:
-                ops.lincomb(plan, extra['known'], x, w_one, zero_ptr, mask=extra['mask'], mask_else=x, label="edm.inpaint.blend", **kw)
+            if R:   # inpainting (el.py:459-470, 497-498): x_hat = where(mask, known, x) + added noise — the known pixels go into x first
+                ops.lincomb(plan, st['known'], x, w_one, zero_ptr, mask=st['mask'], mask_else=x, label="edm.inpaint.blend", **kw)
             ops.lincomb(plan, x, xhat, w_hat, step_ptr, t1=noise, out2=eng.x_in, label="edm.x_hat", **kw)
             plan.extend(step_plan)
             ops.cfg_x0(plan, xhat, eng.out, coef, step_ptr, x0a, absx0, B=B, n_per_sample=n, cfg=cfg, cond_scale=float(cond_scale),
@@ -229,7 +213,7 @@ class ElucidatedImagen(Imagen):
         ops.lincomb(full, xhat, x, w_heun, step_ptr, t1=x0a, t2=xnext, t3=x0b, q1=qa if dyn else None, q3=qb if dyn else None,
                     thr_mode=thr, advance=not R, thr3_out=sc, label="edm.heun", **kw)
         if R:   # RePaint re-noising before the next resample of the same timestep (identity weights where the reference skips it)
-            ops.lincomb(full, x, x, w_renoise, step_ptr, t1=extra['noise_renoise'], advance=True, label="edm.inpaint.renoise",
+            ops.lincomb(full, x, x, w_renoise, step_ptr, t1=st['noise_renoise'], advance=True, label="edm.inpaint.renoise",
                         **{**kw, "stream_id": idx | 0x200})
 
         last = Plan(f"edm-stage{idx}-last")       # sigma_next = 0: Euler step only, then clamp + unnormalise (el.py:515, 540-545)
@@ -241,10 +225,8 @@ class ElucidatedImagen(Imagen):
 
         w_init = torch.zeros(1, 8, device=dev)
         w_init[0, 0] = init_sigma
-        st = dict(eng=eng, plan=full, last=last, graph=None, graph_last=None, coef=coef, step_ptr=step_ptr, seed_dev=seed_dev, noise=noise,
-                  final=final, T=hp.num_sample_steps, S=S, x=x, w_init=w_init, zero_ptr=zero_ptr,
-                  tables=(w_hat, w_euler, w_heun, w_renoise, w_one), self_cond=sc, video=video, frames=frames, R=R,
-                  bufs=(xhat, xnext, x0a, x0b, absx0, qa, qb, scr_a, scr_b), **extra)
+        st.update(plan=full, last=last, graph_last=None, T=hp.num_sample_steps, x=x, w_init=w_init, zero_ptr=zero_ptr,
+                  tables=(w_hat, w_euler, w_heun, w_renoise, w_one), self_cond=sc, bufs=(xhat, xnext, x0a, x0b, absx0, qa, qb, scr_a, scr_b))
         self._stages[key] = st
         return st
 
@@ -262,18 +244,14 @@ class ElucidatedImagen(Imagen):
         B = eng.src_batch
         n = x[0].numel()
 
-        def draw(tag, like):   # videos are drawn in the reference's (b, c, f, h, w) layout, the state is frame-major
-            if not st.get('video', False):
-                return noise_fn(tag, tuple(like.shape))
-            b, f, c, h, w = like.shape
-            return noise_fn(tag, (b, c, f, h, w)).permute(0, 2, 1, 3, 4)
+        draw = functools.partial(self._draw, st, noise_fn)
 
         def init_state():
             if noise_fn is not None:
                 x.copy_(draw(("init", stage), x))
             else:
                 pl = Plan("edm-init-noise")
-                ops.randn(pl, x, seed=seed, stream_id=stage, tag=TAG_INIT, sample_offset=st.get('sample_offset', 0))
+                ops.randn(pl, x, seed=seed, stream_id=stage, tag=TAG_INIT, sample_offset=st['sample_offset'])
                 pl.run()
             pl = Plan("edm-init-scale")                      # images = init_sigma * randn (el.py:440-442; sigma_0 also when steps are skipped)
             ops.lincomb(pl, x, x, st['w_init'], st['zero_ptr'], B=B, n_per_sample=n)
@@ -284,7 +262,7 @@ class ElucidatedImagen(Imagen):
                 st['self_cond'].zero_()                      # el.py:451: x_start = None (also after the warm-up and when steps are skipped)
             st['step_ptr'].fill_(self._row(skip, inner - 1, T, inner))   # el.py:477-479: the skipped steps are never run
 
-        st['seed_dev'].copy_(torch.tensor([seed & 0x7FFFFFFF, (seed >> 31) & 0x7FFFFFFF], dtype=torch.int32))
+        st['seed_dev'].copy_(torch.tensor(self._seed_words(seed), dtype=torch.int32))
         steps = T - skip if max_steps is None else min(T - skip, max_steps)
         if use_graph and st['graph'] is None:
             if noise_fn is not None:
@@ -316,13 +294,7 @@ class ElucidatedImagen(Imagen):
                     (st['last'] if is_last else st['plan']).run()
                 if trace is not None:
                     trace.append(x.clone())
-        if skip + steps == T:
-            out = st['final']
-        else:
-            out = (x.clamp(-1., 1.) + 1) * 0.5                # truncated loop (tests)
-        if R:
-            out = torch.where(st['mask'] != 0, (st['known'] + 1) * 0.5, out)   # el.py:542-545
-        return out
+        return self._stage_output(st, x, skip + steps == T)
 
     # ---- public sampling API (el.py:547-745) ---------------------------------------------------------------------------------
     @torch.no_grad()
@@ -365,24 +337,11 @@ class ElucidatedImagen(Imagen):
         negative_text_embeds=None,
         negative_text_masks=None,
     ):
-        with self._eval_mode():
-            try:
-                self._tls.conditioning = conditioning
-                self._tls.negative = self._negative_of_call(conditioning, negative_texts, negative_text_embeds, negative_text_masks)
-                n_unets = len(self.unets)
-                self._tls.sigma_overrides = None if sigma_min is None and sigma_max is None else dict(
-                    sigma_min=_cast_tuple(sigma_min, n_unets), sigma_max=_cast_tuple(sigma_max, n_unets))
-                if conditioning is not None:
-                    assert texts is None and text_embeds is None and text_masks is None, 'pass either `conditioning` or texts / text_embeds'
-                    text_embeds, text_masks = conditioning.text_embeds, conditioning.text_masks
-                    if text_embeds is None:
-                        batch_size = conditioning.batch_size
-                return self._sample(texts, text_masks, text_embeds, video_frames, cond_images, cond_video_frames, post_cond_video_frames,
-                                    inpaint_videos, inpaint_images, inpaint_masks, inpaint_resample_times, init_images, skip_steps, batch_size,
-                                    cond_scale, lowres_sample_noise_level, start_at_unet_number, start_image_or_video, stop_at_unet_number,
-                                    return_all_unet_outputs, return_pil_images, device, use_tqdm, noise_fn, seed, sample_offset, use_graph,
-                                    max_steps)
-            finally:
-                self._tls.conditioning = None
-                self._tls.negative = None
-                self._tls.sigma_overrides = None
+        return self._sample(self._call(**{k: v for k, v in locals().items() if k != 'self'}))   # (the keywords, as given)
+
+    def _call(self, sigma_min=None, sigma_max=None, **kw):
+        """Imagen._call; this sampler's two extra keywords become the record's per-unet `sigma_overrides`, which `_build_stage` takes."""
+        n_unets = len(self.unets)
+        over = None if sigma_min is None and sigma_max is None else dict(sigma_min=_cast_tuple(sigma_min, n_unets),
+                                                                         sigma_max=_cast_tuple(sigma_max, n_unets))
+        return super()._call(sigma_overrides=over, **kw)

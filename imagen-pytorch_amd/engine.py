@@ -26,7 +26,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .modules import CrossAttentionP, CrossEmbedP, ParallelP, PixelShuffleUpsampleP, ResnetBlockP, TransformerBlockP
+from .modules import CrossAttentionP, ParallelP, PixelShuffleUpsampleP, ResnetBlockP, TransformerBlockP
 from .ops import ACT_GELU, ACT_SILU, LOG2E, OUT_NCHW_F32, OUT_PIXEL_SHUFFLE, Act, Plan
 
 SIM_SCALE = 8.0  # cosine-sim attention scale (ip.py:510, 768, 386)
@@ -38,6 +38,11 @@ def _f32(t, dev):
 
 def _f16(t, dev):
     return t.detach().to(torch.float16).contiguous().to(dev)
+
+
+def _conv_wb(mod):
+    """(weight, bias) of a conv module in fp32, as the init / final conv weight builders take them."""
+    return mod.weight.detach().float(), mod.bias.detach().float()
 
 
 def _pad_vec(v: torch.Tensor, n: int) -> torch.Tensor:
@@ -241,6 +246,59 @@ class UnetEngine:
             out.append(u.final_res_block)
         return out
 
+    def _emit_time_chain(self, plan, replicas: int, split, f32):
+        """The time-conditioning head of a step plan, shared by the image and the video planner (ip.py:1573-1578, 1660, 738-741;
+        iv.py:1764-1781): time_embed -> to_time_cond -> to_time_tokens -> norm_cond -> every ResnetBlock's time MLP as one GEMM -> the
+        (scale, shift) tables `pa2` / `ps2`.  `replicas`: rows of those tables per row of the batch — 1, or the F frames of a clip, whose
+        per-frame convs index their affine by frame: t is then first replicated over the frames (max over the levels' frame counts:
+        temporal strides only shrink F).  `split`: split-precision weights for the fp16 GEMMs (SPLIT_STATIC).  `f32`: to_time_cond and
+        the time MLPs on fp32 rows (TIME_CHAIN_F32 of the planner's module).  Leaves what the traversal reads on the engine: `c_time`
+        (normalised time tokens), `pa2` / `ps2` / `total_c`, `_blk_index` / `_blk_off`, and `hid` / `t` / `_time_embed_op`."""
+        u, R, W = self.unet, self.R, self.W
+        self.hid = self.new(1, 1, R, self.Tc)
+        self._time_embed_op = ops.time_embed(
+            plan, times=self.times, coef=None, step_ptr=None,
+            freqs=W.f32("time.freqs", lambda: u.to_time_hiddens[0].weights), w=W.f32("time.w", lambda: u.to_time_hiddens[1].weight),
+            bias=W.f32("time.b", lambda: u.to_time_hiddens[1].bias), hid=self.hid, label="time_embed")
+        if f32:
+            self.t = self.f32buf(R, self.Tc)
+            ops.linear_f32(plan, self.hid, W.f32("time.cond.wt32", lambda: u.to_time_cond[0].weight.t()), W.f32("time.cond.b32", lambda: u.to_time_cond[0].bias),
+                           self.t, res=self.t_const, label="to_time_cond")
+        else:
+            self.t = self.new(1, 1, R, self.Tc)
+            ops.igemm(plan, self.hid, W.conv("time.cond", u.to_time_cond[0], split=split), self.t, res=self.t_const, label="to_time_cond")
+        # time tokens -> norm_cond (ip.py:1577, 1660)
+        tok_raw = self.new(1, 1, R, self.ntt * self.cond_dim)
+        ops.igemm(plan, self.hid, W.conv("time.tokens", u.to_time_tokens[0], split=split), tok_raw, label="to_time_tokens")
+        self.c_time = self.new(1, 1, R * self.ntt, self.cond_dim)
+        tok_rows = Act(tok_raw.t, 1, 1, R * self.ntt, self.cond_dim, self.cond_dim, R * self.ntt * self.cond_dim)
+        ops.ln_residual(plan, tok_rows, W.f32("norm_cond.w", lambda: u.norm_cond.weight), self.c_time,
+                        beta=W.f32("norm_cond.b", lambda: u.norm_cond.bias), eps=1e-5, label="norm_cond(time)")
+
+        # ---- all ResnetBlock time-MLPs in one GEMM + scale/shift tables (ip.py:738-741)
+        blocks = self._all_resnet_blocks()
+        self._blk_index = {id(rb): i for i, rb in enumerate(blocks)}
+        tw, tb, gam, isc, ish, self._blk_off, total_c = W.get("timemlp.tables", lambda: self._time_mlp_tables(blocks))
+        self.total_c = total_c
+        rows, Tc, t = R * replicas, self.Tc, self.t
+        if replicas > 1 and f32:      # (fp32 rows copied as pairs of halves)
+            t = self.f32buf(rows, Tc)
+            ops.rows_copy(plan, self.t.view(torch.float16), t.view(torch.float16), B=R, rows=replicas, C=2 * Tc, src_bs=2 * Tc, src_rs=0,
+                          dst_bs=2 * replicas * Tc, dst_rs=2 * Tc, label="t_per_frame")
+        elif replicas > 1:
+            t = self.new(1, 1, rows, Tc)
+            ops.rows_copy(plan, self.t.t, t.t, B=R, rows=replicas, C=Tc, src_bs=Tc, src_rs=0, dst_bs=replicas * Tc, dst_rs=Tc, label="t_per_frame")
+        if f32:
+            ss = self.f32buf(rows, tw.shape[0])
+            ops.linear_f32(plan, t, W.f32("timemlp.wt32", lambda: tw.t()), W.f32("timemlp.b32", lambda: tb), ss, act_in=ACT_SILU, label="time_mlps")
+        else:
+            ss = self.new(1, 1, rows, tw.shape[0])
+            ops.igemm(plan, t, W.raw("timemlp.w", tw, tb, split=split), ss, act_in=ACT_SILU, label="time_mlps")
+        self.pa2 = self.f32buf(rows, total_c)
+        self.ps2 = self.f32buf(rows, total_c)
+        ops.scale_shift(plan, ss, W.f32("timemlp.gam", lambda: gam), W.get("timemlp.isc", lambda: isc.to(self.dev)),
+                        W.get("timemlp.ish", lambda: ish.to(self.dev)), self.pa2, self.ps2)
+
     def _build_step_plan(self) -> Plan:
         u, R, S, W = self.unet, self.R, self.S, self.W
         plan = Plan("unet-step")
@@ -253,43 +311,9 @@ class UnetEngine:
         if self.self_cond_in is not None:
             self._self_cond_op = ops.pack_image(plan, self.self_cond_in, self.cond_in, self.cimg, brep=R // self.src_batch, label="pack_self_cond")
 
-        # ---- time conditioning (ip.py:1573-1578)
+        # ---- time conditioning, the batched time MLPs and their scale / shift tables
         chain_begin = len(plan.ops)
-        self.hid = self.new(1, 1, R, self.Tc)
-        self._time_embed_op = ops.time_embed(
-            plan, times=self.times, coef=None, step_ptr=None,
-            freqs=W.f32("time.freqs", lambda: u.to_time_hiddens[0].weights), w=W.f32("time.w", lambda: u.to_time_hiddens[1].weight),
-            bias=W.f32("time.b", lambda: u.to_time_hiddens[1].bias), hid=self.hid, label="time_embed")
-        if TIME_CHAIN_F32:
-            self.t = self.f32buf(R, self.Tc)
-            ops.linear_f32(plan, self.hid, W.f32("time.cond.wt32", lambda: u.to_time_cond[0].weight.t()), W.f32("time.cond.b32", lambda: u.to_time_cond[0].bias),
-                           self.t, res=self.t_const, label="to_time_cond")
-        else:
-            self.t = self.new(1, 1, R, self.Tc)
-            ops.igemm(plan, self.hid, W.conv("time.cond", u.to_time_cond[0], split=SPLIT_STATIC), self.t, res=self.t_const, label="to_time_cond")
-        # time tokens -> norm_cond (ip.py:1577, 1660)
-        tok_raw = self.new(1, 1, R, self.ntt * self.cond_dim)
-        ops.igemm(plan, self.hid, W.conv("time.tokens", u.to_time_tokens[0], split=SPLIT_STATIC), tok_raw, label="to_time_tokens")
-        self.c_time = self.new(1, 1, R * self.ntt, self.cond_dim)
-        tok_rows = Act(tok_raw.t, 1, 1, R * self.ntt, self.cond_dim, self.cond_dim, R * self.ntt * self.cond_dim)
-        ops.ln_residual(plan, tok_rows, W.f32("norm_cond.w", lambda: u.norm_cond.weight), self.c_time,
-                        beta=W.f32("norm_cond.b", lambda: u.norm_cond.bias), eps=1e-5, label="norm_cond(time)")
-
-        # ---- all ResnetBlock time-MLPs in one GEMM + scale/shift tables (ip.py:738-741)
-        blocks = self._all_resnet_blocks()
-        self._blk_index = {id(rb): i for i, rb in enumerate(blocks)}
-        tw, tb, gam, isc, ish, self._blk_off, total_c = W.get("timemlp.tables", lambda: self._time_mlp_tables(blocks))
-        self.total_c = total_c
-        if TIME_CHAIN_F32:
-            ss = self.f32buf(R, tw.shape[0])
-            ops.linear_f32(plan, self.t, W.f32("timemlp.wt32", lambda: tw.t()), W.f32("timemlp.b32", lambda: tb), ss, act_in=ACT_SILU, label="time_mlps")
-        else:
-            ss = self.new(1, 1, R, tw.shape[0])
-            ops.igemm(plan, self.t, W.raw("timemlp.w", tw, tb, split=SPLIT_STATIC), ss, act_in=ACT_SILU, label="time_mlps")
-        self.pa2 = self.f32buf(R, total_c)
-        self.ps2 = self.f32buf(R, total_c)
-        ops.scale_shift(plan, ss, W.f32("timemlp.gam", lambda: gam), W.get("timemlp.isc", lambda: isc.to(self.dev)),
-                        W.get("timemlp.ish", lambda: ish.to(self.dev)), self.pa2, self.ps2)
+        self._emit_time_chain(plan, replicas=1, split=SPLIT_STATIC, f32=TIME_CHAIN_F32)
 
         # ---- conditioning K/V rows that depend on the timestep (filled after the traversal registers the sites)
         self._kv_dynamic_anchor = len(plan.ops)
@@ -363,19 +387,19 @@ class UnetEngine:
         return plan
 
     # ---- init / final convs
-    def _init_conv(self, plan, out: Act):
-        """CrossEmbedLayer (ip.py:1051-1076, stride 1) as ONE kmax x kmax conv with the smaller kernels zero-embedded;
-        or the plain init conv (ip.py:1198)."""
+    def _init_conv_weight(self, wb):
+        """The packed init-conv weight; `wb(module)` yields a conv module's (weight [o, i, kh, kw], bias) in fp32 (the video planner's
+        modules carry singleton frame dims).  CrossEmbedLayer (ip.py:1051-1076, stride 1) becomes ONE kmax x kmax conv with the smaller
+        kernels zero-embedded."""
         u = self.unet
-
-        cc = self.cond_in.shape[1] if self.cond_in is not None else 0
-        sc = self.self_cond_in.shape[1] if self.self_cond_in is not None else 0
+        cc = getattr(u, 'cond_images_channels', 0)
+        sc = u.channels if getattr(u, 'self_cond', False) else 0
         c = u.channels
         nl = c if self.lowres else 0
         auxp = self.cimg.C if self.cimg is not None else 0
 
         def spread(w):
-            """Reference input channels [cond image | x | self_cond | lowres] (ip.py:1541-1560) ->
+            """Reference input channels [cond image | x | self_cond | lowres] (ip.py:1541-1560; iv.py:1676, 1684, 1731) ->
             ours [x | lowres | 0.. (8)] ++ [self_cond | cond image | 0.. (auxp)]."""
             assert w.shape[1] == cc + c + sc + nl
             wp = torch.zeros(w.shape[0], 8 + auxp, *w.shape[2:])
@@ -385,20 +409,38 @@ class UnetEngine:
             wp[:, 8 + sc: 8 + sc + cc] = w[:, :cc]
             return wp
 
-        def make():
-            if isinstance(u.init_conv, CrossEmbedP):
-                kmax = max(u.init_conv.kernel_sizes)
-                ws, bs = [], []
-                for conv, k in zip(u.init_conv.convs, u.init_conv.kernel_sizes):
-                    w = torch.zeros(*conv.weight.shape[:2], kmax, kmax)
-                    p = (kmax - k) // 2
-                    w[:, :, p:p + k, p:p + k] = conv.weight.detach().float()
-                    ws.append(spread(w))
-                    bs.append(conv.bias.detach().float())
-                return ops.pack_weight(torch.cat(ws), torch.cat(bs), self.dev, G=1)
-            conv = u.init_conv
-            return ops.pack_weight(spread(conv.weight.detach().float()), conv.bias.detach().float(), self.dev, G=1)
+        sizes = getattr(u.init_conv, 'kernel_sizes', None)
+        if sizes is None:                                # the plain init conv (ip.py:1198)
+            w, b = wb(u.init_conv)
+            return ops.pack_weight(spread(w), b, self.dev, G=1)
+        kmax = max(sizes)
+        ws, bs = [], []
+        for conv, k in zip(u.init_conv.convs, sizes):
+            cw, cb = wb(conv)
+            w = torch.zeros(*cw.shape[:2], kmax, kmax)
+            p = (kmax - k) // 2
+            w[:, :, p:p + k, p:p + k] = cw
+            ws.append(spread(w))
+            bs.append(cb)
+        return ops.pack_weight(torch.cat(ws), torch.cat(bs), self.dev, G=1)
 
+    def _final_conv_weight(self, wb, C: int, lowres: bool, split: bool, G=None):
+        """The packed final-conv weight over C feature channels; with `lowres` its second input is the packed image
+        [x (c) | lowres (c) | zero pad] (the reference concatenates lowres after the features, ip.py:1722-1725)."""
+        u = self.unet
+        w, b = wb(u.final_conv)
+        if not lowres:
+            return ops.pack_weight(w, b, self.dev, split=split)
+        co, ci, kh, kw = w.shape
+        wp = torch.zeros(co, C + 8, kh, kw)
+        wp[:, : C] = w[:, : C]
+        wp[:, C + u.channels: C + 2 * u.channels] = w[:, C:]
+        return ops.pack_weight(wp, b, self.dev, G=G)
+
+    def _init_conv(self, plan, out: Act):
+        """CrossEmbedLayer (ip.py:1051-1076, stride 1) as ONE kmax x kmax conv with the smaller kernels zero-embedded;
+        or the plain init conv (ip.py:1198)."""
+        make = lambda: self._init_conv_weight(_conv_wb)
         out.ssq = self.f32buf(out.rows)
         R, B = self.R, self.src_batch
         px = out.H * out.W
@@ -428,20 +470,9 @@ class UnetEngine:
         kh = u.final_conv.weight.shape[-1]
         split = extra is None and self._split_small(x.C, kh * kh, u.final_conv.weight.shape[0], x.rows)
 
-        def make():
-            w = u.final_conv.weight.detach().float()
-            co, ci, kh, kw = w.shape
-            if extra is None:
-                return ops.pack_weight(w, u.final_conv.bias.detach().float(), self.dev, split=split)
-            wp = torch.zeros(co, x.C + 8, kh, kw)
-            wp[:, : x.C] = w[:, : x.C]
-            # packed image channel layout: [x (C) | lowres (C) | zero pad]; the reference concatenates lowres after the features
-            wp[:, x.C + u.channels: x.C + 2 * u.channels] = w[:, x.C:]
-            # 32-channel k-chunks whenever the feature part allows it (the 8 image channels then occupy one group of a second,
-            # otherwise zero chunk): the 8-channel-chunk path (G = 1) took 100 us for this layer at 256^2, twice a 32->32 conv
-            G = 4 if x.C % 32 == 0 else None
-            return ops.pack_weight(wp, u.final_conv.bias.detach().float(), self.dev, G=G)
-
+        # 32-channel k-chunks whenever the feature part allows it (the 8 image channels then occupy one group of a second,
+        # otherwise zero chunk): the 8-channel-chunk path (G = 1) took 100 us for this layer at 256^2, twice a 32->32 conv
+        make = lambda: self._final_conv_weight(_conv_wb, x.C, extra is not None, split, G=4 if x.C % 32 == 0 else None)
         ops.igemm(plan, x, self.W.get("final_conv|split" if split else "final_conv", make), self.out, x2=extra, out_mode=OUT_NCHW_F32, label="final_conv")
 
     def _combine_upsample_fmaps(self, plan, x: Act, fmaps: List[Act]) -> Act:

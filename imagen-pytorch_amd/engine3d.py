@@ -33,7 +33,7 @@ import torch.nn.functional as TF
 
 from . import ops
 from .engine import SIM_SCALE, UnetEngine, _pad_vec
-from .modules3d import CrossEmbed3dP, Parallel3dP, PixelShuffleUpsample3dP, TransformerBlock3dP
+from .modules3d import Parallel3dP, PixelShuffleUpsample3dP, TransformerBlock3dP
 from .ops import ACT_GELU, ACT_SILU, OUT_NCHW_F32, OUT_PIXEL_SHUFFLE, Act, Plan
 
 
@@ -46,6 +46,12 @@ def _w2d(mod):
     elif w.ndim == 3:
         w = w[:, :, :, None]
     return SimpleNamespace(weight=w, bias=None if mod.bias is None else mod.bias.detach().float())
+
+
+def _wb2d(mod):
+    """_w2d as the (weight, bias) pair the image planner's init / final conv weight builders take."""
+    cw = _w2d(mod)
+    return cw.weight, cw.bias
 
 
 # Split-precision weights (engine.py, SPLIT_*) on the video path's OUTPUT stage: `final_conv` and block1 of `final_res_block` — the two convs
@@ -166,50 +172,8 @@ class UnetEngine3D(UnetEngine):
                 ops.rows_copy(plan, self.img_x.t, self.fin2.t, B=R, rows=1, C=Fx * fr, src_bs=Fx * fr, src_rs=0, dst_bs=F * fr, dst_rs=0,
                               dst_off=self.Fpre * fr, label="place_lowres_frames")
 
-        # ---- time conditioning: identical to the image Unet (iv.py:1764-1781)
-        self.hid = self.new(1, 1, R, self.Tc)
-        self._time_embed_op = ops.time_embed(
-            plan, times=self.times, coef=None, step_ptr=None,
-            freqs=W.f32("time.freqs", lambda: u.to_time_hiddens[0].weights), w=W.f32("time.w", lambda: u.to_time_hiddens[1].weight),
-            bias=W.f32("time.b", lambda: u.to_time_hiddens[1].bias), hid=self.hid, label="time_embed")
-        # the timestep-conditioning chain in fp32 (engine.TIME_CHAIN_F32): these are PER-SAMPLE rows, so an fp16 rounding of them is a
-        # bias of the whole clip, not noise that averages over pixels
-        if TIME_CHAIN_F32:
-            self.t = self.f32buf(R, self.Tc)
-            ops.linear_f32(plan, self.hid, W.f32("time.cond.wt32", lambda: u.to_time_cond[0].weight.t()), W.f32("time.cond.b32", lambda: u.to_time_cond[0].bias),
-                           self.t, res=self.t_const, label="to_time_cond")
-        else:
-            self.t = self.new(1, 1, R, self.Tc)
-            ops.igemm(plan, self.hid, W.conv("time.cond", u.to_time_cond[0]), self.t, res=self.t_const, label="to_time_cond")
-        tok_raw = self.new(1, 1, R, self.ntt * self.cond_dim)
-        ops.igemm(plan, self.hid, W.conv("time.tokens", u.to_time_tokens[0]), tok_raw, label="to_time_tokens")
-        self.c_time = self.new(1, 1, R * self.ntt, self.cond_dim)
-        tok_rows = Act(tok_raw.t, 1, 1, R * self.ntt, self.cond_dim, self.cond_dim, R * self.ntt * self.cond_dim)
-        ops.ln_residual(plan, tok_rows, W.f32("norm_cond.w", lambda: u.norm_cond.weight), self.c_time,
-                        beta=W.f32("norm_cond.b", lambda: u.norm_cond.bias), eps=1e-5, label="norm_cond(time)")
-
-        # ---- every ResnetBlock's time-MLP in one GEMM.  The per-frame convs index their affine by frame (batch R*F), so t is
-        # first replicated over the frames of its clip (max over the levels' frame counts: temporal strides only shrink F)
-        blocks = self._all_resnet_blocks()
-        self._blk_index = {id(rb): i for i, rb in enumerate(blocks)}
-        tw, tb, gam, isc, ish, self._blk_off, total_c = W.get("timemlp.tables", lambda: self._time_mlp_tables(blocks))
-        self.total_c = total_c
-        if TIME_CHAIN_F32:     # (fp32 rows copied as pairs of halves)
-            t_rep = self.f32buf(R * F, self.Tc)
-            ops.rows_copy(plan, self.t.view(torch.float16), t_rep.view(torch.float16), B=R, rows=F, C=2 * self.Tc, src_bs=2 * self.Tc, src_rs=0,
-                          dst_bs=2 * F * self.Tc, dst_rs=2 * self.Tc, label="t_per_frame")
-            ss = self.f32buf(R * F, tw.shape[0])
-            ops.linear_f32(plan, t_rep, W.f32("timemlp.wt32", lambda: tw.t()), W.f32("timemlp.b32", lambda: tb), ss, act_in=ACT_SILU, label="time_mlps")
-        else:
-            t_rep = self.new(1, 1, R * F, self.Tc)
-            ops.rows_copy(plan, self.t.t, t_rep.t, B=R, rows=F, C=self.Tc, src_bs=self.Tc, src_rs=0, dst_bs=F * self.Tc, dst_rs=self.Tc,
-                          label="t_per_frame")
-            ss = self.new(1, 1, R * F, tw.shape[0])
-            ops.igemm(plan, t_rep, W.raw("timemlp.w", tw, tb), ss, act_in=ACT_SILU, label="time_mlps")
-        self.pa2 = self.f32buf(R * F, total_c)
-        self.ps2 = self.f32buf(R * F, total_c)
-        ops.scale_shift(plan, ss, W.f32("timemlp.gam", lambda: gam), W.get("timemlp.isc", lambda: isc.to(self.dev)),
-                        W.get("timemlp.ish", lambda: ish.to(self.dev)), self.pa2, self.ps2)
+        # ---- time conditioning: the image Unet's (iv.py:1764-1781), one (scale, shift) row per frame, plain fp16 weights
+        self._emit_time_chain(plan, replicas=F, split=False, f32=TIME_CHAIN_F32)
         self._kv_dynamic_anchor = len(plan.ops)
 
         # ---- traversal (iv.py:1751-1941)
@@ -291,43 +255,9 @@ class UnetEngine3D(UnetEngine):
     # ------------------------------------------------------------------------------------------ convolutions
     def _init_conv3d(self, plan) -> Act:
         """CrossEmbedLayer per frame (iv.py:1121-1146) as ONE kmax x kmax conv, or the plain init conv."""
-        u = self.unet
-
-        cc = getattr(u, 'cond_images_channels', 0)
-        sc = u.channels if self.self_cond_in is not None else 0
-        c = u.channels
-        nl = c if self.lowres else 0
-        auxp = self.cimg.C if self.cimg is not None else 0
-
-        def spread(w):
-            """Reference input channels [cond image | x | self_cond | lowres] (iv.py:1676, 1684, 1731), of which at most one of the cond
-            image and self_cond is there -> ours [x | lowres | 0.. (8)] ++ [self_cond or cond image | 0.. (auxp)]."""
-            assert w.shape[1] == cc + c + sc + nl and not (cc and sc)
-            wp = torch.zeros(w.shape[0], 8 + auxp, *w.shape[2:])
-            wp[:, :c] = w[:, cc: cc + c]
-            wp[:, c: c + nl] = w[:, cc + c + sc:]
-            wp[:, 8: 8 + sc] = w[:, c: c + sc]
-            wp[:, 8: 8 + cc] = w[:, :cc]
-            return wp
-
-        def make():
-            if isinstance(u.init_conv, CrossEmbed3dP):
-                kmax = max(u.init_conv.kernel_sizes)
-                ws, bs = [], []
-                for conv, k in zip(u.init_conv.convs, u.init_conv.kernel_sizes):
-                    cw = _w2d(conv)
-                    w = torch.zeros(*cw.weight.shape[:2], kmax, kmax)
-                    p = (kmax - k) // 2
-                    w[:, :, p:p + k, p:p + k] = cw.weight
-                    ws.append(spread(w))
-                    bs.append(cw.bias)
-                return ops.pack_weight(torch.cat(ws), torch.cat(bs), self.dev, G=1)
-            cw = _w2d(u.init_conv)
-            return ops.pack_weight(spread(cw.weight), cw.bias, self.dev, G=1)
-
         out = self.new(self.R * self.F, self.S, self.S, self.lc["init_dim"])
         out.ssq = self.f32buf(out.rows)
-        if not ops.igemm(plan, self.img, self.W.get("init_conv", make), out, x2=self.cimg, ssq_out=out.ssq, label="init_conv").ssq_emitted:
+        if not ops.igemm(plan, self.img, self.W.get("init_conv", lambda: self._init_conv_weight(_wb2d)), out, x2=self.cimg, ssq_out=out.ssq, label="init_conv").ssq_emitted:
             out.ssq = None
         return out
 
@@ -340,16 +270,7 @@ class UnetEngine3D(UnetEngine):
         kh_ = cw.weight.shape[-1]
         split = extra is None and self._split_output(x.C, kh_ * kh_, cw.weight.shape[0], x.rows)
 
-        def make():
-            w = cw.weight
-            co, ci, kh, kw = w.shape
-            if extra is None:
-                return ops.pack_weight(w, cw.bias, self.dev, split=split)
-            wp = torch.zeros(co, x.C + 8, kh, kw)
-            wp[:, : x.C] = w[:, : x.C]
-            wp[:, x.C + u.channels: x.C + 2 * u.channels] = w[:, x.C:]      # packed frame = [x | lowres | zero pad]
-            return ops.pack_weight(wp, cw.bias, self.dev)
-
+        make = lambda: self._final_conv_weight(_wb2d, x.C, extra is not None, split)
         out4 = self.out_full.view(self.R * self.F, u.channels_out, self.S, self.S)
         ops.igemm(plan, x, self.W.get("final_conv|split" if split else "final_conv", make), out4, x2=extra, out_mode=OUT_NCHW_F32, label="final_conv")
         plan.keep.append(self.out_full)

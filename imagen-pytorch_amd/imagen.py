@@ -16,11 +16,12 @@ the reference signature: `noise_fn`,
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 import functools
 import os
 import queue
 import threading
-from typing import Callable, Dict, List, Optional
+from typing import Any, Callable, Dict, List, Optional
 
 import torch
 import torch.nn.functional as F
@@ -94,6 +95,60 @@ class Conditioning:
         self.token = object()
 
 
+@dataclasses.dataclass
+class _Call:
+    """One sample() call: the public keywords as given (the defaults are sample()'s), what the callers inside the package add, and — once
+    `Imagen._resolve` has run — what was resolved from them, in place: `device` a torch.device, `text_embeds` / `text_masks` / `cond_images` on
+    it, `batch_size` the rows, `cond_scale` / `skip_steps` one entry per unet, `init_images` a normalised list, `seed` drawn.  It is handed
+    from `_resolve` to `_prepare_stage` to the stage loop; nothing of a call lives anywhere else."""
+    texts: Any = None
+    text_masks: Any = None
+    text_embeds: Any = None
+    video_frames: Any = None
+    cond_images: Any = None
+    cond_video_frames: Any = None
+    post_cond_video_frames: Any = None
+    inpaint_videos: Any = None
+    inpaint_images: Any = None
+    inpaint_masks: Any = None
+    inpaint_resample_times: int = 5
+    init_images: Any = None
+    skip_steps: Any = None
+    batch_size: int = 1
+    cond_scale: Any = 1.
+    lowres_sample_noise_level: Any = None
+    start_at_unet_number: int = 1
+    start_image_or_video: Any = None
+    stop_at_unet_number: Any = None
+    return_all_unet_outputs: bool = False
+    return_pil_images: bool = False
+    device: Any = None
+    use_tqdm: bool = True
+    use_one_unet_in_gpu: bool = True
+    noise_fn: Optional[Callable] = None
+    seed: Any = None
+    sample_offset: int = 0
+    use_graph: bool = True
+    max_steps: Optional[int] = None
+    conditioning: Optional[Conditioning] = None
+    negative_texts: Any = None
+    negative_text_embeds: Any = None
+    negative_text_masks: Any = None
+    # not public keywords: set by sample_requests, the sample_pipelined workers and ElucidatedImagen._call
+    negative_rows: Optional[torch.Tensor] = None       # bool [rows]: the samples the merged negative prompt applies to
+    pipelined_stage: bool = False                      # one stage of a cascade whose guidance scales sample_pipelined has checked as a whole
+    sigma_overrides: Optional[dict] = None             # ElucidatedImagen.sample(sigma_min=, sigma_max=): one entry per unet each
+    # resolved
+    negative: Optional[tuple] = None                   # the negative prompt as _negative_of_call returns it
+    neg_embeds: Any = None                             # ... resolved and checked (_check_negative)
+    neg_masks: Any = None
+    neg_rows: Any = None
+    frames: int = 0                                    # video_frames of a video cascade, else 0
+    known: Any = None                                  # inpainting: the normalised known image / clip (reference layout) and its mask
+    known_mask: Any = None
+    level: float = 0.                                  # low-res augmentation level
+    img: Any = None                                    # the hand-off image (internal layout, [0, 1]): start_image_or_video, then each stage's output
+
 
 def _seed_spans(seed, batch: int, sample_offset: int = 0):
     """[(Philox seed, first row, rows, global index of the first row)]: an int seed is one span over the whole batch; a list of (seed, rows)
@@ -108,6 +163,8 @@ def _seed_spans(seed, batch: int, sample_offset: int = 0):
     return [(int(seed), 0, batch, sample_offset)]
 
 class Imagen(nn.Module):
+    _lowres_time_raw = False   # the low-res stages are conditioned on the log-SNR of the augmentation level (ip.py:2081), not the level itself
+
     def __init__(
         self,
         unets,
@@ -210,7 +267,7 @@ class Imagen(nn.Module):
         self.to(next(self.unets.parameters()).device)
         self._stages = {}
         self._streams: Dict[tuple, torch.cuda.Stream] = {}   # (lane, device) -> private stream
-        self._tls = threading.local()                        # per-thread: lane index, conditioning handle
+        self._tls = threading.local()                        # per-thread: the lane index, nothing else (a call's state is its _Call record)
         self._mode_lock = threading.Lock()
         self._build_lock = threading.RLock()                 # stage construction (engine plans + shared weight packing) is serialised
         self._mode_depth = 0
@@ -335,11 +392,7 @@ class Imagen(nn.Module):
                 neg_rows = torch.cat([torch.full((b,), n is not None) for n, b in zip(negs, sizes)])
         else:
             kw['batch_size'] = sum(sizes)
-        try:
-            self._tls.negative_rows = neg_rows      # bool [rows]: the samples the merged negative prompt applies to (sample() reads it here)
-            out = self.sample(seed=seeds, **kw)
-        finally:
-            self._tls.negative_rows = None
+        out = self._sample(self._call(seed=seeds, negative_rows=neg_rows, **kw))
         return list(torch.split(out, sizes))
 
     @torch.no_grad()
@@ -385,7 +438,6 @@ class Imagen(nn.Module):
 
         def worker(s: int):
             try:
-                self._tls.pipelined_stage = True         # (this thread's: its sample() calls are single stages of cascades checked above)
                 with self.lane(0x100 + s), torch.cuda.device(self.device):
                     torch.cuda.current_stream().wait_event(ready)
                     while True:
@@ -396,7 +448,8 @@ class Imagen(nn.Module):
                         kw = dict(jobs[k])
                         if s > 0:
                             kw.update(start_at_unet_number=s + 1, start_image_or_video=img)
-                        out = self.sample(**kw, stop_at_unet_number=s + 1)   # returns after this lane's stream has drained
+                        # (pipelined_stage: a single stage of a cascade checked above); returns after this lane's stream has drained
+                        out = self._sample(self._call(**kw, stop_at_unet_number=s + 1, pipelined_stage=True))
                         qs[s + 1].put((k, out))
             except BaseException as e:   # noqa: BLE001 — re-raised in the caller
                 errors.append(e)
@@ -435,24 +488,16 @@ class Imagen(nn.Module):
                 torch.cuda.current_stream().synchronize()
             return st
 
-    def _build_stage(self, idx: int, B: int, device, *, cond_scale: float, with_text: bool, inject_noise: bool, sample_offset: int,
-                     resample_times: int = 0, frames: int = 0, prompt_frames: tuple = (0, 0)):
-        """Build (or fetch) the per-timestep plan + graph of stage `idx` for batch B.
-
-        resample_times = R > 0 selects the inpainting plan (ip.py:2237-2275): the device counter then counts INNER iterations
-        (timestep i, resample r = R-1..0), every coefficient table has one row per inner iteration, and one launch sequence
-        [blend known pixels at level t -> denoiser -> posterior step -> re-noise t_next -> t] serves all of them: the re-noising
-        weights are the identity on the rows where the reference skips it, so a single captured graph covers the whole loop."""
-        unet = self.unets[idx]
-        S = self.image_sizes[idx]
-        sched = self.noise_schedulers[idx]
-        T = sched.num_timesteps
-        cfg = cond_scale != 1.
-        key = (idx, B, S, str(device), float(cond_scale), with_text, inject_noise, sample_offset, self.dynamic_thresholding[idx],
-               self.pred_objectives[idx], self.dynamic_thresholding_percentile, resample_times, frames, prompt_frames, self._lane)
+    def _new_stage(self, key: tuple, idx: int, B: int, device, *, cfg: bool, with_text: bool, inject_noise: bool, sample_offset: int,
+                   resample_times: int, frames: int, prompt_frames: tuple, coef: Callable):
+        """What both samplers' `_build_stage` do first.  Returns (the cached stage of `key`, False) while its engine is not stale; else
+        (a new stage dict, True): the engine (image or video), the device step counter and seed words, the engine bound to `coef()` — the
+        sampler's per-evaluation table, built only now — the per-request time table where it applies, and the buffers every sampler has.
+        EVERY key the run side reads is present (None where unused); the sampler adds its plan(s), tables and buffers and files the stage."""
         st = self._stages.get(key)
         if st is not None and not st['eng'].stale():
-            return st
+            return st, False
+        unet, S, R = self.unets[idx], self.image_sizes[idx], resample_times
         rows = 2 * B if cfg else B
         video = isinstance(unet, Unet3D)
         if video:
@@ -466,39 +511,61 @@ class Imagen(nn.Module):
         else:
             from . import engine
             eng = engine.UnetEngine(unet, rows, B, S, device, with_text=with_text)
-        n = eng.x_in[0].numel()
-        dev = device
-        R = resample_times
-        if R:
-            coef, blend_coef, renoise_coef = (t.to(dev) for t in sched.inpaint_coefficients(R, philox=not inject_noise))
-        else:
-            coef = sched.step_coefficients().to(dev)
-        step_ptr = torch.zeros(1, dtype=torch.int32, device=dev)
-        seed_dev = torch.zeros(2, dtype=torch.int32, device=dev)
-        row_keys = torch.zeros(B, 4, dtype=torch.int32, device=dev)   # (Philox key lo, hi, global sample index, 0) of every row: _run_stage fills it per call
+        step_ptr = torch.zeros(1, dtype=torch.int32, device=device)
+        seed_dev = torch.zeros(2, dtype=torch.int32, device=device)
+        coef = coef()
         eng.bind_step_counter(coef, step_ptr)
-        x0 = torch.empty(B, n, device=dev)
-        absx0 = torch.empty(B, n, device=dev)
-        quant = torch.empty(B, device=dev)
-        scratch = torch.empty(B * ops.ENUMS["IMAGEN_QUANTILE_SCRATCH_WORDS"], dtype=torch.int32, device=dev)
-        noise = torch.empty_like(eng.x_in) if inject_noise else None
-        final = torch.empty_like(eng.x_in)
-        plan = Plan(f"stage{idx}-step")
-        extra = {}
-        if R:
-            known = torch.zeros_like(eng.x_in)           # the known image (video: frame-major clip), normalised, at this stage's size
-            mask = torch.zeros_like(eng.x_in)            # 1.0 where the known pixel is kept
-            noise_blend = torch.zeros_like(known) if inject_noise else None
-            noise_renoise = torch.zeros_like(known) if inject_noise else None
-            ops.lincomb(plan, known, eng.x_in, blend_coef, step_ptr, B=B, n_per_sample=n, t1=noise_blend, mask=mask, mask_else=eng.x_in,
-                        stream_id=idx | 0x100, sample_offset=sample_offset, seed_ptr=seed_dev, label="inpaint.blend")
-            extra = dict(known=known, mask=mask, noise_blend=noise_blend, noise_renoise=noise_renoise)
         # image stages without inpainting resampling: the timestep-only conditioning chain of the denoiser is evaluated for all steps at
-        # once per request (engine.enable_time_table), each step copies its rows
+        # once per request (engine.enable_time_table: the table has one row per evaluation of `coef`), each step copies its rows; the
+        # video engine builds none and keeps the per-step chain
         step_plan = eng.step_plan
-        if TIME_TABLE and not video and not R:
+        if TIME_TABLE and not R:
             step_plan = eng.enable_time_table(coef, step_ptr) or step_plan
-        plan.extend(step_plan)
+        zeros = lambda: torch.zeros_like(eng.x_in)
+        return dict(eng=eng, step_plan=step_plan, plan=None, graph=None, coef=coef, step_ptr=step_ptr, seed_dev=seed_dev,
+                    n=eng.x_in[0].numel(), S=S, R=R, video=video, frames=frames, sample_offset=sample_offset,
+                    noise=torch.empty_like(eng.x_in) if inject_noise else None, final=torch.empty_like(eng.x_in),
+                    # inpainting: the known image (video: frame-major clip), normalised, at this stage's size; 1.0 where it is kept
+                    known=zeros() if R else None, mask=zeros() if R else None,
+                    noise_renoise=zeros() if R and inject_noise else None), True
+
+    def _build_stage(self, idx: int, B: int, device, *, cond_scale: float, with_text: bool, inject_noise: bool, sample_offset: int,
+                     resample_times: int = 0, frames: int = 0, prompt_frames: tuple = (0, 0)):
+        """Build (or fetch) the per-timestep plan + graph of stage `idx` for batch B.
+
+        resample_times = R > 0 selects the inpainting plan (ip.py:2237-2275): the device counter then counts INNER iterations
+        (timestep i, resample r = R-1..0), every coefficient table has one row per inner iteration, and one launch sequence
+        [blend known pixels at level t -> denoiser -> posterior step -> re-noise t_next -> t] serves all of them: the re-noising
+        weights are the identity on the rows where the reference skips it, so a single captured graph covers the whole loop."""
+        unet = self.unets[idx]
+        sched = self.noise_schedulers[idx]
+        T, R = sched.num_timesteps, resample_times
+        cfg = cond_scale != 1.
+        key = (idx, B, self.image_sizes[idx], str(device), float(cond_scale), with_text, inject_noise, sample_offset, self.dynamic_thresholding[idx],
+               self.pred_objectives[idx], self.dynamic_thresholding_percentile, resample_times, frames, prompt_frames, self._lane)
+        tables = []
+
+        def coef():
+            tables[:] = [t.to(device) for t in (sched.inpaint_coefficients(R, philox=not inject_noise) if R else (sched.step_coefficients(),))]
+            return tables[0]
+
+        st, built = self._new_stage(key, idx, B, device, cfg=cfg, with_text=with_text, inject_noise=inject_noise, sample_offset=sample_offset,
+                                    resample_times=R, frames=frames, prompt_frames=prompt_frames, coef=coef)
+        if not built:
+            return st
+        eng, n, coef, step_ptr, seed_dev, noise = st['eng'], st['n'], st['coef'], st['step_ptr'], st['seed_dev'], st['noise']
+        row_keys = torch.zeros(B, 4, dtype=torch.int32, device=device)   # (Philox key lo, hi, global sample index, 0) of every row: _run_stage fills it per call
+        x0 = torch.empty(B, n, device=device)
+        absx0 = torch.empty(B, n, device=device)
+        quant = torch.empty(B, device=device)
+        scratch = torch.empty(B * ops.ENUMS["IMAGEN_QUANTILE_SCRATCH_WORDS"], dtype=torch.int32, device=device)
+        plan = Plan(f"stage{idx}-step")
+        noise_blend = None
+        if R:
+            noise_blend = torch.zeros_like(eng.x_in) if inject_noise else None
+            ops.lincomb(plan, st['known'], eng.x_in, tables[1], step_ptr, B=B, n_per_sample=n, t1=noise_blend, mask=st['mask'], mask_else=eng.x_in,
+                        stream_id=idx | 0x100, sample_offset=sample_offset, seed_ptr=seed_dev, label="inpaint.blend")
+        plan.extend(st['step_plan'])
         ops.cfg_x0(plan, eng.x_in, eng.out, coef, step_ptr, x0, absx0, B=B, n_per_sample=n, cfg=cfg, cond_scale=float(cond_scale),
                    objective=self.pred_objectives[idx])
         dyn = bool(self.dynamic_thresholding[idx])
@@ -506,19 +573,40 @@ class Imagen(nn.Module):
             ops.quantile(plan, absx0, quant, scratch, B=B, n=n, q=float(self.dynamic_thresholding_percentile))
         x0_thr = None
         if getattr(unet, 'self_cond', False):            # ip.py:2249: each step conditions on the previous step's thresholded x0
-            x0_thr = torch.zeros(B, n, device=dev)       # (video: the frame-major clip, as the state)
+            x0_thr = torch.zeros(B, n, device=device)    # (video: the frame-major clip, as the state)
             eng.bind_self_cond(x0_thr)
-            extra['x0_thr'] = x0_thr
-        ops.ddpm_update(plan, eng.x_in, x0, quant if dyn else None, coef, noise, final, step_ptr, B=B, n_per_sample=n,
+        ops.ddpm_update(plan, eng.x_in, x0, quant if dyn else None, coef, noise, st['final'], step_ptr, B=B, n_per_sample=n,
                         dynamic_threshold=dyn, total_steps=T * max(R, 1), seed=0, stream_id=idx, sample_offset=sample_offset,
                         seed_ptr=seed_dev, advance=not R, x0_thr=x0_thr, row_keys=None if inject_noise else row_keys)
         if R:
-            ops.lincomb(plan, eng.x_in, eng.x_in, renoise_coef, step_ptr, B=B, n_per_sample=n, t1=extra['noise_renoise'], advance=True,
+            ops.lincomb(plan, eng.x_in, eng.x_in, tables[2], step_ptr, B=B, n_per_sample=n, t1=st['noise_renoise'], advance=True,
                         stream_id=idx | 0x200, sample_offset=sample_offset, seed_ptr=seed_dev, label="inpaint.renoise")
-        st = dict(eng=eng, plan=plan, graph=None, coef=coef, step_ptr=step_ptr, seed_dev=seed_dev, row_keys=row_keys, noise=noise, final=final, T=T, S=S,
-                  quant=quant, x0=x0, R=R, video=video, frames=frames, **extra)
+        st.update(plan=plan, T=T, row_keys=row_keys, quant=quant, x0=x0, x0_thr=x0_thr, noise_blend=noise_blend)
         self._stages[key] = st
         return st
+
+    # ---- what both samplers' `_run_stage` share
+    @staticmethod
+    def _draw(st, noise_fn, tag, like):
+        """Injected Gaussian draw for the internal buffer `like`; videos are drawn in the reference's (b, c, f, h, w) layout."""
+        if not st['video']:
+            return noise_fn(tag, tuple(like.shape))
+        b, f, c, h, w = like.shape
+        return noise_fn(tag, (b, c, f, h, w)).permute(0, 2, 1, 3, 4)
+
+    @staticmethod
+    def _seed_words(seed: int) -> tuple:
+        """A Philox key as the two 31-bit words the kernels take (seed_ptr, row_keys)."""
+        return seed & 0x7FFFFFFF, (seed >> 31) & 0x7FFFFFFF
+
+    @staticmethod
+    def _stage_output(st, state, complete: bool):
+        """The stage's [0, 1] result: what the last step's kernel wrote, or — a truncated loop (tests) — the same epilogue on the state
+        (ip.py:2281-2288, el.py:540-545); then the paste of the known pixels (ip.py:2283-2288, el.py:542-545)."""
+        out = st['final'] if complete else (state.clamp(-1., 1.) + 1) * 0.5
+        if st['R']:
+            out = torch.where(st['mask'] != 0, (st['known'] + 1) * 0.5, out)
+        return out
 
     @torch.no_grad()
     def _run_stage(self, st, *, noise_fn: Optional[Callable], stage: int, seed: int, use_graph: bool = True, use_tqdm: bool = False,
@@ -528,26 +616,18 @@ class Imagen(nn.Module):
         `inpaint_resample_times` times when st is an inpainting plan), clamp + unnormalise (done by the last step's kernel) and
         the final paste of the known pixels."""
         eng, plan, T, R = st['eng'], st['plan'], st['T'], st['R']
-        B, S = eng.src_batch, st['S']
+        B = eng.src_batch
         stream = torch.cuda.current_stream()
         skip = skip_steps or 0
         assert 0 <= skip < T, 'skip_steps must leave at least one timestep'
         inner = max(R, 1)
         init = None
-        spans = _seed_spans(seed, B, st.get('sample_offset', 0))
+        spans = _seed_spans(seed, B, st['sample_offset'])
         if noise_fn is None:
             init = Plan("init-noise")
             for sd, r0, cnt, i0 in spans:               # (one span per merged request: its own key, its own sample indices)
                 ops.randn(init, eng.x_in[r0:r0 + cnt], seed=sd, stream_id=stage, tag=TAG_INIT, sample_offset=i0)
-
-        video = st.get('video', False)
-
-        def draw(tag, like):
-            """Injected Gaussian draw for the internal buffer `like`; videos are drawn in the reference's (b, c, f, h, w) layout."""
-            if not video:
-                return noise_fn(tag, tuple(like.shape))
-            b, f, c, h, w = like.shape
-            return noise_fn(tag, (b, c, f, h, w)).permute(0, 2, 1, 3, 4)
+        draw = functools.partial(self._draw, st, noise_fn)
 
         def reset_state():
             if noise_fn is not None:
@@ -556,16 +636,16 @@ class Imagen(nn.Module):
                 init.run()
             if init_images is not None:
                 eng.x_in.add_(init_images)              # ip.py:2205-2206
-            if st.get('x0_thr') is not None:
+            if st['x0_thr'] is not None:
                 st['x0_thr'].zero_()                    # no x0 estimate yet: the first step self-conditions on zeros (ip.py:2210, 1542)
             st['step_ptr'].fill_(skip * inner)           # ip.py:2228-2229: the skipped timesteps are simply never run
 
         reset_state()
         assert not (R and len(spans) > 1), 'merged requests do not cover inpainting (its re-noising launches take one key per batch)'
-        st['seed_dev'].copy_(torch.tensor([spans[0][0] & 0x7FFFFFFF, (spans[0][0] >> 31) & 0x7FFFFFFF], dtype=torch.int32))
+        st['seed_dev'].copy_(torch.tensor(self._seed_words(spans[0][0]), dtype=torch.int32))
         keys = torch.zeros(B, 4, dtype=torch.int64)
         for sd, r0, cnt, i0 in spans:
-            keys[r0:r0 + cnt, 0], keys[r0:r0 + cnt, 1] = sd & 0x7FFFFFFF, (sd >> 31) & 0x7FFFFFFF
+            keys[r0:r0 + cnt, 0], keys[r0:r0 + cnt, 1] = self._seed_words(sd)
             keys[r0:r0 + cnt, 2] = torch.arange(i0, i0 + cnt)
         st['row_keys'].copy_(keys.to(torch.int32))
         steps = T - skip if max_steps is None else min(T - skip, max_steps)
@@ -597,13 +677,7 @@ class Imagen(nn.Module):
                     plan.run()
                 if trace is not None:
                     trace.append(eng.x_in.clone())
-        if skip + steps == T:
-            out = st['final']
-        else:
-            out = (eng.x_in.clamp(-1., 1.) + 1) * 0.5    # truncated loop (tests): same epilogue as ip.py:2281-2288
-        if R:
-            out = torch.where(st['mask'] != 0, (st['known'] + 1) * 0.5, out)   # ip.py:2283-2288
-        return out
+        return self._stage_output(st, eng.x_in, skip + steps == T)
 
     # ---- the reference's step-level sampler methods (ip.py:2042-2289) ------------------------------------------------------
     # `sample()` below runs a whole stage as one captured graph per timestep and never calls these.  They are the reference's
@@ -756,28 +830,15 @@ class Imagen(nn.Module):
         negative_text_embeds=None,                     #   every guided evaluation is neg + (pos - neg) * cond_scale
         negative_text_masks=None,
     ):
-        with self._eval_mode():
-            try:
-                self._tls.conditioning = conditioning
-                self._tls.negative = self._negative_of_call(conditioning, negative_texts, negative_text_embeds, negative_text_masks)
-                if conditioning is not None:
-                    assert texts is None and text_embeds is None and text_masks is None, 'pass either `conditioning` or texts / text_embeds'
-                    text_embeds, text_masks = conditioning.text_embeds, conditioning.text_masks
-                    if text_embeds is None:
-                        batch_size = conditioning.batch_size
-                return self._sample(texts, text_masks, text_embeds, video_frames, cond_images, cond_video_frames, post_cond_video_frames,
-                                    inpaint_videos, inpaint_images, inpaint_masks, inpaint_resample_times, init_images, skip_steps, batch_size,
-                                    cond_scale, lowres_sample_noise_level, start_at_unet_number, start_image_or_video, stop_at_unet_number,
-                                    return_all_unet_outputs, return_pil_images, device, use_tqdm, noise_fn, seed, sample_offset, use_graph,
-                                    max_steps)
-            finally:
-                self._tls.conditioning = None
-                self._tls.negative = None
+        return self._sample(self._call(**{k: v for k, v in locals().items() if k != 'self'}))   # (the keywords, as given)
 
-    def _negative_of_call(self, conditioning, negative_texts, negative_text_embeds, negative_text_masks):
-        """The negative prompt of one sample() call as given — by keyword, or on the conditioning handle — for _sample, which resolves and
+    def _call(self, **kw) -> _Call:
+        """The record of one call from sample()'s keywords (+ the private ones of _Call)."""
+        return _Call(**kw)
+
+    def _negative_of_call(self, conditioning, negative_texts, negative_text_embeds, negative_text_masks, negative_rows=None):
+        """The negative prompt of one sample() call as given — by keyword, or on the conditioning handle — for _resolve, which resolves and
         checks it once the batch and the guidance scales are known.  (The fourth entry, the samples it applies to, is sample_requests'.)"""
-        negative_rows = getattr(self._tls, 'negative_rows', None)
         given = negative_texts is not None or negative_text_embeds is not None or negative_text_masks is not None
         if conditioning is not None:
             if given:
@@ -849,37 +910,57 @@ class Imagen(nn.Module):
                                                 batch=None if text_embeds is None else text_embeds.shape[0])
         return Conditioning(text_embeds, text_masks, text_embeds.shape[0] if text_embeds is not None else batch_size, neg, neg_masks)
 
-    def _sample(self, texts, text_masks, text_embeds, video_frames, cond_images, cond_video_frames, post_cond_video_frames,
-                inpaint_videos, inpaint_images, inpaint_masks, inpaint_resample_times, init_images, skip_steps, batch_size, cond_scale,
-                lowres_sample_noise_level, start_at_unet_number, start_image_or_video, stop_at_unet_number, return_all_unet_outputs,
-                return_pil_images, device, use_tqdm, noise_fn, seed, sample_offset, use_graph, max_steps):
-        device = torch.device(device) if device is not None else self.device
+    # ---- one call: resolve (nothing is built or launched) -> per stage: prepare, run --------------------------------------------
+    def _to_internal(self, t):
+        """(b, c, f, h, w) <-> (b, f, c, h, w) of a video cascade (the permutation is its own inverse); images as they are."""
+        return t.permute(0, 2, 1, 3, 4).contiguous() if self.is_video else t
+
+    def _resize(self, im, size):
+        return im if im.shape[-1] == size else F.interpolate(im, size, mode=self.resize_mode)     # ip.py:152-168, 1924
+
+    def _resize_clip(self, v, size, f):
+        """resize_video_to (iv.py:134-156) of a (b, c, f', h, w) clip to f frames of size x size — nearest over all three axes —
+        returned in the internal frame-major layout."""
+        if tuple(v.shape[-3:]) != (f, size, size):
+            v = F.interpolate(v, (f, size, size), mode='nearest')
+        return self._to_internal(v)
+
+    def _resolve(self, c: _Call) -> _Call:
+        """Everything of sample() (ip.py:2291-2404) up to the stage loop, written back into the record: device, text, batch size, inpainting
+        inputs, the per-unet tuples, the seed, the negative prompt with its refusals, the start image.  Builds no stage and launches nothing."""
+        c.negative = self._negative_of_call(c.conditioning, c.negative_texts, c.negative_text_embeds, c.negative_text_masks, c.negative_rows)
+        if c.conditioning is not None:
+            assert c.texts is None and c.text_embeds is None and c.text_masks is None, 'pass either `conditioning` or texts / text_embeds'
+            c.text_embeds, c.text_masks = c.conditioning.text_embeds, c.conditioning.text_masks
+            if c.text_embeds is None:
+                c.batch_size = c.conditioning.batch_size
+        device = c.device = torch.device(c.device) if c.device is not None else self.device
         if device.type not in _SAMPLING_DEVICE_TYPES:
             raise RuntimeError("imagen_pytorch_amd.Imagen.sample runs on MI355X only (move the module to 'cuda'); there is no CPU path")
         self.reset_unets_all_one_device(device)
-        if inpaint_videos is not None:                   # ip.py:2342: the video argument wins
-            inpaint_images = inpaint_videos
+        if c.inpaint_videos is not None:                 # ip.py:2342: the video argument wins
+            c.inpaint_images = c.inpaint_videos
         if not self.is_video:                            # ip.py:2417-2427: only video cascades hand the prompt frames to their unets
-            cond_video_frames = post_cond_video_frames = None
-        if cond_images is not None:
-            cond_images = cond_images.to(device)
-            if cond_images.dtype == torch.uint8:         # cast_uint8_images_to_float, ip.py:2324
-                cond_images = cond_images.float() / 255
-        assert not (self.is_video and video_frames is None), 'video_frames must be passed in on sample time if training on video'   # ip.py:2381
+            c.cond_video_frames = c.post_cond_video_frames = None
+        if c.cond_images is not None:
+            c.cond_images = c.cond_images.to(device)
+            if c.cond_images.dtype == torch.uint8:       # cast_uint8_images_to_float, ip.py:2324
+                c.cond_images = c.cond_images.float() / 255
+        assert not (self.is_video and c.video_frames is None), 'video_frames must be passed in on sample time if training on video'   # ip.py:2381
         if self.is_video:
             for f in self.temporal_downsample_factor:                       # calc_all_frame_dims, ip.py:170-183
-                assert int(video_frames) % f == 0, f'video_frames {video_frames} must be divisible by the temporal downsample factor {f}'
-        frames = int(video_frames) if self.is_video else 0
-        to_internal = (lambda t: t.permute(0, 2, 1, 3, 4).contiguous()) if self.is_video else (lambda t: t)   # (b,c,f,h,w) <-> (b,f,c,h,w)
-        assert not (return_pil_images and self.is_video), 'converting sampled video tensor to video file is not supported yet'   # ip.py:2494
+                assert int(c.video_frames) % f == 0, f'video_frames {c.video_frames} must be divisible by the temporal downsample factor {f}'
+        c.frames = int(c.video_frames) if self.is_video else 0
+        assert not (c.return_pil_images and self.is_video), 'converting sampled video tensor to video file is not supported yet'   # ip.py:2494
 
-        text_embeds, text_masks = self._resolve_text(texts, text_embeds, text_masks, device)
+        c.text_embeds, c.text_masks = self._resolve_text(c.texts, c.text_embeds, c.text_masks, device)
+        text_embeds, inpaint_images = c.text_embeds, c.inpaint_images
         if not self.unconditional:
-            batch_size = text_embeds.shape[0]
+            c.batch_size = text_embeds.shape[0]
         if inpaint_images is not None:                   # ip.py:2344-2351
-            if self.unconditional and batch_size == 1:
-                batch_size = inpaint_images.shape[0]
-            assert inpaint_images.shape[0] == batch_size, \
+            if self.unconditional and c.batch_size == 1:
+                c.batch_size = inpaint_images.shape[0]
+            assert inpaint_images.shape[0] == c.batch_size, \
                 'number of inpainting images must be equal to the specified batch size on sample `sample(batch_size=<int>)``'
             assert not (self.condition_on_text and inpaint_images.shape[0] != text_embeds.shape[0]), \
                 'number of inpainting images must be equal to the number of text to be conditioned on'
@@ -888,173 +969,168 @@ class Imagen(nn.Module):
         assert not (text_embeds is not None and text_embeds.shape[-1] != self.text_embed_dim), \
             f'invalid text embedding dimension being passed in (should be {self.text_embed_dim})'
 
-        assert not ((inpaint_images is not None) ^ (inpaint_masks is not None)), \
+        assert not ((inpaint_images is not None) ^ (c.inpaint_masks is not None)), \
             'inpaint images and masks must be both passed in to do inpainting'
         num_unets = len(self.unets)
-        normalize = (lambda im: im * 2 - 1) if self.auto_normalize_img else (lambda im: im)             # ip.py:1885-1888
         assert not (self.is_video and self.resize_mode != 'nearest'), 'video cascades resize with nearest only in this build'
-        resize = lambda im, size: im if im.shape[-1] == size else F.interpolate(im, size, mode=self.resize_mode)   # ip.py:152-168, 1924
-
-        def resize_clip(v, size, f):
-            """resize_video_to (iv.py:134-156) of a (b, c, f', h, w) clip to f frames of size x size — nearest over all three axes —
-            returned in the internal frame-major layout."""
-            if tuple(v.shape[-3:]) != (f, size, size):
-                v = F.interpolate(v, (f, size, size), mode='nearest')
-            return to_internal(v)
-
-        known = known_mask = None
         if inpaint_images is not None:                   # ip.py:2217-2220
-            known = normalize(inpaint_images.to(device).float())
-            known_mask = inpaint_masks.to(device)
+            c.known = self.normalize_img(inpaint_images.to(device).float())
+            known_mask = c.inpaint_masks.to(device)
             if self.is_video:                            # ip.py:2373-2379
-                assert known.ndim == 5, 'inpaint_videos must be (b, c, f, h, w)'
+                assert c.known.ndim == 5, 'inpaint_videos must be (b, c, f, h, w)'
                 if known_mask.ndim == 3:
-                    known_mask = known_mask[:, None].expand(-1, frames, -1, -1)
-                assert known_mask.shape[1] == frames
-            known_mask = known_mask[:, None].float()
-        init_images = [None if im is None else normalize(im.to(device).float()) for im in _cast_tuple(init_images, num_unets)]  # ip.py:2390-2391
-        skip_steps = _cast_tuple(skip_steps, num_unets)
-        level = lowres_sample_noise_level if lowres_sample_noise_level is not None else self.lowres_sample_noise_level
-        cond_scale = _cast_tuple(cond_scale, num_unets)
-        if seed is None:
-            seed = self._next_seed()
+                    known_mask = known_mask[:, None].expand(-1, c.frames, -1, -1)
+                assert known_mask.shape[1] == c.frames
+            c.known_mask = known_mask[:, None].float()
+        c.init_images = [None if im is None else self.normalize_img(im.to(device).float()) for im in _cast_tuple(c.init_images, num_unets)]  # ip.py:2390-2391
+        c.skip_steps = _cast_tuple(c.skip_steps, num_unets)
+        c.level = c.lowres_sample_noise_level if c.lowres_sample_noise_level is not None else self.lowres_sample_noise_level
+        c.cond_scale = _cast_tuple(c.cond_scale, num_unets)
+        if c.seed is None:
+            c.seed = self._next_seed()
         # the negative prompt of this call: resolved and checked here, before any stage is built or anything is launched
-        neg_embeds = neg_masks = neg_rows = None
-        negative = getattr(self._tls, 'negative', None)
-        if negative is not None:
-            last = num_unets if stop_at_unet_number is None else stop_at_unet_number
-            scales = None if getattr(self._tls, 'pipelined_stage', False) else cond_scale[start_at_unet_number - 1:last]
-            neg_embeds, neg_masks, neg_rows = self._check_negative(negative, batch_size, scales, device)
+        if c.negative is not None:
+            last = num_unets if c.stop_at_unet_number is None else c.stop_at_unet_number
+            scales = None if c.pipelined_stage else c.cond_scale[c.start_at_unet_number - 1:last]
+            c.neg_embeds, c.neg_masks, c.neg_rows = self._check_negative(c.negative, c.batch_size, scales, device)
 
-        img = None
-        if start_at_unet_number > 1:
-            assert start_at_unet_number <= num_unets, 'must start a unet that is less than the total number of unets'
-            assert stop_at_unet_number is None or start_at_unet_number <= stop_at_unet_number
-            assert start_image_or_video is not None, 'starting image or video must be supplied if only doing upscaling'
-            img = to_internal(start_image_or_video.to(device).float()).contiguous()
-            prev_size = self.image_sizes[start_at_unet_number - 2]
+        if c.start_at_unet_number > 1:
+            assert c.start_at_unet_number <= num_unets, 'must start a unet that is less than the total number of unets'
+            assert c.stop_at_unet_number is None or c.start_at_unet_number <= c.stop_at_unet_number
+            assert c.start_image_or_video is not None, 'starting image or video must be supplied if only doing upscaling'
+            img = self._to_internal(c.start_image_or_video.to(device).float()).contiguous()
+            prev_size = self.image_sizes[c.start_at_unet_number - 2]
             assert img.shape[-3] == self.channels, f'start image must have {self.channels} channels'
             if img.shape[-1] != prev_size:               # ip.py:2400-2404: first to the PREVIOUS stage's size (lowres_prep then resizes to this one's)
                 lead = img.shape[:-3]
-                img = resize(img.reshape(-1, *img.shape[-3:]), prev_size).reshape(*lead, self.channels, prev_size, prev_size).contiguous()
+                img = self._resize(img.reshape(-1, *img.shape[-3:]), prev_size).reshape(*lead, self.channels, prev_size, prev_size).contiguous()
+            c.img = img
+        return c
 
-        stream = self._streams.get((self._lane, str(device)))
-        if stream is None:
-            stream = self._streams[(self._lane, str(device))] = torch.cuda.Stream(device=device)
-        outputs = []
-        # inputs were produced on the caller's stream: order this lane's stream behind it (no device-wide drain — other lanes keep running)
-        stream.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.device(device), torch.cuda.stream(stream):
-            for idx in range(num_unets):
-                unet_number = idx + 1
-                if unet_number < start_at_unet_number:
-                    continue
-                unet = self.unets[idx]
-                assert not isinstance(unet, NullUnet), 'one cannot sample from null / placeholder unets'
-                cs = cond_scale[idx]
-                assert not (cs != 1. and not self.can_classifier_guidance), \
-                    'imagen was not trained with conditional dropout, and thus one cannot use classifier free guidance (cond_scale anything other than 1)'
-                with_text = text_embeds is not None and unet.cond_on_text
-                prompts = [None, None]
-                if isinstance(unet, Unet3D):                # ip.py:2417-2434: the same prompt frames for every stage, at the stage's frame rate
-                    tds = self.temporal_downsample_factor[idx]
-                    for k, v in enumerate((cond_video_frames, post_cond_video_frames)):
-                        if v is not None and self.resize_cond_video_frames and tds != 1:     # scale_video_time, iv.py:158-178
-                            assert v.shape[2] % tds == 0, f'trying to temporally downsample a conditioning video frames of length ' \
-                                                          f'{v.shape[2]} by {tds}, however it is not neatly divisible'
-                            v = F.interpolate(v.float(), (v.shape[2] // tds, v.shape[-2], v.shape[-1]), mode='nearest')
-                        prompts[k] = v
-                st = self._stage(idx, batch_size, device, cond_scale=cs, with_text=with_text, inject_noise=noise_fn is not None,
-                                 sample_offset=sample_offset, resample_times=inpaint_resample_times if known is not None else 0,
-                                 frames=frames // self.temporal_downsample_factor[idx] if isinstance(unet, Unet3D) else 0,
-                                 prompt_frames=tuple(0 if v is None else v.shape[2] for v in prompts))
-                st['sample_offset'] = sample_offset
-                eng = st['eng']
-                S = self.image_sizes[idx]
-                assert not (getattr(unet, 'has_cond_image', False) ^ (cond_images is not None)), \
-                    'you either requested to condition on an image on the unet, but the conditioning image is not supplied, or vice versa'   # ip.py:1555
-                if cond_images is not None:
-                    eng.set_cond_images(cond_images)
-                if prompts[0] is not None or prompts[1] is not None:
-                    eng.set_cond_video_frames(*prompts)
-                stage_frames = st['frames']
-                if known is not None and st['video']:
-                    st['known'].copy_(resize_clip(known, S, stage_frames))
-                    st['mask'].copy_(resize_clip(known_mask, S, stage_frames).bool().expand(-1, -1, self.channels, -1, -1))
-                elif known is not None:
-                    st['known'].copy_(resize(known, S))
-                    st['mask'].copy_(resize(known_mask, S).bool().expand(-1, self.channels, -1, -1))
-                lowres_logsnr = None
-                if unet.lowres_cond:
-                    assert img is not None
-                    a, s, lsnr = self.lowres_noise_schedule.q_sample_coefficients(level)
-                    # Imagen conditions on the log-SNR of the augmentation level (ip.py:2081); ElucidatedImagen.sample passes the
-                    # raw level (elucidated_imagen.py:700, 728) — `_lowres_time_raw` is set by that subclass
-                    lowres_logsnr = torch.full((batch_size,), level if getattr(self, "_lowres_time_raw", False) else lsnr, dtype=torch.float32)
-                    aug = torch.empty_like(eng.lowres_in)
-                    if noise_fn is not None:
-                        if st.get('video', False):
-                            b_, f_, c_, h_, w_ = aug.shape
-                            aug.copy_(noise_fn(("lowres", idx), (b_, c_, f_, h_, w_)).permute(0, 2, 1, 3, 4))
-                        else:
-                            aug.copy_(noise_fn(("lowres", idx), tuple(aug.shape)))
-                    prep = Plan("lowres-prep")
-                    if noise_fn is None:
-                        for sd, r0, cnt, i0 in _seed_spans(seed, batch_size, sample_offset):
-                            ops.randn(prep, aug[r0:r0 + cnt], seed=sd, stream_id=idx, tag=TAG_LOWRES, sample_offset=i0)
-                    src = img if self.auto_normalize_img else (img + 1) * 0.5                  # kernel normalises [0,1] -> [-1,1]
-                    if st.get('video', False) and src.shape[1] != aug.shape[1]:
-                        # a stage sampled at a lower frame rate feeds this one: nearest over the frame axis (resize_video_to,
-                        # iv.py:134-156); once per stage
-                        src = src[:, nearest_indices(src.shape[1], aug.shape[1]).to(src.device)]
-                    if self.resize_mode != 'nearest' and src.shape[-1] != S:
-                        # LOWRES_PREP resizes with nearest in-kernel; any other mode is resized here, once per stage, and the kernel's
-                        # own resize becomes the identity.  The resize acts on the [0, 1] image as in ip.py:2444-2446 (normalisation after).
-                        src = resize(img, S) if self.auto_normalize_img else (resize(img, S) + 1) * 0.5
-                    src = src.contiguous()
-                    # frames are independent images for the nearest resize (resize_video_to with unchanged frame count, iv.py:134-156)
-                    as_images = lambda t: t.reshape(-1, *t.shape[-3:])
-                    ops.lowres_prep(prep, as_images(src), as_images(aug), as_images(eng.lowres_in), alpha=a, sigma=s)
-                    prep.keep += [src, aug, eng.lowres_in]
-                    prep.run()
-                rows = eng.R
-                keep = torch.ones(rows, dtype=torch.bool)
-                if rows == 2 * batch_size:
-                    keep[batch_size:] = False            # second half = null-conditioned CFG branch (cond_drop_prob = 1, ip.py:1521)
-                cond = getattr(self._tls, 'conditioning', None)
-                stamp = None if cond is None else (cond.token, None if lowres_logsnr is None else float(lowres_logsnr[0]))
-                if stamp is None or getattr(eng, '_cond_stamp', None) != stamp:
-                    neg_kw = {}
-                    if neg_embeds is not None and with_text and rows == 2 * batch_size:     # (a stage at cond_scale 1 has no null rows)
-                        neg_kw = dict(negative_text_embeds=neg_embeds, negative_text_mask=neg_masks, negative_rows=neg_rows)
-                    eng.set_conditioning(text_embeds=text_embeds if with_text else None, text_mask=text_masks if with_text else None,
-                                         keep=keep, lowres_noise_times=lowres_logsnr, **neg_kw)
-                    eng.static_runs = getattr(eng, 'static_runs', 0) + 1
-                eng._cond_stamp = stamp
-                timing = os.environ.get("IMAGEN_TIMING")
-                if timing:
-                    stream.synchronize()
-                    import time as _time
-                    t_stage = _time.perf_counter()
-                out = self._run_stage(st, noise_fn=noise_fn, stage=idx, seed=seed, use_graph=use_graph, use_tqdm=use_tqdm,
-                                         max_steps=max_steps, skip_steps=skip_steps[idx],
-                                         init_images=None if init_images[idx] is None else
-                                         (resize_clip(init_images[idx], S, stage_frames) if st['video'] else resize(init_images[idx], S)))
-                if timing:
-                    stream.synchronize()
-                    dt = _time.perf_counter() - t_stage
-                    self.last_stage_seconds = getattr(self, "last_stage_seconds", {})
-                    self.last_stage_seconds[idx] = dt
-                    print(f"[imagen] stage {idx} ({S}x{S}, rows {eng.R}): {dt * 1e3:.1f} ms for {st['T'] if max_steps is None else min(st['T'], max_steps)} steps "
-                          f"({len(st['plan'])} launches/step)", flush=True, file=__import__('sys').stderr)
-                img = out.clone()                    # internal layout (videos: frame-major), feeds the next stage's low-res conditioning
-                if not self.auto_normalize_img:
-                    img = img * 2 - 1
-                outputs.append(to_internal(img) if st.get('video', False) else img)   # the permutation is its own inverse
-                if stop_at_unet_number is not None and stop_at_unet_number == unet_number:
-                    break
-        stream.synchronize()
-        if return_pil_images:                                # ip.py:2488-2498: a list of PIL images (one list per unet with return_all_unet_outputs)
-            pil = [_to_pil_images(o) for o in (outputs if return_all_unet_outputs else outputs[-1:])]
-            return pil if return_all_unet_outputs else pil[-1]
-        return outputs if return_all_unet_outputs else outputs[-1]
+    def _prepare_stage(self, c: _Call, idx: int) -> dict:
+        """Stage `idx` made ready for `_run_stage`: the prompt frames at its frame rate, the stage itself (built or fetched), its conditioning
+        images / frames, the known pixels at its size, the augmented low-res image (one launch sequence) and the static conditioning plan."""
+        unet, device, batch_size, noise_fn = self.unets[idx], c.device, c.batch_size, c.noise_fn
+        assert not isinstance(unet, NullUnet), 'one cannot sample from null / placeholder unets'
+        cs = c.cond_scale[idx]
+        assert not (cs != 1. and not self.can_classifier_guidance), \
+            'imagen was not trained with conditional dropout, and thus one cannot use classifier free guidance (cond_scale anything other than 1)'
+        with_text = c.text_embeds is not None and unet.cond_on_text
+        prompts = [None, None]
+        if isinstance(unet, Unet3D):                # ip.py:2417-2434: the same prompt frames for every stage, at the stage's frame rate
+            tds = self.temporal_downsample_factor[idx]
+            for k, v in enumerate((c.cond_video_frames, c.post_cond_video_frames)):
+                if v is not None and self.resize_cond_video_frames and tds != 1:     # scale_video_time, iv.py:158-178
+                    assert v.shape[2] % tds == 0, f'trying to temporally downsample a conditioning video frames of length ' \
+                                                  f'{v.shape[2]} by {tds}, however it is not neatly divisible'
+                    v = F.interpolate(v.float(), (v.shape[2] // tds, v.shape[-2], v.shape[-1]), mode='nearest')
+                prompts[k] = v
+        extra = {} if c.sigma_overrides is None else dict(sigma_overrides=c.sigma_overrides)
+        st = self._stage(idx, batch_size, device, cond_scale=cs, with_text=with_text, inject_noise=noise_fn is not None,
+                         sample_offset=c.sample_offset, resample_times=c.inpaint_resample_times if c.known is not None else 0,
+                         frames=c.frames // self.temporal_downsample_factor[idx] if isinstance(unet, Unet3D) else 0,
+                         prompt_frames=tuple(0 if v is None else v.shape[2] for v in prompts), **extra)
+        eng = st['eng']
+        S = st['S']
+        assert not (getattr(unet, 'has_cond_image', False) ^ (c.cond_images is not None)), \
+            'you either requested to condition on an image on the unet, but the conditioning image is not supplied, or vice versa'   # ip.py:1555
+        if c.cond_images is not None:
+            eng.set_cond_images(c.cond_images)
+        if prompts[0] is not None or prompts[1] is not None:
+            eng.set_cond_video_frames(*prompts)
+        if c.known is not None and st['video']:
+            st['known'].copy_(self._resize_clip(c.known, S, st['frames']))
+            st['mask'].copy_(self._resize_clip(c.known_mask, S, st['frames']).bool().expand(-1, -1, self.channels, -1, -1))
+        elif c.known is not None:
+            st['known'].copy_(self._resize(c.known, S))
+            st['mask'].copy_(self._resize(c.known_mask, S).bool().expand(-1, self.channels, -1, -1))
+        lowres_logsnr = None
+        if unet.lowres_cond:
+            img = c.img
+            assert img is not None
+            a, s, lsnr = self.lowres_noise_schedule.q_sample_coefficients(c.level)
+            # Imagen conditions on the log-SNR of the augmentation level (ip.py:2081); ElucidatedImagen.sample passes the
+            # raw level (elucidated_imagen.py:700, 728): `_lowres_time_raw`
+            lowres_logsnr = torch.full((batch_size,), c.level if self._lowres_time_raw else lsnr, dtype=torch.float32)
+            aug = torch.empty_like(eng.lowres_in)
+            if noise_fn is not None:
+                aug.copy_(self._draw(st, noise_fn, ("lowres", idx), aug))
+            prep = Plan("lowres-prep")
+            if noise_fn is None:
+                for sd, r0, cnt, i0 in _seed_spans(c.seed, batch_size, c.sample_offset):
+                    ops.randn(prep, aug[r0:r0 + cnt], seed=sd, stream_id=idx, tag=TAG_LOWRES, sample_offset=i0)
+            src = img if self.auto_normalize_img else (img + 1) * 0.5                  # kernel normalises [0,1] -> [-1,1]
+            if st['video'] and src.shape[1] != aug.shape[1]:
+                # a stage sampled at a lower frame rate feeds this one: nearest over the frame axis (resize_video_to,
+                # iv.py:134-156); once per stage
+                src = src[:, nearest_indices(src.shape[1], aug.shape[1]).to(src.device)]
+            if self.resize_mode != 'nearest' and src.shape[-1] != S:
+                # LOWRES_PREP resizes with nearest in-kernel; any other mode is resized here, once per stage, and the kernel's
+                # own resize becomes the identity.  The resize acts on the [0, 1] image as in ip.py:2444-2446 (normalisation after).
+                src = self._resize(img, S) if self.auto_normalize_img else (self._resize(img, S) + 1) * 0.5
+            src = src.contiguous()
+            # frames are independent images for the nearest resize (resize_video_to with unchanged frame count, iv.py:134-156)
+            as_images = lambda t: t.reshape(-1, *t.shape[-3:])
+            ops.lowres_prep(prep, as_images(src), as_images(aug), as_images(eng.lowres_in), alpha=a, sigma=s)
+            prep.keep += [src, aug, eng.lowres_in]
+            prep.run()
+        rows = eng.R
+        keep = torch.ones(rows, dtype=torch.bool)
+        if rows == 2 * batch_size:
+            keep[batch_size:] = False            # second half = null-conditioned CFG branch (cond_drop_prob = 1, ip.py:1521)
+        cond = c.conditioning
+        stamp = None if cond is None else (cond.token, None if lowres_logsnr is None else float(lowres_logsnr[0]))
+        if stamp is None or getattr(eng, '_cond_stamp', None) != stamp:
+            neg_kw = {}
+            if c.neg_embeds is not None and with_text and rows == 2 * batch_size:     # (a stage at cond_scale 1 has no null rows)
+                neg_kw = dict(negative_text_embeds=c.neg_embeds, negative_text_mask=c.neg_masks, negative_rows=c.neg_rows)
+            eng.set_conditioning(text_embeds=c.text_embeds if with_text else None, text_mask=c.text_masks if with_text else None,
+                                 keep=keep, lowres_noise_times=lowres_logsnr, **neg_kw)
+            eng.static_runs = getattr(eng, 'static_runs', 0) + 1
+        eng._cond_stamp = stamp
+        return st
+
+    @torch.no_grad()
+    def _sample(self, c: _Call):
+        """The one private entry of sample(), sample_requests and the sample_pipelined workers."""
+        with self._eval_mode():
+            self._resolve(c)
+            device = c.device
+            stream = self._streams.get((self._lane, str(device)))
+            if stream is None:
+                stream = self._streams[(self._lane, str(device))] = torch.cuda.Stream(device=device)
+            outputs = []
+            # inputs were produced on the caller's stream: order this lane's stream behind it (no device-wide drain — other lanes keep running)
+            stream.wait_stream(torch.cuda.current_stream(device))
+            with torch.cuda.device(device), torch.cuda.stream(stream):
+                for idx in range(c.start_at_unet_number - 1, len(self.unets)):
+                    st = self._prepare_stage(c, idx)
+                    S = st['S']
+                    timing = os.environ.get("IMAGEN_TIMING")
+                    if timing:
+                        stream.synchronize()
+                        import time as _time
+                        t_stage = _time.perf_counter()
+                    init = c.init_images[idx]
+                    out = self._run_stage(st, noise_fn=c.noise_fn, stage=idx, seed=c.seed, use_graph=c.use_graph, use_tqdm=c.use_tqdm,
+                                          max_steps=c.max_steps, skip_steps=c.skip_steps[idx],
+                                          init_images=None if init is None else
+                                          (self._resize_clip(init, S, st['frames']) if st['video'] else self._resize(init, S)))
+                    if timing:
+                        stream.synchronize()
+                        dt = _time.perf_counter() - t_stage
+                        self.last_stage_seconds = getattr(self, "last_stage_seconds", {})
+                        self.last_stage_seconds[idx] = dt
+                        print(f"[imagen] stage {idx} ({S}x{S}, rows {st['eng'].R}): {dt * 1e3:.1f} ms for {st['T'] if c.max_steps is None else min(st['T'], c.max_steps)} steps "
+                              f"({len(st['plan'])} launches/step)", flush=True, file=__import__('sys').stderr)
+                    c.img = out.clone()                  # internal layout (videos: frame-major), feeds the next stage's low-res conditioning
+                    if not self.auto_normalize_img:
+                        c.img = c.img * 2 - 1
+                    outputs.append(self._to_internal(c.img) if st['video'] else c.img)
+                    if c.stop_at_unet_number is not None and c.stop_at_unet_number == idx + 1:
+                        break
+            stream.synchronize()
+        if c.return_pil_images:                              # ip.py:2488-2498: a list of PIL images (one list per unet with return_all_unet_outputs)
+            pil = [_to_pil_images(o) for o in (outputs if c.return_all_unet_outputs else outputs[-1:])]
+            return pil if c.return_all_unet_outputs else pil[-1]
+        return outputs if c.return_all_unet_outputs else outputs[-1]
