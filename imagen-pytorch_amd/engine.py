@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import math
 import os
+from types import SimpleNamespace
 from typing import Dict, List, Optional
 
 import torch
@@ -27,6 +28,7 @@ from torch import nn
 
 from . import ops
 from .modules import CrossAttentionP, ParallelP, PixelShuffleUpsampleP, ResnetBlockP, TransformerBlockP
+from .modules3d import Parallel3dP
 from .ops import ACT_GELU, ACT_SILU, LOG2E, OUT_NCHW_F32, OUT_PIXEL_SHUFFLE, Act, Plan
 
 SIM_SCALE = 8.0  # cosine-sim attention scale (ip.py:510, 768, 386)
@@ -43,6 +45,17 @@ def _f16(t, dev):
 def _conv_wb(mod):
     """(weight, bias) of a conv module in fp32, as the init / final conv weight builders take them."""
     return mod.weight.detach().float(), mod.bias.detach().float()
+
+
+def _w2d(mod):
+    """View of a conv module as the (weight [o, i, kh, kw], bias) holder the weight packer expects, in fp32: the identity on a Conv2d; the video
+    path's modules carry singleton frame / spatial dims, Conv3d (o, i, 1, kh, kw) and Conv1d (o, i, 1)."""
+    w = mod.weight.detach().float()
+    if w.ndim == 5:
+        w = w[:, :, 0]
+    elif w.ndim == 3:
+        w = w[:, :, :, None]
+    return SimpleNamespace(weight=w, bias=None if mod.bias is None else mod.bias.detach().float())
 
 
 def _pad_vec(v: torch.Tensor, n: int) -> torch.Tensor:
@@ -440,8 +453,7 @@ class UnetEngine:
     def _init_conv(self, plan, out: Act):
         """CrossEmbedLayer (ip.py:1051-1076, stride 1) as ONE kmax x kmax conv with the smaller kernels zero-embedded;
         or the plain init conv (ip.py:1198)."""
-        make = lambda: self._init_conv_weight(_conv_wb)
-        out.ssq = self.f32buf(out.rows)
+        w = self.W.get("init_conv", lambda: self._init_conv_weight(_conv_wb))
         R, B = self.R, self.src_batch
         px = out.H * out.W
         # classifier-free guidance runs rows [B, 2B) on the SAME image: nothing conditions the init conv (ip.py:1562), so it is computed
@@ -449,19 +461,16 @@ class UnetEngine:
         shared = (INIT_CONV_SHARED and R == 2 * B and B * px >= INIT_CONV_SHARED_MIN_PIXELS and out.ld == out.C and out.bs == px * out.C and px % 4 == 0)
         if shared:
             half = lambda a: Act(a.t, B, a.H, a.W, a.C, a.ld, a.bs, a.off)
-            op = ops.igemm(plan, half(self.img), self.W.get("init_conv", make), half(out), x2=half(self.cimg) if self.cimg is not None else None,
-                           ssq_out=out.ssq, label="init_conv")
+            self._igemm_ssq(plan, half(self.img), w, out, view=half(out), x2=half(self.cimg) if self.cimg is not None else None, label="init_conv")
             ops.rows_copy(plan, out.t, out.t, B=1, rows=B * px, C=out.C, src_bs=0, src_rs=out.C, dst_bs=0, dst_rs=out.C, src_off=out.off,
                           dst_off=out.off + B * px * out.C, label="init_conv.cfg_rows")
-            if op.ssq_emitted:   # the statistics too: fp32 [rows] seen as rows of 4 floats (8 halves)
+            if out.ssq is not None:   # the statistics too: fp32 [rows] seen as rows of 4 floats (8 halves)
                 ssq16 = out.ssq.view(torch.float16)
                 ops.rows_copy(plan, ssq16, ssq16, B=1, rows=B * px // 4, C=8, src_bs=0, src_rs=8, dst_bs=0, dst_rs=8, src_off=0, dst_off=2 * B * px,
                               label="init_conv.cfg_rows.ssq")
                 plan.keep.append(out.ssq)
         else:
-            op = ops.igemm(plan, self.img, self.W.get("init_conv", make), out, x2=self.cimg, ssq_out=out.ssq, label="init_conv")
-        if not op.ssq_emitted:
-            out.ssq = None
+            self._igemm_ssq(plan, self.img, w, out, x2=self.cimg, label="init_conv")
 
     def _final_conv(self, plan, x: Act):
         """final_conv over cat(x, lowres_cond_img) (ip.py:1722-1725) -> fp32 NCHW."""
@@ -512,140 +521,213 @@ class UnetEngine:
             off += dout
         return cat
 
-    # ---- ResnetBlock (ip.py:693-757)
-    def _resnet(self, plan, x: Act, skip: Optional[Act], rb: ResnetBlockP, name: str, with_cond: bool, skip_scale: Optional[float] = None) -> Act:
-        W, R = self.W, self.R
+    # ---- ResnetBlock (ip.py:693-757; iv.py:743-815): ONE skeleton for the image and the video planner.  The stages below pass one record `b`;
+    # each owns one decision.  What engine3d.UnetEngine3D supplies instead of the following: the frame count `f` of the level, F, `temporal`,
+    # SHORTCUTS off, _spatial, _split_block1, _temporal_conv, and the clip / frames views.
+    SHORTCUTS = True    # the image path's producer shortcuts: block2's prologue in block1's epilogue (`post`), ACT_PREP + conv_big, request_act /
+                        # request_prep, GlobalContext partials from block2's epilogue, GCA_TAIL, RESPREP.  Off on the video path, never measured there
+    temporal = False    # a causal temporal conv behind each Block conv (pseudo-3D conv): block1 then emits no statistics
+    F = 1               # frames per row of `pa2` / `ps2`
+
+    def clip(self, a: Act, f: int) -> Act:
+        """The view whose batch entries are what GlobalContext, the cross attention and the tail's gate act on: here the image itself."""
+        return a
+
+    def frames(self, a: Act, f: int) -> Act:
+        return a
+
+    def _spatial(self, project):
+        """The 3x3 conv module of a Block's `project`."""
+        return project
+
+    def _split_block1(self, b) -> bool:
+        return self._split_small(b.Cin, 9, b.Cout, b.px)
+
+    def _resnet(self, plan, x: Act, skip: Optional[Act], rb: ResnetBlockP, name: str, with_cond: bool, skip_scale: Optional[float] = None, f: int = 1) -> Act:
+        b = self._resnet_inputs(plan, x, skip, rb, name, skip_scale, f)
+        h1 = self._resnet_block1(plan, b)
+        if rb.cross_attn is not None:
+            assert with_cond
+            h1 = self.frames(self._cross_attn(plan, self.clip(h1, f), rb.cross_attn, name + ".cross_attn"), f)
+        h2 = self._resnet_block2(plan, b, h1)
+        self._resnet_gate(plan, b, h2)
+        return self._resnet_tail(plan, b, h2)
+
+    def _resnet_inputs(self, plan, x: Act, skip: Optional[Act], rb, name: str, skip_scale: Optional[float], f: int) -> SimpleNamespace:
+        """The channel bookkeeping of a block, its folded gains and its slice of the time MLPs' (scale, shift) tables; the later stages add
+        what they decide (post_applied / ep_part: block1 / block2; gate, gca, hidden, fused_tail, tail_part, tail_chunks, gate_ready: gate)."""
+        W = self.W
         C1, C2 = x.C, (skip.C if skip is not None else 0)
         Cin, Cout = C1 + C2, rb.dim_out
         assert Cin == rb.dim, f"{name}: {Cin} input channels, block expects {rb.dim}"
-        s = self.unet.skip_connect_scale if skip_scale is None else skip_scale
-        H, Wd = x.H, x.W
-        in_scale = None
+        assert x.B == self.R * f
+        b = SimpleNamespace(x=x, skip=skip, rb=rb, name=name, f=f, Cin=Cin, Cout=Cout, H=x.H, Wd=x.W, px=x.B * x.H * x.W,
+                            s=self.unet.skip_connect_scale if skip_scale is None else skip_scale, in_scale=None, ss=None, gate=None, hidden=None)
         if skip is not None:
-            in_scale = torch.ones(Cin)
-            in_scale[C1:] = s
-        # block1: ChanRMSNorm over the (scaled) concat -> SiLU -> conv3x3.  The norm statistics come from the per-pixel sums of
-        # squares the producers of x / skip emitted in their epilogues (a ROWSTAT pass only where a producer could not).
-        stat_x = lambda: self._ssq_of(plan, x, name + ".block1.stat_x")
+            b.in_scale = torch.ones(Cin)
+            b.in_scale[C1:] = b.s
         # what the launch that produced x may read of the skip's statistics (request_prep below wires them into THAT earlier launch): only sums of
         # squares a producer already emitted — _ssq_of() would append a ROWSTAT at the current plan position, behind the launch that needs them
-        skip_ssq_ready = skip.ssq if skip is not None else None
-        ss = self._ssq_of(plan, skip, name + ".block1.stat_skip") if skip is not None else None
-        w1 = W.conv(name + ".block1", rb.block1.project, split=skip is None and self._split_small(Cin, 9, Cout, R * H * Wd))
-        pa1 = W.f32(name + ".block1.pa", lambda: _pad_vec(rb.block1.norm.gamma.detach().float().flatten().cpu() * math.sqrt(Cin)
-                                                         * (in_scale if in_scale is not None else 1.0), w1.Cin_pad))
+        b.skip_ssq_ready = skip.ssq if skip is not None else None
+        if skip is not None:
+            b.ss = self._ssq_of(plan, skip, name + ".block1.stat_skip")
+        # (the video path's output stage — no skip input, batch-shared affine — has its own, wider, bound: UnetEngine3D._split_block1)
+        b.w1 = W.conv(name + ".block1", self._spatial(rb.block1.project), split=skip is None and self._split_block1(b))
+        b.pa1 = W.f32(name + ".block1.pa", lambda: _pad_vec(rb.block1.norm.gamma.detach().float().flatten().cpu() * math.sqrt(Cin)
+                                                           * (b.in_scale if b.in_scale is not None else 1.0), b.w1.Cin_pad))
         off = self._blk_off[self._blk_index[id(rb)]]
-        pa2 = self.pa2[:, off:]
-        ps2 = self.ps2[:, off:]
-        h1 = self.new(R, H, Wd, Cout)
-        h1.ssq = self.f32buf(R * H * Wd)
+        b.pa2, b.ps2 = self.pa2[:, off:], self.ps2[:, off:]
+        # pa2 / ps2 hold one row per frame of the FULL clip (R*F rows, equal within a clip); at a level with f < F frames, frame
+        # b' = r*f + i reads row b' * (F/f) = r*F + i*(F/f), which lies inside clip r
+        b.pstride = self.total_c * (self.F // f)
+        b.gca = self._resnet_gca_weights(b)
+        return b
+
+    def _resnet_block1(self, plan, b) -> Act:
+        """block1: ChanRMSNorm over the (scaled) concat -> SiLU -> conv3x3 [-> temporal conv].  The norm statistics come from the per-pixel sums
+        of squares the producers of x / skip emitted in their epilogues (a ROWSTAT pass only where a producer could not).  Chooses where the
+        conv's input comes from; sets b.prep / b.big (block2 follows them) and b.post_applied."""
+        x, skip, rb, name, Cin, Cout, H, Wd, w1, pa1, s = b.x, b.skip, b.rb, b.name, b.Cin, b.Cout, b.H, b.Wd, b.w1, b.pa1, b.s
+        stat_x = lambda: self._ssq_of(plan, x, name + ".block1.stat_x")
+        h1 = self.new(x.B, H, Wd, Cout)
         # without a cross-attention in between, block1's epilogue applies block2's ChanRMSNorm -> (scale+1, shift) -> SiLU itself
         # (its consumer waves have the slack; block2's producers then stage h1 with no arithmetic at all)
-        post = dict(pa=pa2, ps=ps2, pstride=self.total_c) if rb.cross_attn is None else None
-        prep = ops.CONV_DMA and ACT_PREP_MIN_COUT > 0 and Cout >= ACT_PREP_MIN_COUT and Cin % 32 == 0 and Cout % 32 == 0
+        post = dict(pa=b.pa2, ps=b.ps2, pstride=b.pstride) if self.SHORTCUTS and rb.cross_attn is None else None
+        b.prep = self.SHORTCUTS and ops.CONV_DMA and ACT_PREP_MIN_COUT > 0 and Cout >= ACT_PREP_MIN_COUT and Cin % 32 == 0 and Cout % 32 == 0
         # the big-tile all-DMA family (conv_big.hip) wants activated inputs: where it applies, the Block prologue runs once per element as
         # its own pass (ACT_PREP, which also reduces x's statistics itself where no producer emitted them) instead of once per staging
         # workgroup inside the wave-specialised kernel
-        big = BIG_PREP and ops.big_cfg(Cout, H, Wd, R) is not None
-        big1 = big and Cin % 32 == 0 and Cin <= 512 and w1.Cin_pad == Cin and not w1.split
+        b.big = self.SHORTCUTS and BIG_PREP and ops.big_cfg(Cout, H, Wd, x.B) is not None
+        big1 = b.big and Cin % 32 == 0 and Cin <= 512 and w1.Cin_pad == Cin and not w1.split
         # x comes out of a fused ResnetBlock tail (GCA_TAIL): that launch also writes silu(ChanRMSNorm(x) * gamma) — it has the pixel's
         # channels and its sum of squares in registers — and block1 stages its input with no arithmetic (prologue-free kernel families)
-        xa = ops.request_act(x, pa1) if (skip is None and TAIL_ACT and w1.Cin_pad == w1.Cin) else None
+        xa = ops.request_act(x, pa1) if (self.SHORTCUTS and skip is None and TAIL_ACT and w1.Cin_pad == w1.Cin) else None
         # ... or out of the previous block's res_conv as a ROWCHAIN launch (RESPREP), which then writes the activated concat(x, skip) as well
-        xr = ops.request_prep(x, skip, skip_ssq_ready, s * s, pa1) if (xa is None and (prep or big1)) else None
+        xr = ops.request_prep(x, skip, b.skip_ssq_ready, s * s, pa1) if (xa is None and (b.prep or big1)) else None
+        kw = dict(emit=not self.temporal, post=post, label=name + ".block1")
         if xa is not None:
-            op = ops.igemm(plan, xa, w1, h1, ssq_out=h1.ssq, post=post, label=name + ".block1")
+            op = self._igemm_ssq(plan, xa, w1, h1, **kw)
         elif xr is not None:     # (no ACT_PREP pass)
-            op = ops.igemm(plan, Act(xr.t, R, H, Wd, Cin, Cin, H * Wd * Cin), w1, h1, ssq_out=h1.ssq, post=post, label=name + ".block1")
-        elif prep or big1:   # MFMA-bound layer: the prologue as its own pass, then an all-DMA conv on the activated concat
-            xa = self.new(R, H, Wd, Cin)
+            op = self._igemm_ssq(plan, Act(xr.t, x.B, H, Wd, Cin, Cin, H * Wd * Cin), w1, h1, **kw)
+        elif b.prep or big1:   # MFMA-bound layer: the prologue as its own pass, then an all-DMA conv on the activated concat
+            xa = self.new(x.B, H, Wd, Cin)
             if big1 and x.ssq is None:
-                ops.act_prep(plan, x, xa, x2=skip, ssq_b=ss, ssq_wb=s * s, pa=pa1, pstride=0, act_in=ACT_SILU, self_stat=True, label=name + ".block1.prep")
+                ops.act_prep(plan, x, xa, x2=skip, ssq_b=b.ss, ssq_wb=s * s, pa=pa1, pstride=0, act_in=ACT_SILU, self_stat=True, label=name + ".block1.prep")
             else:
-                ops.act_prep(plan, x, xa, x2=skip, ssq_a=stat_x(), ssq_b=ss, ssq_wb=s * s, pa=pa1, pstride=0, act_in=ACT_SILU, label=name + ".block1.prep")
-            op = ops.igemm(plan, xa, w1, h1, ssq_out=h1.ssq, post=post, label=name + ".block1")
+                ops.act_prep(plan, x, xa, x2=skip, ssq_a=stat_x(), ssq_b=b.ss, ssq_wb=s * s, pa=pa1, pstride=0, act_in=ACT_SILU, label=name + ".block1.prep")
+            op = self._igemm_ssq(plan, xa, w1, h1, **kw)
         else:
-            op = ops.igemm(plan, x, w1, h1, x2=skip, ssq_a=stat_x(), ssq_b=ss, ssq_wb=s * s, pa=pa1, pstride=0, act_in=ACT_SILU, ssq_out=h1.ssq,
-                           post=post, label=name + ".block1")
-        if not op.ssq_emitted:
-            h1.ssq = None
-        if rb.cross_attn is not None:
-            assert with_cond
-            h1 = self._cross_attn(plan, h1, rb.cross_attn, name + ".cross_attn")
-        h2 = self.new(R, H, Wd, Cout)
-        gate, gca_args = None, None
-        if rb.gca is not None:
-            g = rb.gca
-            hidden = g.net[0].weight.shape[0]
-            gate = self.f32buf(R, Cout)
-            gca_args = dict(wk=W.f32(name + ".gca.wk", lambda: g.to_k.weight.reshape(-1)), bk=float(g.to_k.bias.detach().float().item()),
-                            w1t=W.f32(name + ".gca.w1t", lambda: g.net[0].weight.reshape(hidden, Cout).t()),
-                            b1=W.f32(name + ".gca.b1", lambda: g.net[0].bias),
-                            w2t=W.f32(name + ".gca.w2t", lambda: g.net[2].weight.reshape(Cout, hidden).t()),
-                            b2=W.f32(name + ".gca.b2", lambda: g.net[2].bias), gate=gate)
-        gca_ep = dict(wk=gca_args["wk"], bk=gca_args["bk"]) if rb.gca is not None else None   # GlobalContext partials from block2's epilogue
-        if op.post_applied:     # h1 already holds silu(norm(h1) * (scale + 1) + shift)
-            op2 = ops.igemm(plan, h1, W.conv(name + ".block2", rb.block2.project, split=SPLIT_BLOCK2 and self._split_small(Cout, 9, Cout, R * H * Wd)), h2,
+            op = self._igemm_ssq(plan, x, w1, h1, x2=skip, ssq_a=stat_x(), ssq_b=b.ss, ssq_wb=s * s, pa=pa1, pstride=0, act_in=ACT_SILU, **kw)
+        b.post_applied = bool(op.post_applied)
+        if self.temporal:
+            h1 = self._temporal_conv(plan, h1, rb.block1.project.temporal_conv, name + ".block1.temporal", b.f)
+        return h1
+
+    def _resnet_gca_weights(self, b) -> Optional[dict]:
+        """The GlobalContext parameters of the block (ip.py:660-681; iv.py:1004-1027) as the gate kernels take them, and the gate buffer: one row
+        per image / per clip."""
+        g, W, name, Cout = b.rb.gca, self.W, b.name, b.Cout
+        if g is None:
+            return None
+        b.hidden = hidden = g.net[0].weight.shape[0]
+        b.gate = self.f32buf(self.R, Cout)
+        return dict(wk=W.f32(name + ".gca.wk", lambda: g.to_k.weight.reshape(-1)), bk=float(g.to_k.bias.detach().float().item()),
+                    w1t=W.f32(name + ".gca.w1t", lambda: g.net[0].weight.reshape(hidden, Cout).t()), b1=W.f32(name + ".gca.b1", lambda: g.net[0].bias),
+                    w2t=W.f32(name + ".gca.w2t", lambda: g.net[2].weight.reshape(Cout, hidden).t()), b2=W.f32(name + ".gca.b2", lambda: g.net[2].bias))
+
+    def _resnet_block2(self, plan, b, h1: Act) -> Act:
+        """block2: ChanRMSNorm -> (scale+1, shift) from the time MLP -> SiLU -> conv3x3 [-> temporal conv], in three variants; with SHORTCUTS its
+        epilogue also reduces the GlobalContext partials (b.ep_part = (partials, chunks))."""
+        W, rb, name, Cout, H, Wd = self.W, b.rb, b.name, b.Cout, b.H, b.Wd
+        gca_ep = dict(wk=b.gca["wk"], bk=b.gca["bk"]) if self.SHORTCUTS and b.gca is not None else None   # GlobalContext partials from block2's epilogue
+        h2 = self.new(h1.B, H, Wd, Cout)
+        conv2 = self._spatial(rb.block2.project)
+        affine = dict(pa=b.pa2, ps=b.ps2, pstride=b.pstride, act_in=ACT_SILU)
+        if b.post_applied:     # h1 already holds silu(norm(h1) * (scale + 1) + shift)
+            op2 = ops.igemm(plan, h1, W.conv(name + ".block2", conv2, split=SPLIT_BLOCK2 and self._split_small(Cout, 9, Cout, b.px)), h2,
                             gca=gca_ep, label=name + ".block2")
-        else:                   # block2: ChanRMSNorm -> (scale+1, shift) from the time MLP -> SiLU -> conv3x3
-            w2 = W.conv(name + ".block2", rb.block2.project)
-            if (prep or big) and Cout % 32 == 0 and Cout <= 512:   # the prologue as its own pass (it reduces h1's statistics itself where block1 could not emit them)
-                ha = self.new(R, H, Wd, Cout)
-                if h1.ssq is None and big:
-                    ops.act_prep(plan, h1, ha, pa=pa2, ps=ps2, pstride=self.total_c, act_in=ACT_SILU, self_stat=True, label=name + ".block2.prep")
-                else:
-                    ops.act_prep(plan, h1, ha, ssq_a=self._ssq_of(plan, h1, name + ".block2.stat"), pa=pa2, ps=ps2, pstride=self.total_c,
-                                 act_in=ACT_SILU, label=name + ".block2.prep")
-                op2 = ops.igemm(plan, ha, w2, h2, gca=gca_ep, label=name + ".block2")
+        elif (b.prep or b.big) and Cout % 32 == 0 and Cout <= 512:   # the prologue as its own pass (it reduces h1's statistics itself where block1 could not emit them)
+            ha = self.new(h1.B, H, Wd, Cout)
+            if h1.ssq is None and b.big:
+                ops.act_prep(plan, h1, ha, self_stat=True, label=name + ".block2.prep", **affine)
             else:
-                op2 = ops.igemm(plan, h1, w2, h2, ssq_a=self._ssq_of(plan, h1, name + ".block2.stat"), pa=pa2, ps=ps2, pstride=self.total_c,
-                                act_in=ACT_SILU, gca=gca_ep, label=name + ".block2")
+                ops.act_prep(plan, h1, ha, ssq_a=self._ssq_of(plan, h1, name + ".block2.stat"), label=name + ".block2.prep", **affine)
+            op2 = ops.igemm(plan, ha, W.conv(name + ".block2", conv2), h2, gca=gca_ep, label=name + ".block2")
+        else:
+            op2 = ops.igemm(plan, h1, W.conv(name + ".block2", conv2), h2, ssq_a=self._ssq_of(plan, h1, name + ".block2.stat"), gca=gca_ep,
+                            label=name + ".block2", **affine)
+        b.ep_part = (op2.gca_part_t, op2.gca_chunks) if op2.gca_part_t is not None else None
+        if self.temporal:
+            h2 = self._temporal_conv(plan, h2, rb.block2.project.temporal_conv, name + ".block2.temporal", b.f)
+        return h2
+
+    def _resnet_gate(self, plan, b, h2: Act):
+        """Whether the tail is the fused one, where the GlobalContext partials come from and who finalises the gate: sets b.fused_tail,
+        b.tail_part / b.tail_chunks (partials the fused tail merges itself) and b.gate_ready (b.gate is written by the ops emitted here)."""
+        x, rb, name, Cout, g = b.x, b.rb, b.name, b.Cout, b.gca
         # identity block: GlobalContext finalisation + h2 * gate + x (+ statistics) as ONE launch (GCA_TAIL) where its shapes allow
-        fused_tail = (TAIL_FUSED and rb.res_conv is None and x.ld == x.C and x.bs == H * Wd * x.C
-                      and ops.gca_tail_ok(Cout, (hidden if rb.gca is not None else None)))
-        tail_part, tail_chunks, gate_ready = None, 0, False
-        if rb.gca is not None:
-            wide = ops.GCA_FINAL_SPLIT and ops.gca_final_is_wide(Cout, hidden)   # (a fused tail would stream 1-4 MB of MLP weights in EVERY workgroup)
-            if op2.gca_part_t is not None:   # the partials came out of block2's epilogue: only the merge + squeeze MLP is left
-                if fused_tail and op2.gca_chunks <= 1024 and not wide:
-                    tail_part, tail_chunks = op2.gca_part_t, op2.gca_chunks
-                else:
-                    ops.gca_final(plan, op2.gca_part_t, gca_args["w1t"], gca_args["b1"], gca_args["w2t"], gca_args["b2"], gate, B=R, C=Cout,
-                                  chunks=op2.gca_chunks, label=name + ".gca")
-                    gate_ready = True
-            else:                            # stand-alone pass over h2 (+ in-kernel finalisation where one workgroup covers the image)
-                chunks = ops.gca_chunks(H * Wd, R, Cout)
-                part = self.f32buf(R, chunks, Cout + 2)
-                gate_ready = ops.gca(plan, h2, gca_args["wk"], gca_args["bk"], gca_args["w1t"], gca_args["b1"], gca_args["w2t"], gca_args["b2"], part,
-                                     gate, chunks, label=name + ".gca", final=(not fused_tail) or wide)
-                if not gate_ready:
-                    tail_part, tail_chunks = part, chunks
-        out = self.new(R, H, Wd, Cout)
-        out.ssq = self.f32buf(R * H * Wd)
-        if fused_tail:
+        b.fused_tail = bool(self.SHORTCUTS and TAIL_FUSED and rb.res_conv is None and x.ld == x.C and x.bs == b.H * b.Wd * x.C
+                            and ops.gca_tail_ok(Cout, b.hidden))
+        b.tail_part, b.tail_chunks, b.gate_ready = None, 0, False
+        if g is None:
+            return
+        wide = ops.GCA_FINAL_SPLIT and ops.gca_final_is_wide(Cout, b.hidden)   # (a fused tail would stream 1-4 MB of MLP weights in EVERY workgroup)
+        if b.ep_part is not None:   # the partials came out of block2's epilogue: only the merge + squeeze MLP is left
+            part, chunks = b.ep_part
+            if b.fused_tail and chunks <= 1024 and not wide:
+                b.tail_part, b.tail_chunks = part, chunks
+            else:
+                ops.gca_final(plan, part, g["w1t"], g["b1"], g["w2t"], g["b2"], b.gate, B=self.R, C=Cout, chunks=chunks, label=name + ".gca")
+                b.gate_ready = True
+        else:                       # stand-alone pass over h2 (+ in-kernel finalisation where one workgroup covers the image); on a clip: softmax
+            h2c = self.clip(h2, b.f)   # pooling over ALL f*h*w positions (iv.py:1022-1027)
+            chunks = ops.gca_chunks(h2c.H * h2c.W, self.R, Cout)
+            part = self.f32buf(self.R, chunks, Cout + 2)
+            b.gate_ready = ops.gca(plan, h2c, g["wk"], g["bk"], g["w1t"], g["b1"], g["w2t"], g["b2"], part, b.gate, chunks, label=name + ".gca",
+                                   final=(not b.fused_tail) or wide)
+            if not b.gate_ready:
+                b.tail_part, b.tail_chunks = part, chunks
+
+    def _resnet_tail(self, plan, b, h2: Act) -> Act:
+        """out = h2 * gate + res_conv(concat(x, skip)) (ip.py:741, 753-757) with its per-pixel statistics, as one of four launches; the gate is
+        per image / per clip, so the tail runs on the clip views."""
+        x, skip, rb, name, g, f = b.x, b.skip, b.rb, b.name, b.gca, b.f
+        out = self.new(x.B, b.H, b.Wd, b.Cout)
+        h2c, xc, outc = self.clip(h2, f), self.clip(x, f), self.clip(out, f)
+        if b.fused_tail:
             assert skip is None
-            ops.gca_tail(plan, h2, x, out, part=tail_part, chunks=tail_chunks, w1t=gca_args and gca_args["w1t"], b1=gca_args and gca_args["b1"],
-                         w2t=gca_args and gca_args["w2t"], b2=gca_args and gca_args["b2"], gate_in=gate if gate_ready else None,
-                         gate=gate if tail_part is not None else None, ssq_out=out.ssq, label=name + ".tail")
-        elif rb.res_conv is not None:
-            wr = W.conv(name + ".res_conv", rb.res_conv, in_scale=in_scale)
-            if big and ops.resprep_ok(x, skip, wr, H * Wd):
+            out.ssq = self.f32buf(out.rows)
+            ops.gca_tail(plan, h2, x, out, part=b.tail_part, chunks=b.tail_chunks, w1t=g and g["w1t"], b1=g and g["b1"], w2t=g and g["w2t"], b2=g and g["b2"],
+                         gate_in=b.gate if b.gate_ready else None, gate=b.gate if b.tail_part is not None else None, ssq_out=out.ssq, label=name + ".tail")
+        elif rb.res_conv is not None:                             # 1x1: the clip view keeps the gate per clip
+            wr = self.W.conv(name + ".res_conv", _w2d(rb.res_conv), in_scale=b.in_scale)
+            skc = self.clip(skip, f) if skip is not None else None
+            if b.big and ops.resprep_ok(x, skip, wr, b.H * b.Wd):
                 # on the levels whose Blocks take the big-tile all-DMA convs (their prologue is a pass of its own), the res_conv + gate tail is
                 # a ROWCHAIN launch that the NEXT block asks for its activated input too (request_prep): that block needs no ACT_PREP
-                op = ops.rowchain_resprep(plan, x.tokens(), skip.tokens() if skip is not None else None, h2.tokens(), gate, out.tokens(), wr,
-                                          rows_per_batch=H * Wd, ssq_out=out.ssq, label=name + ".res_conv.chain")
+                out.ssq = self.f32buf(out.rows)                   # (a RESPREP chain always emits its output's statistics)
+                op = ops.rowchain_resprep(plan, x.tokens(), skip.tokens() if skip is not None else None, h2.tokens(), b.gate, out.tokens(), wr,
+                                          rows_per_batch=b.H * b.Wd, ssq_out=out.ssq, label=name + ".res_conv.chain")
                 out.res_op = (op, plan)
-                op.ssq_emitted = True
-            elif gate is not None:
-                op = ops.igemm(plan, x, wr, out, x2=skip, addend=h2, gate=gate, ssq_out=out.ssq, label=name + ".res_conv")
+            elif b.gate is not None:
+                self._igemm_ssq(plan, xc, wr, out, view=outc, x2=skc, addend=h2c, gate=b.gate, label=name + ".res_conv")
             else:
-                op = ops.igemm(plan, x, wr, out, x2=skip, res=h2, ssq_out=out.ssq, label=name + ".res_conv")
-            if not op.ssq_emitted:
-                out.ssq = None
+                self._igemm_ssq(plan, xc, wr, out, view=outc, x2=skc, res=h2c, label=name + ".res_conv")
         else:
             assert skip is None
-            ops.gate_residual(plan, h2, gate, x, out, rs_out=out.ssq, raw_ssq=True, label=name + ".tail")
+            out.ssq = self.f32buf(out.rows)
+            ops.gate_residual(plan, h2c, b.gate, xc, outc, rs_out=out.ssq, raw_ssq=True, label=name + ".tail")
         return out
+
+    def _igemm_ssq(self, plan, x: Act, w, out: Act, view: Optional[Act] = None, emit: bool = True, **kw):
+        """ops.igemm into `out` — launched on `view` where the launch sees `out`'s memory in another shape — that also emits out's per-pixel sums of
+        squares.  A launch whose tile does not cover Cout cannot (and with emit=False it is not asked to): out.ssq is then None and the consumer
+        runs a ROWSTAT pass (_ssq_of).  Returns the params."""
+        out.ssq = self.f32buf(out.rows) if emit else None
+        op = ops.igemm(plan, x, w, out if view is None else view, ssq_out=out.ssq, **kw)
+        if not op.ssq_emitted:
+            out.ssq = None
+        return op
 
     def _ssq_of(self, plan, a: Act, label: str) -> torch.Tensor:
         """Per-pixel sum of squares of `a`: the producer's epilogue output if it emitted one, else one ROWSTAT (mode 2) pass."""
@@ -807,64 +889,60 @@ class UnetEngine:
         ops.ln_residual(plan, y, W.f32(nm + ".out_g", lambda: attn.to_out[1].g), x1, res=tok, eps=1e-5, ln_stats_out=st, label=nm + ".out_norm")
         return x1, st
 
-    def _feed_forward(self, plan, x: Act, ff: nn.Sequential, name: str, ln_stats: Optional[tuple] = None, split: bool = False) -> Act:
-        """ip.py:972-980 + residual (ip.py:1018): LN -> Linear -> GELU -> LN -> Linear, + x.  ln_stats: (mean, rstd) of x's rows where its
-        producer emitted them."""
+    def _feed_forward(self, plan, x: Act, ff: nn.Sequential, name: str, ln_stats: Optional[tuple] = None, split: bool = False,
+                      labels=(".lin1", ".lin2"), between=None, out: Optional[Act] = None) -> Act:
+        """ip.py:972-980 + residual (ip.py:1018): LN -> Linear -> GELU -> LN -> Linear, + x, on the token view x.  ln_stats: (mean, rstd) of x's
+        rows where its producer emitted them.  The video planner's ChanFeedForward (iv.py:1048-1057) is the same chain under its own `labels`, with
+        `between(hidden) -> hidden` in front of the second LayerNorm and an `out` of another shape over the same rows (it carries the statistics)."""
         W = self.W
         rows = x.rows
-        hidden = ff[1].weight.shape[0]
         if ln_stats is not None:
             mu, rs = ln_stats
         else:
             mu, rs = self.f32buf(rows), self.f32buf(rows)
             ops.rowstat(plan, x, mode=1, rs=rs, mu=mu, eps=1e-5, label=name + ".ln0")
-        w1 = W.conv(name + ".w1", ff[1], split=split)
-        hid = self.new(x.B, x.H, x.W, hidden)
+        w1 = W.conv(name + ".w1", _w2d(ff[1]), split=split)
+        hid = self.new(x.B, x.H, x.W, w1.Cout)
         ops.igemm(plan, x, w1, hid, mu=mu, rs=rs, pa=W.f32(name + ".g0", lambda: _pad_vec(ff[0].g, w1.Cin_pad)), act_out=ACT_GELU,
-                  label=name + ".lin1")
+                  label=name + labels[0])
+        if between is not None:
+            hid = between(hid)
         mu2, rs2 = self.f32buf(rows), self.f32buf(rows)
         ops.rowstat(plan, hid, mode=1, rs=rs2, mu=mu2, eps=1e-5, label=name + ".ln1")
-        w2 = W.conv(name + ".w2", ff[4], split=split)
-        out = self.new(x.B, x.H, x.W, x.C)
-        out.ssq = self.f32buf(rows)
-        op = ops.igemm(plan, hid, w2, out, mu=mu2, rs=rs2, pa=W.f32(name + ".g1", lambda: _pad_vec(ff[3].g, w2.Cin_pad)), res=x,
-                       ssq_out=out.ssq, label=name + ".lin2")
-        if not op.ssq_emitted:
-            out.ssq = None
+        w2 = W.conv(name + ".w2", _w2d(ff[-1]), split=split)
+        view = None if out is None else Act(out.t, x.B, x.H, x.W, x.C, x.C, x.H * x.W * x.C)
+        out = out if out is not None else self.new(x.B, x.H, x.W, x.C)
+        self._igemm_ssq(plan, hid, w2, out, view=view, mu=mu2, rs=rs2, pa=W.f32(name + ".g1", lambda: _pad_vec(ff[-2].g, w2.Cin_pad)), res=x,
+                        label=name + labels[1])
         return out
 
     # ---- resampling
     def _downsample(self, plan, x: Act, mod, name: str) -> Act:
-        R = self.R
-        if isinstance(mod, ParallelP):  # last level (ip.py:1366): conv3x3 + conv1x1 summed == one 3x3 conv with the 1x1 folded into its centre tap
+        """Per image / per frame (the video path's modules carry a singleton frame dim: _w2d)."""
+        if isinstance(mod, (ParallelP, Parallel3dP)):  # last level (ip.py:1366; iv.py:1465): conv3x3 + conv1x1 summed == one 3x3 conv with the 1x1 folded into its centre tap
             def make():
-                w3 = mod.fns[0].weight.detach().float().clone()
-                w3[:, :, 1, 1] += mod.fns[1].weight.detach().float()[:, :, 0, 0]
-                return ops.pack_weight(w3, mod.fns[0].bias.detach().float() + mod.fns[1].bias.detach().float(), self.dev)
+                c3, c1 = _w2d(mod.fns[0]), _w2d(mod.fns[1])
+                w3 = c3.weight.clone()
+                w3[:, :, 1, 1] += c1.weight[:, :, 0, 0]
+                return ops.pack_weight(w3, c3.bias + c1.bias, self.dev)
             w = self.W.get(name, make)
-            out = self.new(R, x.H, x.W, w.Cout)
-            out.ssq = self.f32buf(out.rows)
-            if not ops.igemm(plan, x, w, out, ssq_out=out.ssq, label=name).ssq_emitted:
-                out.ssq = None
+            out = self.new(x.B, x.H, x.W, w.Cout)
+            self._igemm_ssq(plan, x, w, out, label=name)
             return out
-        conv = mod[1]  # pixel-unshuffle + 1x1 conv (ip.py:633-640) == 2x2 stride-2 conv
-        def make():
-            w = conv.weight.detach().float()
-            return ops.pack_weight(w.view(w.shape[0], x.C, 2, 2), conv.bias.detach().float(), self.dev)
-        w = self.W.get(name, make)
-        out = self.new(R, x.H // 2, x.W // 2, w.Cout)
-        out.ssq = self.f32buf(out.rows)
-        if not ops.igemm(plan, x, w, out, stride=2, pad=0, ssq_out=out.ssq, label=name).ssq_emitted:
-            out.ssq = None
+        conv = _w2d(mod[1])  # pixel-unshuffle + 1x1 conv (ip.py:633-640; iv.py:640-645) == 2x2 stride-2 conv
+        w = self.W.get(name, lambda: ops.pack_weight(conv.weight.reshape(conv.weight.shape[0], x.C, 2, 2), conv.bias, self.dev))
+        out = self.new(x.B, x.H // 2, x.W // 2, w.Cout)
+        self._igemm_ssq(plan, x, w, out, stride=2, pad=0, label=name)
         return out
 
-    def _upsample(self, plan, x: Act, mod: PixelShuffleUpsampleP, name: str) -> Act:
-        conv = mod.net[0]
+    def _upsample(self, plan, x: Act, mod, name: str) -> Act:
+        """PixelShuffleUpsample (ip.py:603-631; iv.py:609-631), per image / per frame."""
+        conv = _w2d(mod.net[0])
         c4 = conv.weight.shape[0]
         cq = c4 // 4
         perm = torch.arange(c4).view(cq, 4).t().reshape(-1)  # PixelShuffle channel c*4 + s -> packed order (s, c)
         w = self.W.conv(name, conv, out_perm=perm)
-        out = self.new(self.R, 2 * x.H, 2 * x.W, cq)
+        out = self.new(x.B, 2 * x.H, 2 * x.W, cq)
         ops.igemm(plan, x, w, out, act_out=ACT_SILU, out_mode=OUT_PIXEL_SHUFFLE, label=name)
         return out
 
@@ -880,9 +958,7 @@ class UnetEngine:
                               src_off=x.off, dst_off=(dy * 2 * Wd + dx) * C, label=f"{name}.nearest{dy}{dx}")
         w = self.W.conv(name + ".conv", mod[1])
         out = self.new(R, 2 * H, 2 * Wd, w.Cout)
-        out.ssq = self.f32buf(out.rows)
-        if not ops.igemm(plan, up, w, out, ssq_out=out.ssq, label=name + ".conv").ssq_emitted:
-            out.ssq = None
+        self._igemm_ssq(plan, up, w, out, label=name + ".conv")
         return out
 
     # ------------------------------------------------------------------------------------------ conditioning K/V

@@ -25,27 +25,15 @@ frames [len(pre), len(pre) + Fx) — two strided row copies around the unchanged
 from __future__ import annotations
 
 import math
-from types import SimpleNamespace
 from typing import List, Optional
 
 import torch
 import torch.nn.functional as TF
 
 from . import ops
-from .engine import SIM_SCALE, UnetEngine, _pad_vec
-from .modules3d import Parallel3dP, PixelShuffleUpsample3dP, TransformerBlock3dP
-from .ops import ACT_GELU, ACT_SILU, OUT_NCHW_F32, OUT_PIXEL_SHUFFLE, Act, Plan
-
-
-def _w2d(mod):
-    """View of a conv module whose weight carries singleton frame / spatial dims, as the (w [o, i, kh, kw], bias) pair the image-path
-    weight packer expects: Conv3d (o, i, 1, kh, kw) and Conv1d (o, i, 1)."""
-    w = mod.weight.detach().float()
-    if w.ndim == 5:
-        w = w[:, :, 0]
-    elif w.ndim == 3:
-        w = w[:, :, :, None]
-    return SimpleNamespace(weight=w, bias=None if mod.bias is None else mod.bias.detach().float())
+from .engine import SIM_SCALE, UnetEngine, _pad_vec, _w2d
+from .modules3d import PixelShuffleUpsample3dP, TransformerBlock3dP
+from .ops import ACT_SILU, OUT_NCHW_F32, Act, Plan
 
 
 def _wb2d(mod):
@@ -79,6 +67,7 @@ class UnetEngine3D(UnetEngine):
         self.Fx, self.Fpre, self.Fpost = frames, pre_frames, post_frames   # frames of the sampler state / of the two prompts
         self.F = frames + pre_frames + post_frames                         # frames the network runs on
         self.ignore_time = ignore_time
+        self.temporal = not ignore_time
         assert self.F <= 128, "the temporal attention kernels hold at most 128 frames per pixel"
         div = getattr(unet, 'total_temporal_divisor', 1)
         assert pre_frames % div == 0 and post_frames % div == 0, \
@@ -184,17 +173,17 @@ class UnetEngine3D(UnetEngine):
             x = self._temporal_attn(plan, x, u.init_temporal_attn, "init_temporal_attn", f)
         self.taps['init'] = x
         if u.init_resnet_block is not None:
-            x = self._resnet3d(plan, x, None, u.init_resnet_block, "init_resnet", f, with_cond=False)
+            x = self._resnet(plan, x, None, u.init_resnet_block, "init_resnet", with_cond=False, f=f)
         hiddens: List[Act] = []
         strides = self.lc["temporal_strides"]
         n_levels = len(self.lc["in_out"])
         for i, lvl in enumerate(u.downs):
             pre, init_block, res_blocks, attn_block, peg, tattn, tdown, post = lvl
             if pre is not None:
-                x = self._downsample3d(plan, x, pre, f"downs.{i}.0")
-            x = self._resnet3d(plan, x, None, init_block, f"downs.{i}.1", f, with_cond=True)
+                x = self._downsample(plan, x, pre, f"downs.{i}.0")
+            x = self._resnet(plan, x, None, init_block, f"downs.{i}.1", with_cond=True, f=f)
             for j, rb in enumerate(res_blocks):
-                x = self._resnet3d(plan, x, None, rb, f"downs.{i}.2.{j}", f, with_cond=False)
+                x = self._resnet(plan, x, None, rb, f"downs.{i}.2.{j}", with_cond=False, f=f)
                 hiddens.append(x)
             if isinstance(attn_block, TransformerBlock3dP):
                 x = self._transformer3d(plan, x, attn_block, f"downs.{i}.3", f)
@@ -207,9 +196,9 @@ class UnetEngine3D(UnetEngine):
                 x = self._temporal_down(plan, x, tdown, f"downs.{i}.6", f)
                 f //= strides[i]
             if post is not None:
-                x = self._downsample3d(plan, x, post, f"downs.{i}.7")
+                x = self._downsample(plan, x, post, f"downs.{i}.7")
         self.taps['mid_in'] = x
-        x = self._resnet3d(plan, x, None, u.mid_block1, "mid_block1", f, with_cond=True)
+        x = self._resnet(plan, x, None, u.mid_block1, "mid_block1", with_cond=True, f=f)
         self.taps['mid_block1'] = x
         if u.mid_attn is not None:                    # Residual(Attention) over all f*h*w tokens, no context, no feed-forward
             tok = self.clip(x, f).tokens()
@@ -221,7 +210,7 @@ class UnetEngine3D(UnetEngine):
             self.taps['mid_peg'] = x
             x = self._temporal_attn(plan, x, u.mid_temporal_attn, "mid_temporal_attn", f)
             self.taps['mid_tattn'] = x
-        x = self._resnet3d(plan, x, None, u.mid_block2, "mid_block2", f, with_cond=True)
+        x = self._resnet(plan, x, None, u.mid_block2, "mid_block2", with_cond=True, f=f)
         self.taps['mid'] = x
         for i, lvl in enumerate(u.ups):
             init_block, res_blocks, attn_block, peg, tattn, tup, upsample = lvl
@@ -229,20 +218,20 @@ class UnetEngine3D(UnetEngine):
             if tup is not None and not it:
                 x = self._temporal_up(plan, x, tup, f"ups.{i}.5", f)
                 f *= strides[lv]
-            x = self._resnet3d(plan, x, hiddens.pop(), init_block, f"ups.{i}.0", f, with_cond=True)
+            x = self._resnet(plan, x, hiddens.pop(), init_block, f"ups.{i}.0", with_cond=True, f=f)
             for j, rb in enumerate(res_blocks):
-                x = self._resnet3d(plan, x, hiddens.pop(), rb, f"ups.{i}.1.{j}", f, with_cond=False)
+                x = self._resnet(plan, x, hiddens.pop(), rb, f"ups.{i}.1.{j}", with_cond=False, f=f)
             if isinstance(attn_block, TransformerBlock3dP):
                 x = self._transformer3d(plan, x, attn_block, f"ups.{i}.2", f)
             if not it:
                 x = self._temporal_peg(plan, x, peg, f"ups.{i}.3", f)
                 x = self._temporal_attn(plan, x, tattn, f"ups.{i}.4", f)
             if isinstance(upsample, PixelShuffleUpsample3dP):
-                x = self._upsample3d(plan, x, upsample, f"ups.{i}.6")
+                x = self._upsample(plan, x, upsample, f"ups.{i}.6")
             self.taps[f'up{i}'] = x
         assert not hiddens and f == F
         if u.final_res_block is not None:
-            x = self._resnet3d(plan, x, None, u.final_res_block, "final_res_block", f, with_cond=False)
+            x = self._resnet(plan, x, None, u.final_res_block, "final_res_block", with_cond=False, f=f)
         self._final_conv3d(plan, x)
 
         dyn = Plan("kv-dynamic")
@@ -256,9 +245,7 @@ class UnetEngine3D(UnetEngine):
     def _init_conv3d(self, plan) -> Act:
         """CrossEmbedLayer per frame (iv.py:1121-1146) as ONE kmax x kmax conv, or the plain init conv."""
         out = self.new(self.R * self.F, self.S, self.S, self.lc["init_dim"])
-        out.ssq = self.f32buf(out.rows)
-        if not ops.igemm(plan, self.img, self.W.get("init_conv", lambda: self._init_conv_weight(_wb2d)), out, x2=self.cimg, ssq_out=out.ssq, label="init_conv").ssq_emitted:
-            out.ssq = None
+        self._igemm_ssq(plan, self.img, self.W.get("init_conv", lambda: self._init_conv_weight(_wb2d)), out, x2=self.cimg, label="init_conv")
         return out
 
     def _final_conv3d(self, plan, x: Act):
@@ -343,74 +330,19 @@ class UnetEngine3D(UnetEngine):
         return y
 
     # ------------------------------------------------------------------------------------------ ResnetBlock (iv.py:743-815)
-    def _resnet3d(self, plan, x: Act, skip: Optional[Act], rb, name: str, f: int, with_cond: bool) -> Act:
-        W, R = self.W, self.R
-        C1, C2 = x.C, (skip.C if skip is not None else 0)
-        Cin, Cout = C1 + C2, rb.dim_out
-        assert Cin == rb.dim, f"{name}: {Cin} input channels, block expects {rb.dim}"
-        s = self.unet.skip_connect_scale
-        H, Wd = x.H, x.W
-        temporal = not self.ignore_time
-        in_scale = None
-        if skip is not None:
-            in_scale = torch.ones(Cin)
-            in_scale[C1:] = s
-        sx = self._ssq_of(plan, x, name + ".block1.stat_x")
-        ss = self._ssq_of(plan, skip, name + ".block1.stat_skip") if skip is not None else None
-        # (the output stage's block1 — no skip input, batch-shared affine — takes a split-precision weight: _split_output)
-        w1 = W.conv(name + ".block1", rb.block1.project.spatial_conv,
-                    split=name == "final_res_block" and skip is None and self._split_output(Cin, 9, Cout, R * f * H * Wd))
-        pa1 = W.f32(name + ".block1.pa", lambda: _pad_vec(rb.block1.norm.gamma.detach().float().flatten().cpu() * math.sqrt(Cin)
-                                                         * (in_scale if in_scale is not None else 1.0), w1.Cin_pad))
-        off = self._blk_off[self._blk_index[id(rb)]]
-        pa2, ps2 = self.pa2[:, off:], self.ps2[:, off:]
-        h1 = self.new(R * f, H, Wd, Cout)
-        h1.ssq = self.f32buf(h1.rows)
-        op = ops.igemm(plan, x, w1, h1, x2=skip, ssq_a=sx, ssq_b=ss, ssq_wb=s * s, pa=pa1, pstride=0, act_in=ACT_SILU,
-                       ssq_out=None if temporal else h1.ssq, label=name + ".block1")
-        if temporal or not op.ssq_emitted:
-            h1.ssq = None
-        if temporal:
-            h1 = self._temporal_conv(plan, h1, rb.block1.project.temporal_conv, name + ".block1.temporal", f)
-        if rb.cross_attn is not None:
-            assert with_cond
-            h1 = self.frames(self._cross_attn(plan, self.clip(h1, f), rb.cross_attn, name + ".cross_attn"), f)
-        s1 = self._ssq_of(plan, h1, name + ".block2.stat")
-        h2 = self.new(R * f, H, Wd, Cout)
-        # pa2 / ps2 hold one row per frame of the FULL clip (R*F rows, equal within a clip); at a level with f < F frames, frame
-        # b' = r*f + i reads row b' * (F/f) = r*F + i*(F/f), which lies inside clip r
-        ops.igemm(plan, h1, W.conv(name + ".block2", rb.block2.project.spatial_conv), h2, ssq_a=s1, pa=pa2, ps=ps2,
-                  pstride=self.total_c * (self.F // f), act_in=ACT_SILU, label=name + ".block2")
-        if temporal:
-            h2 = self._temporal_conv(plan, h2, rb.block2.project.temporal_conv, name + ".block2.temporal", f)
-        gate = None
-        h2c = self.clip(h2, f)
-        if rb.gca is not None:                                  # softmax pooling over ALL f*h*w positions of the clip (iv.py:1022-1027)
-            g = rb.gca
-            hidden = g.net[0].weight.shape[0]
-            gate = self.f32buf(R, Cout)
-            chunks = ops.gca_chunks(f * H * Wd, R, Cout)
-            part = self.f32buf(R, chunks, Cout + 2)
-            ops.gca(plan, h2c, W.f32(name + ".gca.wk", lambda: g.to_k.weight.reshape(-1)), float(g.to_k.bias.detach().float().item()),
-                    W.f32(name + ".gca.w1t", lambda: g.net[0].weight.reshape(hidden, Cout).t()), W.f32(name + ".gca.b1", lambda: g.net[0].bias),
-                    W.f32(name + ".gca.w2t", lambda: g.net[2].weight.reshape(Cout, hidden).t()), W.f32(name + ".gca.b2", lambda: g.net[2].bias),
-                    part, gate, chunks, label=name + ".gca")
-        out = self.new(R * f, H, Wd, Cout)
-        out.ssq = self.f32buf(out.rows)
-        outc, xc = self.clip(out, f), self.clip(x, f)
-        if rb.res_conv is not None:                             # 1x1: the clip view keeps the gate per clip
-            wr = W.conv(name + ".res_conv", _w2d(rb.res_conv), in_scale=in_scale)
-            skc = self.clip(skip, f) if skip is not None else None
-            if gate is not None:
-                op = ops.igemm(plan, xc, wr, outc, x2=skc, addend=h2c, gate=gate, ssq_out=out.ssq, label=name + ".res_conv")
-            else:
-                op = ops.igemm(plan, xc, wr, outc, x2=skc, res=h2c, ssq_out=out.ssq, label=name + ".res_conv")
-            if not op.ssq_emitted:
-                out.ssq = None
-        else:
-            assert skip is None
-            ops.gate_residual(plan, h2c, gate, xc, outc, rs_out=out.ssq, raw_ssq=True, label=name + ".tail")
-        return out
+    # engine.UnetEngine._resnet with f frames per clip; what differs from the image path is stated here and in `temporal`, clip / frames above.
+    SHORTCUTS = False   # the image path's producer shortcuts (engine.UnetEngine.SHORTCUTS) stay off: the C5 plan is pinned without them
+
+    def _spatial(self, project):
+        return project.spatial_conv
+
+    def _split_block1(self, b) -> bool:
+        """The output stage's block1 takes a split-precision weight (SPLIT_OUTPUT_* above)."""
+        return b.name == "final_res_block" and self._split_output(b.Cin, 9, b.Cout, b.px)
+
+    def _resnet_inputs(self, plan, x: Act, skip: Optional[Act], rb, name: str, skip_scale, f: int):
+        self._ssq_of(plan, x, name + ".block1.stat_x")       # (this planner reduces x's statistics ahead of the skip's: the launch order is pinned)
+        return super()._resnet_inputs(plan, x, skip, rb, name, skip_scale, f)
 
     # ------------------------------------------------------------------------------------------ temporal PEG / attention
     def _temporal_peg(self, plan, x: Act, mod, name: str, f: int) -> Act:
@@ -477,21 +409,12 @@ class UnetEngine3D(UnetEngine):
 
     def _chan_feed_forward(self, plan, x: Act, ff, name: str, f: int) -> Act:
         """x + ChanFeedForward(x) (iv.py:1048-1057): per-position LayerNorm over C -> 1x1 -> GELU -> [second half of the hidden channels
-        taken from the previous frame] -> LayerNorm -> 1x1."""
-        W, R = self.W, self.R
-        C, P = x.C, x.H * x.W
+        taken from the previous frame] -> LayerNorm -> 1x1: the image path's feed-forward on the token view, with the shift in between."""
+        R, C, P = self.R, x.C, x.H * x.W
         rows = R * f * P
-        shift = getattr(ff, "time_token_shift", True)
-        j = 4 if shift else 3
-        tok = Act(x.t, 1, 1, rows, C, C, rows * C, x.off)
-        mu, rs = self.f32buf(rows), self.f32buf(rows)
-        ops.rowstat(plan, tok, mode=1, rs=rs, mu=mu, eps=1e-5, label=name + ".ln0")
-        w1 = W.conv(name + ".w1", _w2d(ff[1]))
-        hidden = w1.Cout
-        hid = self.new(1, 1, rows, hidden)
-        ops.igemm(plan, tok, w1, hid, mu=mu, rs=rs, pa=W.f32(name + ".g0", lambda: _pad_vec(ff[0].g, w1.Cin_pad)), act_out=ACT_GELU,
-                  label=name + ".conv1")
-        if shift and x.B == R * f:                                # 5-D input only (iv.py:1041-1042); here always
+
+        def shift(hid: Act) -> Act:
+            hidden = hid.C
             half = hidden // 2 + hidden % 2                       # torch.chunk(2): the first chunk takes the ceiling
             assert half % 8 == 0 and (hidden - half) % 8 == 0, "time token shift needs 8-channel aligned halves"
             sh = self.new(1, 1, rows, hidden)
@@ -501,53 +424,16 @@ class UnetEngine3D(UnetEngine):
             if f > 1:
                 ops.rows_copy(plan, hid.t, sh.t, B=R, rows=(f - 1) * P, C=hidden - half, src_bs=f * fr, src_rs=hidden, dst_bs=f * fr,
                               dst_rs=hidden, src_off=half, dst_off=fr + half, label=name + ".shift_half")
-            zeros = W.get(("zeros16", hidden), lambda: torch.zeros(hidden, dtype=torch.float16, device=self.dev))
+            zeros = self.W.get(("zeros16", hidden), lambda: torch.zeros(hidden, dtype=torch.float16, device=self.dev))
             ops.rows_copy(plan, zeros, sh.t, B=R, rows=P, C=hidden - half, src_bs=0, src_rs=0, dst_bs=f * fr, dst_rs=hidden, dst_off=half,
                           label=name + ".shift_zero")
-            hid = sh
-        mu2, rs2 = self.f32buf(rows), self.f32buf(rows)
-        ops.rowstat(plan, hid, mode=1, rs=rs2, mu=mu2, eps=1e-5, label=name + ".ln1")
-        w2 = W.conv(name + ".w2", _w2d(ff[j + 1]))
-        out = self.new(x.B, x.H, x.W, C)
-        out.ssq = self.f32buf(rows)
-        op = ops.igemm(plan, hid, w2, Act(out.t, 1, 1, rows, C, C, rows * C), mu=mu2, rs=rs2,
-                       pa=W.f32(name + ".g1", lambda: _pad_vec(ff[j].g, w2.Cin_pad)), res=tok, ssq_out=out.ssq, label=name + ".conv2")
-        if not op.ssq_emitted:
-            out.ssq = None
-        return out
+            return sh
+
+        tok = Act(x.t, 1, 1, rows, C, C, rows * C, x.off)
+        on = getattr(ff, "time_token_shift", True) and x.B == R * f      # 5-D input only (iv.py:1041-1042); here always
+        return self._feed_forward(plan, tok, ff, name, labels=(".conv1", ".conv2"), between=shift if on else None, out=self.new(x.B, x.H, x.W, C))
 
     # ------------------------------------------------------------------------------------------ resampling
-    def _downsample3d(self, plan, x: Act, mod, name: str) -> Act:
-        if isinstance(mod, Parallel3dP):      # last level: conv3x3 + conv1x1 summed == one 3x3 conv (iv.py:1465)
-            def make():
-                a, b = _w2d(mod.fns[0]), _w2d(mod.fns[1])
-                w3 = a.weight.clone()
-                w3[:, :, 1, 1] += b.weight[:, :, 0, 0]
-                return ops.pack_weight(w3, a.bias + b.bias, self.dev)
-            w = self.W.get(name, make)
-            out = self.new(x.B, x.H, x.W, w.Cout)
-            out.ssq = self.f32buf(out.rows)
-            if not ops.igemm(plan, x, w, out, ssq_out=out.ssq, label=name).ssq_emitted:
-                out.ssq = None
-            return out
-        cw = _w2d(mod[1])                     # pixel-unshuffle + 1x1 conv per frame (iv.py:640-645) == 2x2 stride-2 conv
-        w = self.W.get(name, lambda: ops.pack_weight(cw.weight.reshape(cw.weight.shape[0], x.C, 2, 2), cw.bias, self.dev))
-        out = self.new(x.B, x.H // 2, x.W // 2, w.Cout)
-        out.ssq = self.f32buf(out.rows)
-        if not ops.igemm(plan, x, w, out, stride=2, pad=0, ssq_out=out.ssq, label=name).ssq_emitted:
-            out.ssq = None
-        return out
-
-    def _upsample3d(self, plan, x: Act, mod: PixelShuffleUpsample3dP, name: str) -> Act:
-        cw = _w2d(mod.net[0])
-        c4 = cw.weight.shape[0]
-        cq = c4 // 4
-        perm = torch.arange(c4).view(cq, 4).t().reshape(-1)
-        w = self.W.conv(name, cw, out_perm=perm)
-        out = self.new(x.B, 2 * x.H, 2 * x.W, cq)
-        ops.igemm(plan, x, w, out, act_out=ACT_SILU, out_mode=OUT_PIXEL_SHUFFLE, label=name)
-        return out
-
     def _temporal_down(self, plan, x: Act, mod, name: str, f: int) -> Act:
         """'b c (f p) h w -> b (c p) f h w' + 1x1 conv (iv.py:681-686), p = 2: a two-input GEMM over the even / odd frames."""
         stride = mod.stride
@@ -564,9 +450,7 @@ class UnetEngine3D(UnetEngine):
         even = Act(x.t, n, x.H, x.W, C, C, 2 * fr, x.off)
         odd = Act(x.t, n, x.H, x.W, C, C, 2 * fr, x.off + fr)
         out = self.new(n, x.H, x.W, pw.Cout)
-        out.ssq = self.f32buf(out.rows)
-        if not ops.igemm(plan, even, pw, out, x2=odd, ssq_out=out.ssq, label=name).ssq_emitted:
-            out.ssq = None
+        self._igemm_ssq(plan, even, pw, out, x2=odd, label=name)
         return out
 
     def _temporal_up(self, plan, x: Act, mod, name: str, f: int) -> Act:

@@ -325,7 +325,7 @@ def test_unet_plan_config_sweep(name, reference_weights):
 
 
 def test_unet_plan_with_big_tile_family(reference_weights, monkeypatch):
-    """The planner path of the big-tile all-DMA family (ops.big_cfg -> conv_big.hip; engine._resnet: ACT_PREP in front of it, with the
+    """The planner path of the big-tile all-DMA family (ops.big_cfg -> conv_big.hip; engine._resnet_block1 / _resnet_block2: ACT_PREP in front of it, with the
     statistics reduced by the pass itself where no producer emitted them), which the benchmark-sized layers take on the GPU, forced onto
     a small model (its workgroup threshold lowered): buffer wiring, folded gains and launch order vs the oracle."""
     from imagen_pytorch_amd import ops

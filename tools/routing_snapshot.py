@@ -10,6 +10,8 @@ A record is {"kind", "label", <field>: value ...} of one op: integer fields by v
 null / non-null (addresses differ from run to run); fields that are 0 / null are left out.  IGEMM records also carry what ops.igemm() told
 its caller (ssq_emitted, post_applied, gca_chunks).  The fixture keeps the records of the IGEMM, ROWCHAIN, ACT_PREP and GCA_* ops exactly and in
 order — each distinct one once, as a line of values — and one SHA-256 per plan over the ordered records of every other kind (see digest()).
+tests/golden/routing_wiring.json holds a second view of the same plans: one SHA-256 per plan over wired_records(), which carry the pointer fields
+as ordinals of first use — the buffer wiring.
 """
 from __future__ import annotations
 
@@ -27,6 +29,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 FIXTURE = os.path.join(GOLDEN, "routing_snapshot.json")
+WIRING_FIXTURE = os.path.join(GOLDEN, "routing_wiring.json")   # {plan name: wiring_sha256}: the buffer wiring the other fixture leaves out
 
 README_U1 = dict(dim=32, cond_dim=512, dim_mults=(1, 2, 4, 8), num_resnet_blocks=3, layer_attns=(False, True, True, True),
                  layer_cross_attns=(False, True, True, True))
@@ -62,6 +65,22 @@ def plan_records(plan) -> list:
     return [record(names[kind], p, label) for kind, p, label in plan.ops]
 
 
+def wired_records(plan) -> list:
+    """plan_records with every pointer field as the ordinal of its address among the distinct addresses of the plan, in order of first use
+    (0 = null, left out): which launch reads what which other launch wrote, and at which of its offsets, without the addresses themselves.
+    (A plan keeps every tensor it references alive, so distinct buffers have distinct addresses.)"""
+    seen, out = {}, plan_records(plan)
+    for rec, (_, p, _) in zip(out, plan.ops):
+        for name, ctype in p._fields_:
+            if ctype is ctypes.c_void_p and getattr(p, name):
+                rec[name] = seen.setdefault(getattr(p, name), len(seen) + 1)
+    return out
+
+
+def wiring_sha256(plan) -> str:
+    return hashlib.sha256(json.dumps(wired_records(plan), sort_keys=True).encode()).hexdigest()
+
+
 def _engines():
     """(name, engine) of every covered model, one at a time (the 256^2 engine alone holds a few GB of CPU buffers)."""
     from imagen_pytorch_amd import Unet, Unet3D
@@ -81,13 +100,18 @@ def _engines():
         yield name + "_r4", UnetEngine(u, 4, 2, g["x"].shape[-1], "cpu", dry=True)
 
 
-def snapshot() -> dict:
-    """{plan name: [record of every op, in launch order]}: the step plan of every covered model, and the static plan of the 2D ones."""
+def snapshot(wiring: dict = None) -> dict:
+    """{plan name: [record of every op, in launch order]}: the step plan of every covered model, and the static plan of the 2D ones.
+    `wiring`, if given, receives {plan name: wiring_sha256} of the same plans (every engine is built once)."""
     out = {}
     for name, eng in _engines():
-        out[name + ".step"] = plan_records(eng.step_plan)
+        plans = {name + ".step": eng.step_plan}
         if not name.startswith("c5"):
-            out[name + ".static"] = plan_records(eng._build_static_plan(STATIC_TOKENS)[0])
+            plans[name + ".static"] = eng._build_static_plan(STATIC_TOKENS)[0]
+        for pname, plan in plans.items():
+            out[pname] = plan_records(plan)
+            if wiring is not None:
+                wiring[pname] = wiring_sha256(plan)
     return out
 
 
@@ -185,18 +209,24 @@ def first_difference(old: dict, snap: dict):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--write", action="store_true", help="regenerate tests/golden/routing_snapshot.json from this tree")
+    ap.add_argument("--write", action="store_true", help="regenerate tests/golden/routing_snapshot.json and routing_wiring.json from this tree")
     args = ap.parse_args()
-    snap = snapshot()
+    wiring = {}
+    snap = snapshot(wiring)
     fams, modes = coverage(snap)
     print(f"{len(snap)} plans, {sum(map(len, snap.values()))} ops, {sum(r['kind'] == 'IGEMM' for v in snap.values() for r in v)} igemm launches; "
           f"families {sorted(fams)}, rowchain modes {sorted(modes)}")
     if args.write:
         write(snap)
-        print(f"wrote {FIXTURE} ({os.path.getsize(FIXTURE)} bytes)")
+        with open(WIRING_FIXTURE, "w") as f:
+            json.dump(wiring, f, indent=0)
+            f.write("\n")
+        print(f"wrote {FIXTURE} ({os.path.getsize(FIXTURE)} bytes) and {WIRING_FIXTURE}")
         return 0
-    diff = first_difference(load(), snap)
-    print(diff or "launch lists unchanged")
+    with open(WIRING_FIXTURE) as f:
+        moved = [n for n, h in json.load(f).items() if wiring.get(n) != h]
+    diff = first_difference(load(), snap) or (f"buffer wiring changed (same launch lists): {moved}" if moved else None)
+    print(diff or "launch lists and buffer wiring unchanged")
     return 1 if diff else 0
 
 

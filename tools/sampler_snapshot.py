@@ -5,14 +5,13 @@ fixture models of tests/golden under both samplers (Imagen = DDPM, ElucidatedIma
     python tools/sampler_snapshot.py --write    # regenerate the fixture (a deliberate change of what a stage launches)
 
 The stages are built dry (CPU memory, nothing launched).  A record is tools/routing_snapshot.py's — kind, label, every integer field by value,
-floats as repr() — except that a pointer field holds the ordinal of its address among the distinct addresses of the plan, in order of first
-use (0 = null): which launch reads what which other launch wrote, and at which of its offsets, without the addresses themselves.  The fixture
+floats as repr() — in its wired form (routing_snapshot.wired_records): a pointer field holds the ordinal of its address among the distinct
+addresses of the plan, in order of first use (0 = null).  The fixture
 keeps, per plan, the labels in launch order and one SHA-256 over the ordered records.  tests/test_sampler_snapshot.py asserts equality.
 """
 from __future__ import annotations
 
 import argparse
-import ctypes
 import functools
 import hashlib
 import json
@@ -68,21 +67,6 @@ def _model(which: str, karras: bool):
     return model.eval()
 
 
-def records(plan) -> list:
-    """routing_snapshot.record of every op, pointer fields as ordinals of the plan's distinct addresses."""
-    from imagen_pytorch_amd import _abi
-
-    names = {v: k[len("IMAGEN_OP_"):] for k, v in _abi.ENUMS.items() if k.startswith("IMAGEN_OP_")}
-    seen, out = {}, []
-    for kind, p, label in plan.ops:
-        rec = rs.record(names[kind], p, label)
-        for name, ctype in p._fields_:
-            if ctype is ctypes.c_void_p and getattr(p, name):
-                rec[name] = seen.setdefault(getattr(p, name), len(seen) + 1)
-        out.append(rec)
-    return out
-
-
 def snapshot() -> dict:
     """{"<sampler>.<case>.<plan>": [record, ...]}: `plan` (and `last` for Karras) of the stage, `step` and `static<i>` of its engine."""
     from imagen_pytorch_amd import engine, engine3d
@@ -106,12 +90,12 @@ def snapshot() -> dict:
                 eng.set_conditioning(text_embeds=torch.zeros(B, TOKENS, 32), text_mask=None, keep=keep,
                                      lowres_noise_times=torch.full((B,), 0.2) if idx else None)
                 name = f"{sampler}.{case}"
-                out[name + ".plan"] = records(st["plan"])
+                out[name + ".plan"] = rs.wired_records(st["plan"])
                 if "last" in st:
-                    out[name + ".last"] = records(st["last"])
-                out[name + ".step"] = records(eng.step_plan)
+                    out[name + ".last"] = rs.wired_records(st["last"])
+                out[name + ".step"] = rs.wired_records(eng.step_plan)
                 for i, pl in enumerate(eng._last_static):
-                    out[f"{name}.static{i}"] = records(pl)
+                    out[f"{name}.static{i}"] = rs.wired_records(pl)
     finally:
         engine.UnetEngine, engine3d.UnetEngine3D = saved
     return out
