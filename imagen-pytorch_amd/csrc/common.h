@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
+#include <utility>
 #include "imagen_hip.h"
 #include "lds_dma.h"
 
@@ -13,6 +15,17 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define IMAGEN_WAVE 64
+
+// compile-time loop: f(std::integral_constant<int, I>) for I in [0, N) — keeps every register-array index static (a long `#pragma unroll` body is
+// left rolled, and its arrays then go to scratch)
+template <class F, int... I>
+__device__ __forceinline__ void imagen_static_for_impl(F&& f, std::integer_sequence<int, I...>) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void imagen_static_for(F&& f) {
+  imagen_static_for_impl(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
+}
 
 void imagen_set_error(const char* fmt, ...);
 

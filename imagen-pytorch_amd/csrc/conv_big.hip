@@ -20,24 +20,10 @@
 //   * fragments are prefetched two K steps ahead into three register sets; ring and halo slots are runtime offsets added per read
 //     (two waves per SIMD: the issue slots are there), so ring depth and chunk count need no unrolling.
 // Contract, packed weight layout and epilogue are those of the other families (ImagenIgemmParams; conv_epilogue.h).
-#include <algorithm>
-#include <cstdio>
-#include <type_traits>
-#include <utility>
-#include "common.h"
-#include "conv_families.h"
+#include "conv_launch.h"
 #include "conv_epilogue.h"
 
 namespace {
-
-template <class F, int... I>
-__device__ __forceinline__ void cb_static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void cb_static_for(F&& f) {
-  cb_static_for_impl(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
-}
 
 // direct-to-LDS copies (1 KiB / 256 B per wave instruction), LDS base, barrier and counted vmcnt wait: lds_dma.h
 #define CB_DMA16 IMAGEN_DMA16
@@ -297,9 +283,9 @@ __global__ __launch_bounds__(512, 1) void conv_big_kernel(const ImagenIgemmParam
   CB_BARRIER();
   CB_STAMP(3);
   unsigned wcur = 0, hcur = 0;   // ring / halo byte offsets of the phase being multiplied
-  cb_static_for<2>([&](auto kc) __attribute__((always_inline)) {
+  imagen_static_for<2>([&](auto kc) __attribute__((always_inline)) {
     constexpr int k = decltype(kc)::value;
-    cb_static_for<NI + MI>([&](auto fc) __attribute__((always_inline)) {
+    imagen_static_for<NI + MI>([&](auto fc) __attribute__((always_inline)) {
       read_frag(F[k], decltype(fc)::value, 0, k / KSW, k % KSW, wcur, hcur);
     });
   });
@@ -313,7 +299,7 @@ __global__ __launch_bounds__(512, 1) void conv_big_kernel(const ImagenIgemmParam
   // in phase 3 (c + 2 - HR), ahead of that phase's weight pieces, stage 3 c + 3 in phase 3 c + 4 - WR — not earlier iff WR <= 3 HR - 2.
   static_assert(3 * (HR - 1) + 1 >= WR, "the next chunk's halo must be issued no later than the stage that follows it");
   for (int c = 0; c < NC; ++c) {
-    cb_static_for<3>([&](auto dyc) __attribute__((always_inline)) {
+    imagen_static_for<3>([&](auto dyc) __attribute__((always_inline)) {
       constexpr int dy = decltype(dyc)::value;
       const unsigned wnext = (wcur + WSTAGE == (unsigned)(WR * WSTAGE)) ? 0u : wcur + WSTAGE;
       const unsigned hnext = dy == 2 ? ((hcur + ABUF == (unsigned)(HR * ABUF)) ? 0u : hcur + ABUF) : hcur;
@@ -324,7 +310,7 @@ __global__ __launch_bounds__(512, 1) void conv_big_kernel(const ImagenIgemmParam
       }();
       constexpr int NPIECE = KD + (dy == 0 ? NJ : 0);   // refill pieces of this phase: the halo tile first (dy = 0), then the weights
       static_assert(NPIECE <= 7, "refill pieces fit the filler slots of two K steps");
-      cb_static_for<SPP>([&](auto kc) __attribute__((always_inline)) {
+      imagen_static_for<SPP>([&](auto kc) __attribute__((always_inline)) {
         constexpr int k = decltype(kc)::value;
         constexpr int gstep = dy * SPP + k;             // K step of the chunk (SPP * 3 steps: a multiple of NS)
         constexpr int kk = k + 2;                       // the step whose fragments are read now
@@ -334,7 +320,7 @@ __global__ __launch_bounds__(512, 1) void conv_big_kernel(const ImagenIgemmParam
         constexpr int dy2 = cross ? (dy + 1) % 3 : dy;
         Frags& cur = F[gstep % NS];
         Frags& nx = F[(gstep + 2) % NS];
-        cb_static_for<4>([&](auto gc) __attribute__((always_inline)) {
+        imagen_static_for<4>([&](auto gc) __attribute__((always_inline)) {
           constexpr int g = decltype(gc)::value;
           constexpr int ni = g / MI, mi = g % MI;
           acc[ni][mi] = __builtin_amdgcn_mfma_f32_32x32x16_f16(cur.a[ni], cur.b[mi], acc[ni][mi], 0, 0, 0);
@@ -406,44 +392,28 @@ constexpr CbCfg kCbCfgs[] = {
 };
 constexpr int kNumCbCfgs = sizeof(kCbCfgs) / sizeof(kCbCfgs[0]);
 
-template <int WM, int WN, int KS, int TW, int WR, int HR, bool GEN>
+constexpr long cb_lds_bytes(const CbCfg& c) { return cb_lds_bytes(c.WM, c.WN, c.KS, c.TW, c.WR, c.HR); }
+
+template <int I, bool GEN>
 int cb_launch_gen(const ImagenIgemmParams& p, hipStream_t s) {
-  constexpr int TP = 64 * WM, TH = TP / TW, BN = 64 * WN;
+  constexpr CbCfg c = kCbCfgs[I];
+  constexpr int TW = c.TW, TP = 64 * c.WM, TH = TP / TW, BN = 64 * c.WN;
   IMAGEN_CHECK(p.TH == TH && p.TW == TW, "conv_big: cfg %d has %dx%d tiles (got %dx%d)", p.cfg, TH, TW, p.TH, p.TW);
   IMAGEN_CHECK(p.stride == 1 && p.KH == 3 && p.KW == 3 && p.pad == 1, "conv_big: 3x3 stride-1 convolutions only");
   IMAGEN_CHECK(!p.x2 && p.C2 == 0 && !p.mu && !p.rs && !p.pa && !p.ps && !p.ssq_a && p.act_in == IMAGEN_ACT_NONE,
                "conv_big: single input without prologue only (run ACT_PREP first)");
   IMAGEN_CHECK(p.Cin_pad == p.C1 && p.C1 % 32 == 0 && p.ld1 % 8 == 0, "conv_big: C1 %d must be a multiple of 32 (ld1 %d of 8)", p.C1, p.ld1);
   IMAGEN_CHECK(p.Cout_pad % BN == 0, "conv_big: Cout_pad %d not a multiple of %d", p.Cout_pad, BN);
-  IMAGEN_CHECK(p.out_mode == IMAGEN_OUT_NCHW_F32 || p.Cout % 4 == 0, "conv_big: Cout %d must be a multiple of 4", p.Cout);
-  IMAGEN_CHECK(p.out_mode != IMAGEN_OUT_PIXEL_SHUFFLE || p.Cout % 16 == 0, "conv_big: pixel-shuffle needs Cout %% 16 == 0");
-  IMAGEN_CHECK(!p.post_pa || (p.post_ps && p.out_mode == IMAGEN_OUT_NHWC && p.Cout <= BN && !p.addend && !p.res && !p.ssq_out &&
-                              p.act_out == IMAGEN_ACT_NONE && p.Cout % 4 == 0),
-               "conv_big: post_pa needs post_ps, a plain NHWC output and one workgroup covering all %d output channels (tile has %d)", p.Cout, BN);
-  IMAGEN_CHECK(!(p.addend && p.res), "conv_big: addend and residual are mutually exclusive");
-  IMAGEN_CHECK(!p.gca_part || (p.gca_wk && !GEN && !p.post_pa && p.Cout <= BN), "conv_big: gca_part needs gca_wk, a plain NHWC output and one tile covering all %d couts", p.Cout);
-  IMAGEN_CHECK(!p.ssq_out || (p.out_mode == IMAGEN_OUT_NHWC && p.Cout <= BN),
-               "conv_big: ssq_out needs NHWC output and one workgroup covering all %d output channels (tile has %d)", p.Cout, BN);
-  constexpr size_t lds = (size_t)cb_lds_bytes(WM, WN, KS, TW, WR, HR);
+  if (int r = conv_epilogue_contract("conv_big", p, BN)) return r;
+  constexpr size_t lds = (size_t)cb_lds_bytes(c);
   static_assert(lds <= 160 * 1024, "conv_big: LDS image too large");
-  auto kern = conv_big_kernel<WM, WN, KS, TW, WR, HR, GEN>;
-  static bool attr_done[16] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev >= 0 && dev < 16 && !attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { imagen_set_error("conv_big: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-    attr_done[dev] = true;
-  }
+  constexpr auto kern = conv_big_kernel<c.WM, c.WN, c.KS, c.TW, c.WR, c.HR, GEN>;
+  if (int e = conv_max_dynamic_lds<kern>("conv_big")) return e;
   const int tilesX = (p.OW + TW - 1) / TW, tilesY = (p.OH + TH - 1) / TH;
   const int total = p.B * tilesX * tilesY * ((p.Cout + BN - 1) / BN);
-  // code size of this instantiation (for the kernel's instruction warm-up), looked up once by its mangled name
-  static const unsigned code_q = [] {
-    char name[160];
-    snprintf(name, sizeof(name), "_ZN12_GLOBAL__N_115conv_big_kernelILi%dELi%dELi%dELi%dELi%dELi%dELb%dEEEv17ImagenIgemmParams", WM, WN, KS, TW, WR, HR,
-             GEN ? 1 : 0);
-    return std::min(imagen_kernel_code_bytes(name) >> 8, 0xffffu);
-  }();
+  // code size of this instantiation (for the kernel's instruction warm-up), looked up once
+  static const unsigned code_q = std::min(conv_kernel_code_bytes("_ZN12_GLOBAL__N_115conv_big_kernelILi%dELi%dELi%dELi%dELi%dELi%dELb%dEEEv17ImagenIgemmParams",
+                                                                 c.WM, c.WN, c.KS, c.TW, c.WR, c.HR, GEN) >> 8, 0xffffu);
   ImagenIgemmParams q = p;
   q.launcher_word = (int)code_q;
 #ifdef CB_TRACE
@@ -454,10 +424,22 @@ int cb_launch_gen(const ImagenIgemmParams& p, hipStream_t s) {
   return imagen_hip_status("conv_big launch");
 }
 
-template <int WM, int WN, int KS, int TW, int WR, int HR>
-int cb_launch(const ImagenIgemmParams& p, hipStream_t s) {
-  const bool plain = p.act_out == IMAGEN_ACT_NONE && p.out_mode == IMAGEN_OUT_NHWC && !p.addend && !p.res;
-  return plain ? cb_launch_gen<WM, WN, KS, TW, WR, HR, false>(p, s) : cb_launch_gen<WM, WN, KS, TW, WR, HR, true>(p, s);
+int cb_info(int idx, int* tile_pixels, int* tile_cout, int* kgroups) {
+  if (idx < 0 || idx >= kNumCbCfgs) return -1;
+  return conv_cfg_info(64 * kCbCfgs[idx].WM, 64 * kCbCfgs[idx].WN, 4, tile_pixels, tile_cout, kgroups);
+}
+
+long cb_lds(int idx, int KH, int KW, int TH, int TW) {
+  if (idx < 0 || idx >= kNumCbCfgs || KH != 3 || KW != 3) return -1;
+  const CbCfg& c = kCbCfgs[idx];
+  return (TW == c.TW && TH * TW == 64 * c.WM) ? cb_lds_bytes(c) : -1;
+}
+
+int cb_launch(const ImagenIgemmParams* p, int idx, hipStream_t s) {
+  IMAGEN_CHECK(idx >= 0 && idx < kNumCbCfgs, "conv_big: bad cfg index %d", idx);
+  return cfg_dispatch<kNumCbCfgs>(idx, [&](auto i) {
+    return conv_plain_epilogue(*p) ? cb_launch_gen<decltype(i)::value, false>(*p, s) : cb_launch_gen<decltype(i)::value, true>(*p, s);
+  });
 }
 
 }  // namespace
@@ -466,32 +448,4 @@ int cb_launch(const ImagenIgemmParams& p, hipStream_t s) {
 extern "C" int imagen_debug_conv_big_trace(void* buf) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_cb_trace), &buf, sizeof(buf)); }
 #endif
 
-int imagen_conv_big_num_configs() { return kNumCbCfgs; }
-
-int imagen_conv_big_config_info(int idx, int* tile_pixels, int* tile_cout, int* kgroups) {
-  if (idx < 0 || idx >= kNumCbCfgs) return -1;
-  const CbCfg& c = kCbCfgs[idx];
-  if (tile_pixels) *tile_pixels = 64 * c.WM;
-  if (tile_cout) *tile_cout = 64 * c.WN;
-  if (kgroups) *kgroups = 4;
-  return 0;
-}
-
-long imagen_conv_big_lds_bytes(int idx, int KH, int KW, int TH, int TW) {
-  if (idx < 0 || idx >= kNumCbCfgs || KH != 3 || KW != 3) return -1;
-  const CbCfg& c = kCbCfgs[idx];
-  if (TW != c.TW || TH * TW != 64 * c.WM) return -1;
-  return cb_lds_bytes(c.WM, c.WN, c.KS, c.TW, c.WR, c.HR);
-}
-
-int launch_conv_big(const ImagenIgemmParams* pp, int idx, hipStream_t s) {
-  const ImagenIgemmParams& p = *pp;
-  switch (idx) {
-    case 0: return cb_launch<4, 2, 1, 16, 4, 2>(p, s);
-    case 1: return cb_launch<2, 2, 2, 16, 4, 2>(p, s);
-    case 2: return cb_launch<2, 2, 2, 16, 4, 3>(p, s);
-    case 3: return cb_launch<4, 2, 1, 16, 3, 2>(p, s);
-  }
-  imagen_set_error("conv_big: bad cfg index %d", idx);
-  return -1;
-}
+CONV_FAMILY(kConvBig, 5, kNumCbCfgs, cb_info, cb_lds, cb_launch, 3, 3, nullptr);

@@ -14,23 +14,10 @@
 //   * waves split the output channels (WN-major) and own private weight rings (counted vmcnt, no barrier); the activation double
 //     buffer is handed over by ONE barrier per 32-channel chunk (18 K steps).
 // Contract, packed weight layout and epilogue are those of the other families (ImagenIgemmParams; conv_epilogue.h).
-#include <algorithm>
-#include <type_traits>
-#include <utility>
-#include "common.h"
-#include "conv_families.h"
+#include "conv_launch.h"
 #include "conv_epilogue.h"
 
 namespace {
-
-template <class F, int... I>
-__device__ __forceinline__ void cd_static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void cd_static_for(F&& f) {
-  cd_static_for_impl(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
-}
 
 // direct-to-LDS copy (1 KiB per wave instruction), LDS base and the two barriers: lds_dma.h
 #define cd_dma16 IMAGEN_DMA16
@@ -211,7 +198,7 @@ __global__ __launch_bounds__(256, (MI * NI <= 2 ? 3 : 2)) void conv_dma_kernel(c
 #pragma unroll
   for (int j = 0; j < RW - 1; ++j) dma_weights(j);
   CD_VM0_BARRIER();
-  cd_static_for<NS>([&](auto kc) __attribute__((always_inline)) {   // (set PF is overwritten by the first loop step)
+  imagen_static_for<NS>([&](auto kc) __attribute__((always_inline)) {   // (set PF is overwritten by the first loop step)
     constexpr int k = decltype(kc)::value;
     read_frags(F[k % NS], 0, k / 2, (k / 2) % RW, k % 2);
   });
@@ -231,7 +218,7 @@ __global__ __launch_bounds__(256, (MI * NI <= 2 ? 3 : 2)) void conv_dma_kernel(c
     constexpr int PAR = decltype(parc)::value;
     constexpr int S0 = (9 * PAR) % RW;   // ring slot of tap 0 of this chunk
     const bool last = c + 1 >= NC;
-    cd_static_for<18>([&](auto kc) __attribute__((always_inline)) {
+    imagen_static_for<18>([&](auto kc) __attribute__((always_inline)) {
       constexpr int k = decltype(kc)::value;
       constexpr int t = k / 2, ks = k % 2;
       constexpr int kk = k + PF;                                   // the K step whose fragments are read now
@@ -246,7 +233,7 @@ __global__ __launch_bounds__(256, (MI * NI <= 2 ? 3 : 2)) void conv_dma_kernel(c
       constexpr int NF = R + DA + DW, per = (NF + M - 1) / M;
       Frags& cur = F[(18 * PAR + k) % NS];
       Frags& nx = F[(18 * PAR + kk) % NS];
-      cd_static_for<M>([&](auto gc) __attribute__((always_inline)) {
+      imagen_static_for<M>([&](auto gc) __attribute__((always_inline)) {
         constexpr int g = decltype(gc)::value;
         constexpr int ni = g / MI, mi = g % MI;
         acc[ni][mi] = __builtin_amdgcn_mfma_f32_32x32x16_f16(cur.a[ni], cur.b[mi], acc[ni][mi], 0, 0, 0);
@@ -256,7 +243,7 @@ __global__ __launch_bounds__(256, (MI * NI <= 2 ? 3 : 2)) void conv_dma_kernel(c
           // chunk boundary: every wave's part of the next halo tile has landed, everybody is done reading this one
           if constexpr (kk == 18) CD_LGKM0_BARRIER();
         }
-        cd_static_for<per>([&](auto fc) __attribute__((always_inline)) {
+        imagen_static_for<per>([&](auto fc) __attribute__((always_inline)) {
           constexpr int f = g * per + decltype(fc)::value;
           if constexpr (f < R) {
             if constexpr (kk < 18) read_frag(nx, f, PAR, u, (S0 + u) % RW, kk % 2);
@@ -281,49 +268,6 @@ __global__ __launch_bounds__(256, (MI * NI <= 2 ? 3 : 2)) void conv_dma_kernel(c
 
   cl_epilogue<MI, NI, WM, WN, GEN>(p, tc, acc, pix_y, pix_x, ep_red, reinterpret_cast<float*>(smem), wm, wn, half, l31);
 }
-
-template <int MI, int NI, int WM, int WN, int TW, int RW, int PF, bool GEN>
-int cd_launch_gen(const ImagenIgemmParams& p, hipStream_t s) {
-  constexpr int TP = 32 * MI * WM, TH = TP / TW, BN = 32 * NI * WN;
-  constexpr int NJ = (((TH + 2) * (TW + 2) * 4 + 63) / 64 + 3) / 4;
-  IMAGEN_CHECK(p.TH == TH && p.TW == TW, "conv_dma: cfg %d has %dx%d tiles (got %dx%d)", p.cfg, TH, TW, p.TH, p.TW);
-  IMAGEN_CHECK(p.stride == 1 && p.KH == 3 && p.KW == 3 && p.pad == 1, "conv_dma: 3x3 stride-1 convolutions only");
-  IMAGEN_CHECK(!p.x2 && p.C2 == 0 && !p.mu && !p.rs && !p.pa && !p.ps && !p.ssq_a && p.act_in == IMAGEN_ACT_NONE,
-               "conv_dma: single input without prologue only (run ACT_PREP first)");
-  IMAGEN_CHECK(p.Cin_pad == p.C1 && p.C1 % 32 == 0 && p.ld1 % 8 == 0, "conv_dma: C1 %d must be a multiple of 32 (ld1 %d of 8)", p.C1, p.ld1);
-  IMAGEN_CHECK(p.Cout_pad % BN == 0, "conv_dma: Cout_pad %d not a multiple of %d", p.Cout_pad, BN);
-  IMAGEN_CHECK(p.out_mode == IMAGEN_OUT_NCHW_F32 || p.Cout % 4 == 0, "conv_dma: Cout %d must be a multiple of 4", p.Cout);
-  IMAGEN_CHECK(p.out_mode != IMAGEN_OUT_PIXEL_SHUFFLE || p.Cout % 16 == 0, "conv_dma: pixel-shuffle needs Cout %% 16 == 0");
-  IMAGEN_CHECK(!p.post_pa || (p.post_ps && p.out_mode == IMAGEN_OUT_NHWC && p.Cout <= BN && !p.addend && !p.res && !p.ssq_out &&
-                              p.act_out == IMAGEN_ACT_NONE && p.Cout % 4 == 0),
-               "conv_dma: post_pa needs post_ps, a plain NHWC output and one workgroup covering all %d output channels (tile has %d)", p.Cout, BN);
-  IMAGEN_CHECK(!(p.addend && p.res), "conv_dma: addend and residual are mutually exclusive");
-  IMAGEN_CHECK(!p.gca_part || (p.gca_wk && !GEN && !p.post_pa && p.Cout <= BN), "conv_dma: gca_part needs gca_wk, a plain NHWC output and one tile covering all %d couts", p.Cout);
-  IMAGEN_CHECK(!p.ssq_out || (p.out_mode == IMAGEN_OUT_NHWC && p.Cout <= BN),
-               "conv_dma: ssq_out needs NHWC output and one workgroup covering all %d output channels (tile has %d)", p.Cout, BN);
-  const size_t lds = (size_t)2 * NJ * 4096 + (size_t)4 * RW * (NI * 2048) + (size_t)(4 * 32 * MI) * sizeof(float) + 16;
-  IMAGEN_CHECK(lds <= 160 * 1024, "conv_dma: LDS tile %zu bytes too large", lds);
-  auto kern = conv_dma_kernel<MI, NI, WM, WN, TW, RW, PF, GEN>;
-  static bool attr_done[16] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev >= 0 && dev < 16 && !attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { imagen_set_error("conv_dma: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-    attr_done[dev] = true;
-  }
-  const int tilesX = (p.OW + TW - 1) / TW, tilesY = (p.OH + TH - 1) / TH;
-  const int total = p.B * tilesX * tilesY * ((p.Cout + BN - 1) / BN);
-  hipLaunchKernelGGL(kern, dim3(total), dim3(256), lds, s, p);
-  return imagen_hip_status("conv_dma launch");
-}
-
-template <int MI, int NI, int WM, int WN, int TW, int RW, int PF = 1>
-int cd_launch(const ImagenIgemmParams& p, hipStream_t s) {
-  const bool plain = p.act_out == IMAGEN_ACT_NONE && p.out_mode == IMAGEN_OUT_NHWC && !p.addend && !p.res;
-  return plain ? cd_launch_gen<MI, NI, WM, WN, TW, RW, PF, false>(p, s) : cd_launch_gen<MI, NI, WM, WN, TW, RW, PF, true>(p, s);
-}
-
 
 struct CdCfg { int MI, NI, WM, WN, TW, RW, PF; };
 constexpr CdCfg kCdCfgs[] = {
@@ -350,53 +294,54 @@ constexpr CdCfg kCdCfgs[] = {
 };
 constexpr int kNumCdCfgs = sizeof(kCdCfgs) / sizeof(kCdCfgs[0]);
 
-}  // namespace
-
-int imagen_conv_dma_num_configs() { return kNumCdCfgs; }
-
-int imagen_conv_dma_ring(int idx) { return (idx < 0 || idx >= kNumCdCfgs) ? -1 : kCdCfgs[idx].RW; }
-
-int imagen_conv_dma_config_info(int idx, int* tile_pixels, int* tile_cout, int* kgroups) {
-  if (idx < 0 || idx >= kNumCdCfgs) return -1;
-  const CdCfg& c = kCdCfgs[idx];
-  if (tile_pixels) *tile_pixels = 32 * c.MI * c.WM;
-  if (tile_cout) *tile_cout = 32 * c.NI * c.WN;
-  if (kgroups) *kgroups = 4;
-  return 0;
-}
-
-long imagen_conv_dma_lds_bytes(int idx, int KH, int KW, int TH, int TW) {
-  if (idx < 0 || idx >= kNumCdCfgs || KH != 3 || KW != 3) return -1;
-  const CdCfg& c = kCdCfgs[idx];
-  if (TW != c.TW || TH * TW != 32 * c.MI * c.WM) return -1;
-  const int NJ = (((TH + 2) * (TW + 2) * 4 + 63) / 64 + 3) / 4;
+// dynamic LDS of a row: two halo tiles (NJ DMA rounds of 4 KiB), four wave-private weight rings, the epilogue's reduction scratch
+constexpr long cd_lds_bytes(const CdCfg& c) {
+  const int TH = 32 * c.MI * c.WM / c.TW;
+  const int NJ = (((TH + 2) * (c.TW + 2) * 4 + 63) / 64 + 3) / 4;
   return 2L * NJ * 4096 + 4L * c.RW * (c.NI * 2048) + 4L * 32 * c.MI * 4 + 16;
 }
 
-int launch_conv_dma(const ImagenIgemmParams* pp, int idx, hipStream_t s) {
-  const ImagenIgemmParams& p = *pp;
-  switch (idx) {
-    case 0: return cd_launch<4, 1, 1, 4, 16, 3>(p, s);
-    case 1: return cd_launch<4, 1, 1, 4, 16, 6>(p, s);
-    case 2: return cd_launch<2, 1, 1, 4, 8, 3>(p, s);
-    case 3: return cd_launch<2, 1, 1, 4, 8, 6>(p, s);
-    case 4: return cd_launch<2, 2, 1, 4, 8, 3>(p, s);
-    case 5: return cd_launch<2, 2, 1, 4, 8, 6>(p, s);
-    case 6: return cd_launch<4, 1, 2, 2, 16, 3>(p, s);
-    case 7: return cd_launch<2, 1, 2, 2, 16, 3>(p, s);
-    case 8: return cd_launch<2, 1, 2, 2, 16, 6>(p, s);
-    case 9: return cd_launch<1, 1, 2, 2, 8, 6>(p, s);
-    case 10: return cd_launch<2, 1, 4, 1, 16, 3>(p, s);
-    case 11: return cd_launch<1, 1, 4, 1, 16, 3>(p, s);
-    case 12: return cd_launch<2, 1, 1, 4, 8, 9>(p, s);
-    case 13: return cd_launch<4, 1, 1, 4, 16, 6, 2>(p, s);
-    case 14: return cd_launch<4, 1, 1, 4, 16, 6, 3>(p, s);
-    case 15: return cd_launch<2, 2, 1, 4, 8, 6, 2>(p, s);
-    case 16: return cd_launch<2, 1, 1, 4, 8, 6, 2>(p, s);
-    case 17: return cd_launch<2, 1, 1, 4, 8, 6, 3>(p, s);
-    case 18: return cd_launch<2, 1, 2, 2, 16, 6, 2>(p, s);
-    case 19: return cd_launch<4, 1, 2, 2, 16, 6, 2>(p, s);
-  }
-  imagen_set_error("conv_dma: bad cfg index %d", idx);
-  return -1;
+template <int I, bool GEN>
+int cd_launch_gen(const ImagenIgemmParams& p, hipStream_t s) {
+  constexpr CdCfg c = kCdCfgs[I];
+  constexpr int TW = c.TW, TP = 32 * c.MI * c.WM, TH = TP / TW, BN = 32 * c.NI * c.WN;
+  IMAGEN_CHECK(p.TH == TH && p.TW == TW, "conv_dma: cfg %d has %dx%d tiles (got %dx%d)", p.cfg, TH, TW, p.TH, p.TW);
+  IMAGEN_CHECK(p.stride == 1 && p.KH == 3 && p.KW == 3 && p.pad == 1, "conv_dma: 3x3 stride-1 convolutions only");
+  IMAGEN_CHECK(!p.x2 && p.C2 == 0 && !p.mu && !p.rs && !p.pa && !p.ps && !p.ssq_a && p.act_in == IMAGEN_ACT_NONE,
+               "conv_dma: single input without prologue only (run ACT_PREP first)");
+  IMAGEN_CHECK(p.Cin_pad == p.C1 && p.C1 % 32 == 0 && p.ld1 % 8 == 0, "conv_dma: C1 %d must be a multiple of 32 (ld1 %d of 8)", p.C1, p.ld1);
+  IMAGEN_CHECK(p.Cout_pad % BN == 0, "conv_dma: Cout_pad %d not a multiple of %d", p.Cout_pad, BN);
+  if (int r = conv_epilogue_contract("conv_dma", p, BN)) return r;
+  constexpr long lds = cd_lds_bytes(c);
+  IMAGEN_CHECK(lds <= 160 * 1024, "conv_dma: LDS tile %ld bytes too large", lds);
+  constexpr auto kern = conv_dma_kernel<c.MI, c.NI, c.WM, c.WN, c.TW, c.RW, c.PF, GEN>;
+  if (int e = conv_max_dynamic_lds<kern>("conv_dma")) return e;
+  const int tilesX = (p.OW + TW - 1) / TW, tilesY = (p.OH + TH - 1) / TH;
+  const int total = p.B * tilesX * tilesY * ((p.Cout + BN - 1) / BN);
+  hipLaunchKernelGGL(kern, dim3(total), dim3(256), lds, s, p);
+  return imagen_hip_status("conv_dma launch");
 }
+
+int cd_info(int idx, int* tile_pixels, int* tile_cout, int* kgroups) {
+  if (idx < 0 || idx >= kNumCdCfgs) return -1;
+  return conv_cfg_info(32 * kCdCfgs[idx].MI * kCdCfgs[idx].WM, 32 * kCdCfgs[idx].NI * kCdCfgs[idx].WN, 4, tile_pixels, tile_cout, kgroups);
+}
+
+long cd_lds(int idx, int KH, int KW, int TH, int TW) {
+  if (idx < 0 || idx >= kNumCdCfgs || KH != 3 || KW != 3) return -1;
+  const CdCfg& c = kCdCfgs[idx];
+  return (TW == c.TW && TH * TW == 32 * c.MI * c.WM) ? cd_lds_bytes(c) : -1;
+}
+
+int cd_ring(int idx) { return (idx < 0 || idx >= kNumCdCfgs) ? -1 : kCdCfgs[idx].RW; }
+
+int cd_launch(const ImagenIgemmParams* p, int idx, hipStream_t s) {
+  IMAGEN_CHECK(idx >= 0 && idx < kNumCdCfgs, "conv_dma: bad cfg index %d", idx);
+  return cfg_dispatch<kNumCdCfgs>(idx, [&](auto i) {
+    return conv_plain_epilogue(*p) ? cd_launch_gen<decltype(i)::value, false>(*p, s) : cd_launch_gen<decltype(i)::value, true>(*p, s);
+  });
+}
+
+}  // namespace
+
+CONV_FAMILY(kConvDma, 2, kNumCdCfgs, cd_info, cd_lds, cd_launch, 3, 3, cd_ring);

@@ -19,11 +19,7 @@
 //     ssq_out / post_pa / GlobalContext partials where one tile covers all couts).
 // Contract: ImagenIgemmParams with KH = KW = 1, stride 1, pad 0; C1, C2 multiples of 32, Cin_pad = C1 + C2; act_in NONE; no ssq_a
 // statistics (mu / rs only).  The packed weight layout of a 1x1 layer is the same for every G >= 2 (consecutive 8-channel group rows).
-#include <algorithm>
-#include <type_traits>
-#include <utility>
-#include "common.h"
-#include "conv_families.h"
+#include "conv_launch.h"
 #include "conv_epilogue.h"
 
 namespace {
@@ -219,40 +215,23 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_kernel(const ImagenIgemmPara
 
 template <bool PRO, bool GEN>
 int cg_launch(const ImagenIgemmParams& p, hipStream_t s) {
-  auto kern = conv_gemm_kernel<PRO, GEN>;
+  constexpr auto kern = conv_gemm_kernel<PRO, GEN>;
   const size_t lds = cg_lds_bytes(p.Cin_pad, PRO);
-  static bool attr_done[16] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 16 || !attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { imagen_set_error("conv_gemm: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-    if (dev >= 0 && dev < 16) attr_done[dev] = true;
-  }
+  if (int e = conv_max_dynamic_lds<kern>("conv_gemm")) return e;
   const int tilesX = (p.OW + p.TW - 1) / p.TW, tilesY = (p.OH + p.TH - 1) / p.TH, tilesN = (p.Cout + CG_BN - 1) / CG_BN;
   const int total = p.B * tilesY * tilesX * tilesN;
   hipLaunchKernelGGL(kern, dim3(total), dim3(256), lds, s, p);
   return imagen_hip_status("conv_gemm launch");
 }
 
-}  // namespace
+int cg_info(int idx, int* tile_pixels, int* tile_cout, int* kgroups) { return idx != 0 ? -1 : conv_cfg_info(CG_TP, CG_BN, 4, tile_pixels, tile_cout, kgroups); }
 
-int imagen_conv_gemm_num_configs() { return 1; }
-
-int imagen_conv_gemm_config_info(int idx, int* tile_pixels, int* tile_cout, int* kgroups) {
-  if (idx != 0) return -1;
-  if (tile_pixels) *tile_pixels = CG_TP;
-  if (tile_cout) *tile_cout = CG_BN;
-  if (kgroups) *kgroups = 4;
-  return 0;
-}
-
-long imagen_conv_gemm_lds_bytes(int idx, int KH, int KW, int TH, int TW) {
+long cg_lds(int idx, int KH, int KW, int TH, int TW) {
   if (idx != 0 || KH != 1 || KW != 1 || TH * TW != CG_TP) return -1;
-  return (long)cg_lds_bytes(1024, true);   // (upper bound: the prologue's affine tables grow with Cin)
+  return (long)cg_lds_bytes(1024, true);   // (a typical layer: the prologue's affine tables grow with Cin, and the real figure is checked at launch)
 }
 
-int launch_conv_gemm(const ImagenIgemmParams* pp, int idx, hipStream_t s) {
+int cg_launch_cfg(const ImagenIgemmParams* pp, int idx, hipStream_t s) {
   const ImagenIgemmParams& p = *pp;
   IMAGEN_CHECK(idx == 0, "conv_gemm: bad cfg index %d", idx);
   IMAGEN_CHECK(p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && p.OH == p.H && p.OW == p.W, "conv_gemm: 1x1 stride-1 convolutions only");
@@ -264,19 +243,14 @@ int launch_conv_gemm(const ImagenIgemmParams* pp, int idx, hipStream_t s) {
   IMAGEN_CHECK(p.Cout_pad % CG_BN == 0, "conv_gemm: Cout_pad %d not a multiple of %d", p.Cout_pad, CG_BN);
   IMAGEN_CHECK(!p.ssq_a && !p.ssq_b && p.act_in == IMAGEN_ACT_NONE, "conv_gemm: the prologue is (x - mu) * rs * pa + ps (no ssq statistics, no input activation)");
   IMAGEN_CHECK(!p.mu || p.rs, "conv_gemm: mu needs rs");
-  IMAGEN_CHECK(p.out_mode == IMAGEN_OUT_NCHW_F32 || p.Cout % 4 == 0, "conv_gemm: Cout %d must be a multiple of 4", p.Cout);
-  IMAGEN_CHECK(p.out_mode != IMAGEN_OUT_PIXEL_SHUFFLE || p.Cout % 16 == 0, "conv_gemm: pixel-shuffle needs Cout %% 16 == 0");
-  IMAGEN_CHECK(!(p.addend && p.res), "conv_gemm: addend and residual are mutually exclusive");
-  IMAGEN_CHECK(!p.addend || p.gate, "conv_gemm: addend requires gate");
-  const bool full = p.ssq_out || p.post_pa || p.gca_part;
-  IMAGEN_CHECK(!full || p.Cout <= CG_BN, "conv_gemm: ssq_out / post_pa / gca_part need one tile over all %d couts", p.Cout);
-  IMAGEN_CHECK(!p.post_pa || (p.post_ps && p.out_mode == IMAGEN_OUT_NHWC && !p.addend && !p.res && !p.ssq_out && p.act_out == IMAGEN_ACT_NONE),
-               "conv_gemm: post_pa needs post_ps and a plain NHWC output");
-  IMAGEN_CHECK(!p.gca_part || (p.gca_wk && !p.post_pa && p.out_mode == IMAGEN_OUT_NHWC && !p.addend && !p.res && p.act_out == IMAGEN_ACT_NONE),
-               "conv_gemm: gca_part needs gca_wk and a plain NHWC output");
+  if (int r = conv_epilogue_contract("conv_gemm", p, CG_BN, CONV_EP_SSQ_ANY_LAYOUT)) return r;
   const bool pro = p.mu || p.rs || p.pa || p.ps;
-  const bool plain = p.act_out == IMAGEN_ACT_NONE && p.out_mode == IMAGEN_OUT_NHWC && !p.addend && !p.res;
+  const bool plain = conv_plain_epilogue(p);
   IMAGEN_CHECK((long)cg_lds_bytes(p.Cin_pad, pro) <= 160 * 1024, "conv_gemm: LDS");
   if (pro) return plain ? cg_launch<true, false>(p, s) : cg_launch<true, true>(p, s);
   return plain ? cg_launch<false, false>(p, s) : cg_launch<false, true>(p, s);
 }
+
+}  // namespace
+
+CONV_FAMILY(kConvGemm, 7, 1, cg_info, cg_lds, cg_launch_cfg, 1, 1, nullptr);

@@ -22,21 +22,9 @@
 //     per-image operands are refreshed once or twice per workgroup.
 // Epilogue: plain NHWC fp16 (+ the per-pixel sum of squares, 32 couts), or the output-side Block prologue post_pa / post_ps.
 // Everything else (addend / residual / other output modes / other channel counts) stays with the other families: the planner asks.
-#include <algorithm>
-#include <utility>
-#include "common.h"
-#include "conv_families.h"
+#include "conv_launch.h"
 
 namespace {
-
-template <class F, int... I>
-__device__ __forceinline__ void cp_static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void cp_static_for(F&& f) {   // f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): compile-time indices
-  cp_static_for_impl(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});   // (a 54-step `#pragma unroll` body is left rolled: arrays then go to scratch)
-}
 
 constexpr int CP_TW = 16, CP_TH = 8, CP_ITW = CP_TW + 2, CP_ITH = CP_TH + 2;
 constexpr int CP_NPX = CP_ITH * CP_ITW;          // 180 halo pixels
@@ -160,7 +148,7 @@ __global__ __launch_bounds__(256 * NCO, WPS) void conv_pro_kernel(const ImagenIg
     }
   };
   auto request = [&](Raw& R, const Tile& c) __attribute__((always_inline)) {
-    cp_static_for<NU>([&](auto ic) __attribute__((always_inline)) { request_unit(R, c, decltype(ic)::value / NCH, decltype(ic)::value % NCH); });
+    imagen_static_for<NU>([&](auto ic) __attribute__((always_inline)) { request_unit(R, c, decltype(ic)::value / NCH, decltype(ic)::value % NCH); });
   };
 
   // per-image operands -> parameter set b & 1 (two consecutive images can be live: tile t in b, tile t + 1 in b + 1)
@@ -238,7 +226,7 @@ __global__ __launch_bounds__(256 * NCO, WPS) void conv_pro_kernel(const ImagenIg
   request(RA, cur);
   {
     Unit U;
-    cp_static_for<NU * 6>([&](auto ic) __attribute__((always_inline)) { transform_part(RA, U, decltype(ic)::value / 6, decltype(ic)::value % 6, 0, cur.b); });
+    imagen_static_for<NU * 6>([&](auto ic) __attribute__((always_inline)) { transform_part(RA, U, decltype(ic)::value / 6, decltype(ic)::value % 6, 0, cur.b); });
   }
   Tile nxt = tile_at(min(t_begin + 1, t_end - 1));
   request(RA, nxt);
@@ -275,7 +263,7 @@ __global__ __launch_bounds__(256 * NCO, WPS) void conv_pro_kernel(const ImagenIg
     bfr[0] = bfrag(0);
     if constexpr (NR == 0) afr[0] = afrag(0);
     Unit U;
-    cp_static_for<STEPS>([&](auto sc) __attribute__((always_inline)) {
+    imagen_static_for<STEPS>([&](auto sc) __attribute__((always_inline)) {
       constexpr int s = decltype(sc)::value;
       if constexpr (s + 1 < STEPS) {      // the fragments of step s + 1 are requested before the MFMA of step s
         bfr[(s + 1) & 1] = bfrag(s + 1);
@@ -362,22 +350,14 @@ __global__ __launch_bounds__(256 * NCO, WPS) void conv_pro_kernel(const ImagenIg
 //   96 -> 64 : <3, 2, 2>  1 workgroup of 8 waves / CU   (chunks 1, 2 from LDS: 72 KB, six tile images 68 KB)
 template <int NCH, int NCO, int WL, bool PRO, int WPS>
 int cp_launch(const ImagenIgemmParams& p, hipStream_t s) {
-  auto kern = conv_pro_kernel<NCH, NCO, WL, PRO, WPS>;
+  constexpr auto kern = conv_pro_kernel<NCH, NCO, WL, PRO, WPS>;
   constexpr size_t lds = cp_lds_bytes(NCH, NCO, WL);
   static_assert(lds <= 160 * 1024, "LDS budget");
-  static bool attr_done[16] = {};
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 16 || !attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { imagen_set_error("conv_pro: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-    if (dev >= 0 && dev < 16) attr_done[dev] = true;
-  }
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  if (int e = conv_max_dynamic_lds<kern>("conv_pro")) return e;
   const int tilesX = (p.OW + CP_TW - 1) / CP_TW, tilesY = (p.OH + CP_TH - 1) / CP_TH;
   const int total = p.B * tilesX * tilesY;
   const int per_cu = std::max(1, std::min(WPS / NCO, (int)((160 * 1024) / lds)));
-  int resident = std::max(8, std::max(1, cus) * per_cu);
+  int resident = std::max(8, conv_num_cus() * per_cu);
   resident -= resident % 8;                                     // (the XCD dealing of the tile ranges wants a multiple of 8)
   int tiles_per_wg = std::max(1, (total + resident - 1) / resident);
   tiles_per_wg += tiles_per_wg & 1;                             // (tiles go in pairs: an odd range would compute its last tile twice)
@@ -387,25 +367,17 @@ int cp_launch(const ImagenIgemmParams& p, hipStream_t s) {
   return imagen_hip_status("conv_pro launch");
 }
 
-}  // namespace
-
 // ---- family interface (igemm.hip lists this family behind the big-tile one): cfg 0 = 32 output channels, cfg 1 = 64
-int imagen_conv_pro_num_configs() { return 2; }
-
-int imagen_conv_pro_config_info(int idx, int* tile_pixels, int* tile_cout, int* kgroups) {
-  if (idx < 0 || idx > 1) return -1;
-  if (tile_pixels) *tile_pixels = CP_TH * CP_TW;
-  if (tile_cout) *tile_cout = 32 * (idx + 1);
-  if (kgroups) *kgroups = 4;
-  return 0;
+int cp_info(int idx, int* tile_pixels, int* tile_cout, int* kgroups) {
+  return (idx < 0 || idx > 1) ? -1 : conv_cfg_info(CP_TH * CP_TW, 32 * (idx + 1), 4, tile_pixels, tile_cout, kgroups);
 }
 
-long imagen_conv_pro_lds_bytes(int idx, int KH, int KW, int TH, int TW) {
+long cp_lds(int idx, int KH, int KW, int TH, int TW) {   // (of the widest instantiation of the cfg)
   if (idx < 0 || idx > 1 || KH != 3 || KW != 3 || TH != CP_TH || TW != CP_TW) return -1;
   return idx == 0 ? (long)cp_lds_bytes(2, 1, 1) : (long)cp_lds_bytes(3, 2, 2);
 }
 
-int launch_conv_pro(const ImagenIgemmParams* pp, int idx, hipStream_t s) {
+int cp_launch_cfg(const ImagenIgemmParams* pp, int idx, hipStream_t s) {
   const ImagenIgemmParams& p = *pp;
   IMAGEN_CHECK(idx == 0 || idx == 1, "conv_pro: bad cfg");
   const int nco = idx + 1;
@@ -423,10 +395,9 @@ int launch_conv_pro(const ImagenIgemmParams* pp, int idx, hipStream_t s) {
   const bool pro = p.ssq_a != nullptr || p.pa != nullptr || p.ps != nullptr || p.act_in != IMAGEN_ACT_NONE;
   IMAGEN_CHECK(!pro || (p.ssq_a && p.pa && p.act_in == IMAGEN_ACT_SILU && ((p.C2 == 0) == (p.ssq_b == nullptr))),
                "conv_pro: the prologue is ssq_a (+ ssq_b with a second tensor) statistics, pa (ps), SiLU");
-  IMAGEN_CHECK(p.out_mode == IMAGEN_OUT_NHWC && !p.addend && !p.res && p.act_out == IMAGEN_ACT_NONE && !p.gca_part,
-               "conv_pro: plain NHWC output only (no addend / residual / output activation / GlobalContext partials)");
+  IMAGEN_CHECK(conv_plain_epilogue(p), "conv_pro: plain NHWC output only (no addend / residual / output activation)");   // (the kernel has its own epilogue: no generic path)
   IMAGEN_CHECK(p.ldy % 8 == 0 && p.bsy % 8 == 0 && ((size_t)p.y & 15) == 0, "conv_pro: output rows must keep 16-byte alignment");
-  IMAGEN_CHECK(!p.post_pa || (p.post_ps && !p.ssq_out), "conv_pro: post_pa needs post_ps and excludes ssq_out");
+  if (int r = conv_epilogue_contract("conv_pro", p, 32 * nco, CONV_EP_NO_GCA)) return r;
   IMAGEN_CHECK(!p.ssq_out || nco == 1, "conv_pro: ssq_out with 32 output channels only");
   switch (nco * 100 + nch * 10 + (pro ? 1 : 0)) {
     case 110: return cp_launch<1, 1, 0, false, 2>(p, s);
@@ -439,3 +410,7 @@ int launch_conv_pro(const ImagenIgemmParams* pp, int idx, hipStream_t s) {
     default: return cp_launch<3, 2, 2, true, 2>(p, s);
   }
 }
+
+}  // namespace
+
+CONV_FAMILY(kConvPro, 6, 2, cp_info, cp_lds, cp_launch_cfg, 3, 3, nullptr);

@@ -15,9 +15,7 @@
 //     reads back conflict-free (slot = channel group ^ ((pixel >> 2) & 3): checked exhaustively for all eight waves);
 //   * operands and outputs move in 16-byte pieces (imagen_pair_quads / imagen_unpair_quads, common.h).
 // Contract: ImagenIgemmParams with KH = KW = 1, stride 1, no prologue, plain NHWC output, C1 and C2 multiples of 32.
-#include <algorithm>
-#include "common.h"
-#include "conv_families.h"
+#include "conv_launch.h"
 
 namespace {
 
@@ -220,34 +218,6 @@ __global__ __launch_bounds__(64 * PW_NW, 2) void conv_pw_kernel(const ImagenIgem
   }
 }
 
-template <int NI, int KCH, int WN>
-int pw_launch(const ImagenIgemmParams& p, hipStream_t s) {
-  constexpr int PW_TP = 32 * PW_NW / WN, PW_CH = PW_TP * 64;
-  const size_t lds = (size_t)2 * KCH * PW_CH + (size_t)(2 * 32 * NI * WN + PW_TP) * sizeof(float);
-  auto kern = conv_pw_kernel<NI, KCH, WN>;
-  static bool attr_done[16] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 16 || !attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { imagen_set_error("conv_pw: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-    if (dev >= 0 && dev < 16) attr_done[dev] = true;
-  }
-  const int tiles_img = (p.OH * p.OW + PW_TP - 1) / PW_TP;
-  const int total = p.B * tiles_img;
-  int cus = 256;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const int per_cu = lds <= 80 * 1024 ? 2 : 1;
-  const int resident = std::max(1, cus * per_cu);
-  int gx = total;
-  if (total > resident) {   // even rounds: every workgroup walks the same number of tiles (+-1)
-    const int rounds = (total + resident - 1) / resident;
-    gx = (total + rounds - 1) / rounds;
-  }
-  hipLaunchKernelGGL(kern, dim3(gx), dim3(64 * PW_NW), lds, s, p);
-  return imagen_hip_status("conv_pw launch");
-}
-
 struct PwCfg { int NI, KCH, WN; };
 constexpr PwCfg kPwCfgs[] = {
     {1, 2, 1},   // 0: 256 px,  64 -> <= 32 channels
@@ -259,52 +229,56 @@ constexpr PwCfg kPwCfgs[] = {
 };
 constexpr int kNumPwCfgs = sizeof(kPwCfgs) / sizeof(kPwCfgs[0]);
 
-}  // namespace
+constexpr int pw_tile_pixels(const PwCfg& c) { return 32 * PW_NW / c.WN; }
+constexpr int pw_tile_cout(const PwCfg& c) { return 32 * c.NI * c.WN; }
+// dynamic LDS of a row: two tiles of KCH 32-channel chunks, [bias | gate | ssq partials]
+constexpr long pw_lds_bytes(const PwCfg& c) { return 2L * c.KCH * pw_tile_pixels(c) * 64 + (2L * pw_tile_cout(c) + pw_tile_pixels(c)) * (long)sizeof(float); }
 
-int imagen_conv_pw_num_configs() { return kNumPwCfgs; }
+template <int I>
+int pw_launch_cfg(const ImagenIgemmParams& p, hipStream_t s) {
+  constexpr PwCfg c = kPwCfgs[I];
+  constexpr size_t lds = (size_t)pw_lds_bytes(c);
+  constexpr auto kern = conv_pw_kernel<c.NI, c.KCH, c.WN>;
+  if (int e = conv_max_dynamic_lds<kern>("conv_pw")) return e;
+  const int total = p.B * ((p.OH * p.OW + pw_tile_pixels(c) - 1) / pw_tile_pixels(c));
+  const int gx = conv_even_rounds_grid(total, conv_num_cus() * (lds <= 80 * 1024 ? 2 : 1));
+  hipLaunchKernelGGL(kern, dim3(gx), dim3(64 * PW_NW), lds, s, p);
+  return imagen_hip_status("conv_pw launch");
+}
 
 // tile_cout: output channels one workgroup covers; kgroups: the number of 32-channel input chunks the instantiation is built for (the
 // packed weight layout of a 1x1 layer is the same for every G >= 2: consecutive 8-channel group rows)
-int imagen_conv_pw_config_info(int idx, int* tile_pixels, int* tile_cout, int* kchunks) {
+int pw_info(int idx, int* tile_pixels, int* tile_cout, int* kchunks) {
   if (idx < 0 || idx >= kNumPwCfgs) return -1;
-  if (tile_pixels) *tile_pixels = 32 * PW_NW / kPwCfgs[idx].WN;
-  if (tile_cout) *tile_cout = 32 * kPwCfgs[idx].NI * kPwCfgs[idx].WN;
-  if (kchunks) *kchunks = kPwCfgs[idx].KCH;
-  return 0;
+  return conv_cfg_info(pw_tile_pixels(kPwCfgs[idx]), pw_tile_cout(kPwCfgs[idx]), kPwCfgs[idx].KCH, tile_pixels, tile_cout, kchunks);
 }
 
-long imagen_conv_pw_lds_bytes(int idx, int KH, int KW, int TH, int TW) {
-  if (idx < 0 || idx >= kNumPwCfgs || KH != 1 || KW != 1) return -1;
-  const PwCfg c = kPwCfgs[idx];
-  const int tp = 32 * PW_NW / c.WN;
-  if (TH * TW != tp) return -1;
-  return 2L * c.KCH * tp * 64 + (2L * 32 * c.NI * c.WN + tp) * (long)sizeof(float);
+long pw_lds(int idx, int KH, int KW, int TH, int TW) {
+  if (idx < 0 || idx >= kNumPwCfgs || KH != 1 || KW != 1 || TH * TW != pw_tile_pixels(kPwCfgs[idx])) return -1;
+  return pw_lds_bytes(kPwCfgs[idx]);
 }
 
-int launch_conv_pw(const ImagenIgemmParams* pp, int idx, hipStream_t s) {
+int pw_launch(const ImagenIgemmParams* pp, int idx, hipStream_t s) {
   const ImagenIgemmParams& p = *pp;
   IMAGEN_CHECK(idx >= 0 && idx < kNumPwCfgs, "conv_pw: bad cfg index %d", idx);
   const PwCfg c = kPwCfgs[idx];
+  const int BN = pw_tile_cout(c);
   IMAGEN_CHECK(p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && p.OH == p.H && p.OW == p.W, "conv_pw: 1x1 stride-1 convolutions only");
-  IMAGEN_CHECK(!p.mu && !p.rs && !p.pa && !p.ps && !p.ssq_a && p.act_in == IMAGEN_ACT_NONE && p.act_out == IMAGEN_ACT_NONE && !p.post_pa && !p.gca_part,
-               "conv_pw: no prologue, no output activation, no post_pa / gca_part");
+  IMAGEN_CHECK(!p.mu && !p.rs && !p.pa && !p.ps && !p.ssq_a && p.act_in == IMAGEN_ACT_NONE && p.act_out == IMAGEN_ACT_NONE && !p.post_pa,
+               "conv_pw: no prologue, no output activation, no post_pa");
   IMAGEN_CHECK(p.out_mode == IMAGEN_OUT_NHWC, "conv_pw: NHWC output only");
   IMAGEN_CHECK(p.C1 % 32 == 0 && p.C2 % 32 == 0 && (p.C1 + p.C2) == 32 * c.KCH && p.Cin_pad == p.C1 + p.C2 && (p.C2 == 0 || p.x2),
                "conv_pw: cfg %d takes %d input channels in 32-channel chunks (got %d + %d)", idx, 32 * c.KCH, p.C1, p.C2);
-  IMAGEN_CHECK(p.Cout <= 32 * c.NI * c.WN && p.Cout % 8 == 0 && p.Cout_pad >= 32 * c.NI * c.WN, "conv_pw: cfg %d covers %d output channels (Cout %d, padded %d)",
-               idx, 32 * c.NI * c.WN, p.Cout, p.Cout_pad);
+  IMAGEN_CHECK(p.Cout <= BN && p.Cout % 8 == 0 && p.Cout_pad >= BN, "conv_pw: cfg %d covers %d output channels (Cout %d, padded %d)", idx, BN, p.Cout, p.Cout_pad);
+  if (int r = conv_epilogue_contract("conv_pw", p, BN, CONV_EP_NO_GCA)) return r;
   IMAGEN_CHECK(p.ld1 % 8 == 0 && (p.C2 == 0 || p.ld2 % 8 == 0) && p.ldy % 8 == 0 && p.bsy % 8 == 0 && ((size_t)p.y & 15) == 0,
                "conv_pw: strides must keep 16-byte alignment");
-  IMAGEN_CHECK(!(p.addend && p.res), "conv_pw: addend and residual are mutually exclusive");
   IMAGEN_CHECK(!p.addend || (p.gate && p.ld_add % 8 == 0 && p.bs_add % 8 == 0 && ((size_t)p.addend & 15) == 0), "conv_pw: addend needs gate and 16-byte aligned rows");
   IMAGEN_CHECK(!p.res || (p.ld_res % 8 == 0 && p.bs_res % 8 == 0 && ((size_t)p.res & 15) == 0), "conv_pw: residual rows must be 16-byte aligned");
-  switch (idx) {
-    case 0: return pw_launch<1, 2, 1>(p, s);
-    case 1: return pw_launch<2, 3, 1>(p, s);
-    case 2: return pw_launch<2, 2, 1>(p, s);
-    case 3: return pw_launch<1, 3, 1>(p, s);
-    case 4: return pw_launch<2, 6, 2>(p, s);
-    case 5: return pw_launch<2, 4, 2>(p, s);
-  }
-  return -1;
+  return cfg_dispatch<kNumPwCfgs>(idx, [&](auto i) { return pw_launch_cfg<decltype(i)::value>(p, s); });
 }
+
+}  // namespace
+
+CONV_FAMILY(kConvPw, 4, kNumPwCfgs, pw_info, pw_lds, pw_launch, 1, 1, nullptr);
+

@@ -31,9 +31,7 @@
 // Contract: ImagenIgemmParams with KH = KW = 3, stride 1, pad 1, G = 4 packing — or KH = KW = 1, pad 0, any G >= 2 (one tap, no halo: the 1x1
 // res_conv / upsample GEMMs of the same maps; the packed rows of a 1x1 layer are consecutive 8-channel groups for every G); C1 % 8 == 0, C1 + C2 == Cin_pad (a multiple of 32);
 // output tiles of 32 pixels as 4 x 8, 2 x 16 or 1 x 32 (partial tiles at the map's edge are masked).
-#include <cstdio>
-#include "common.h"
-#include "conv_families.h"
+#include "conv_launch.h"
 #include "conv_epilogue.h"
 
 namespace {
@@ -390,22 +388,11 @@ __global__ __launch_bounds__(CS_THREADS, CS_MINW) void conv_small_kernel(const I
 
 template <int NT, bool PRO, bool GEN>
 int cs_launch(const ImagenIgemmParams& p, hipStream_t s) {
-  auto kern = conv_small_kernel<NT, PRO, GEN>;
+  constexpr auto kern = conv_small_kernel<NT, PRO, GEN>;
   const size_t lds = cs_lds_bytes<NT>(p.TH, p.TW, p.Cin_pad);
   IMAGEN_CHECK(lds <= 160 * 1024, "conv_small: %zu bytes of LDS (Cin_pad %d)", lds, p.Cin_pad);
-  static bool attr_done[16] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 16 || !attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { imagen_set_error("conv_small: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-    if (dev >= 0 && dev < 16) attr_done[dev] = true;
-  }
-  static const unsigned code_bytes = [] {
-    char name[160];
-    snprintf(name, sizeof(name), "_ZN12_GLOBAL__N_117conv_small_kernelILi%dELb%dELb%dEEEv17ImagenIgemmParamsj", NT, PRO ? 1 : 0, GEN ? 1 : 0);
-    return imagen_kernel_code_bytes(name);
-  }();
+  if (int e = conv_max_dynamic_lds<kern>("conv_small")) return e;
+  static const unsigned code_bytes = conv_kernel_code_bytes("_ZN12_GLOBAL__N_117conv_small_kernelILi%dELb%dELb%dEEEv17ImagenIgemmParamsj", NT, PRO, GEN);
   const int total = p.B * ((p.OH + p.TH - 1) / p.TH) * ((p.OW + p.TW - 1) / p.TW) * ((p.Cout + 32 * NT - 1) / (32 * NT));
   hipLaunchKernelGGL(kern, dim3(total), dim3(CS_THREADS), lds, s, p, code_bytes);
   return imagen_hip_status("conv_small launch");
@@ -414,35 +401,23 @@ int cs_launch(const ImagenIgemmParams& p, hipStream_t s) {
 template <int NT>
 int cs_dispatch(const ImagenIgemmParams& p, hipStream_t s) {
   const bool pro = p.mu || p.rs || p.pa || p.ps || p.ssq_a || p.act_in != IMAGEN_ACT_NONE;
-  const bool plain = p.act_out == IMAGEN_ACT_NONE && p.out_mode == IMAGEN_OUT_NHWC && !p.addend && !p.res;
+  const bool plain = conv_plain_epilogue(p);
   if (pro) return plain ? cs_launch<NT, true, false>(p, s) : cs_launch<NT, true, true>(p, s);
   return plain ? cs_launch<NT, false, false>(p, s) : cs_launch<NT, false, true>(p, s);
 }
 
 constexpr int kCsNT[3] = {1, 2, 4};
 
-}  // namespace
-
-#ifdef CS_TRACE
-extern "C" int imagen_debug_conv_small_trace(void* buf) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_cs_trace), &buf, sizeof(buf)); }
-#endif
-
-int imagen_conv_small_num_configs() { return 3; }
-
-int imagen_conv_small_config_info(int idx, int* tile_pixels, int* tile_cout, int* kgroups) {
-  if (idx < 0 || idx >= 3) return -1;
-  if (tile_pixels) *tile_pixels = 32;
-  if (tile_cout) *tile_cout = 32 * kCsNT[idx];
-  if (kgroups) *kgroups = 4;
-  return 0;
+int cs_info(int idx, int* tile_pixels, int* tile_cout, int* kgroups) {
+  return (idx < 0 || idx >= 3) ? -1 : conv_cfg_info(32, 32 * kCsNT[idx], 4, tile_pixels, tile_cout, kgroups);
 }
 
-long imagen_conv_small_lds_bytes(int idx, int KH, int KW, int TH, int TW) {
+long cs_lds(int idx, int KH, int KW, int TH, int TW) {
   if (idx < 0 || idx >= 3 || KH != KW || (KH != 3 && KH != 1) || TH * TW != 32 || (TW != 8 && TW != 16 && TW != 32)) return -1;
   return (long)cs_lds_bytes<1>(TH, TW, 256);   // (a typical layer: the real figure grows with Cin and is checked at launch)
 }
 
-int launch_conv_small(const ImagenIgemmParams* pp, int idx, hipStream_t s) {
+int cs_launch_cfg(const ImagenIgemmParams* pp, int idx, hipStream_t s) {
   const ImagenIgemmParams& p = *pp;
   IMAGEN_CHECK(idx >= 0 && idx < 3, "conv_small: bad cfg index %d", idx);
   IMAGEN_CHECK(((p.KH == 3 && p.KW == 3 && p.pad == 1) || (p.KH == 1 && p.KW == 1 && p.pad == 0)) && p.stride == 1 && p.OH == p.H && p.OW == p.W,
@@ -457,19 +432,18 @@ int launch_conv_small(const ImagenIgemmParams* pp, int idx, hipStream_t s) {
   IMAGEN_CHECK(p.act_in == IMAGEN_ACT_NONE || p.act_in == IMAGEN_ACT_SILU, "conv_small: input activation none | SiLU");
   IMAGEN_CHECK(!p.mu || p.rs, "conv_small: mu needs rs");
   IMAGEN_CHECK(p.pstride == 0 || p.pstride >= p.Cin_pad || (!p.pa && !p.ps), "conv_small: per-batch affine rows shorter than Cin_pad");
-  IMAGEN_CHECK(p.out_mode == IMAGEN_OUT_NCHW_F32 || p.Cout % 4 == 0, "conv_small: Cout %d must be a multiple of 4", p.Cout);
-  IMAGEN_CHECK(p.out_mode != IMAGEN_OUT_PIXEL_SHUFFLE || p.Cout % 16 == 0, "conv_small: pixel-shuffle needs Cout %% 16 == 0");
-  IMAGEN_CHECK(!(p.addend && p.res), "conv_small: addend and residual are mutually exclusive");
-  IMAGEN_CHECK(!p.addend || p.gate, "conv_small: addend requires gate");
-  const bool full = p.ssq_out || p.post_pa || p.gca_part;
-  IMAGEN_CHECK(!full || p.Cout <= 32 * NT, "conv_small: ssq_out / post_pa / gca_part need one tile over all %d couts", p.Cout);
-  IMAGEN_CHECK(!p.post_pa || (p.post_ps && p.out_mode == IMAGEN_OUT_NHWC && !p.addend && !p.res && !p.ssq_out && p.act_out == IMAGEN_ACT_NONE),
-               "conv_small: post_pa needs post_ps and a plain NHWC output");
-  IMAGEN_CHECK(!p.gca_part || (p.gca_wk && !p.post_pa && p.out_mode == IMAGEN_OUT_NHWC && !p.addend && !p.res && p.act_out == IMAGEN_ACT_NONE),
-               "conv_small: gca_part needs gca_wk and a plain NHWC output");
+  if (int r = conv_epilogue_contract("conv_small", p, 32 * NT, CONV_EP_SSQ_ANY_LAYOUT)) return r;
   switch (NT) {
     case 1: return cs_dispatch<1>(p, s);
     case 2: return cs_dispatch<2>(p, s);
     default: return cs_dispatch<4>(p, s);
   }
 }
+
+}  // namespace
+
+#ifdef CS_TRACE
+extern "C" int imagen_debug_conv_small_trace(void* buf) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_cs_trace), &buf, sizeof(buf)); }
+#endif
+
+CONV_FAMILY(kConvSmall, 8, 3, cs_info, cs_lds, cs_launch_cfg, 3, 3, nullptr);   // (3, 3 although the kernel also runs 1x1: imagen_igemm_stage_slots() has always answered 0 for those)

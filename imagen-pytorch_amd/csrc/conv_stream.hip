@@ -16,10 +16,8 @@
 //     IN PLACE on the landed tile (ds_read_b128 -> fp32 math -> ds_write_b128) by all eight waves, with the per-pixel statistics
 //     of tile t+1 prefetched into registers together with its DMA.
 // Contract, packed weight layout and epilogue are those of the other families (ImagenIgemmParams; conv_epilogue.h).
-#include <algorithm>
 #include <cstdlib>
-#include "common.h"
-#include "conv_families.h"
+#include "conv_launch.h"
 #include "conv_epilogue.h"
 
 namespace {
@@ -383,50 +381,26 @@ __global__ __launch_bounds__(64 * CS_NW, NCH == 1 ? 4 : 2) void conv_stream_kern
 
 template <int NCH, bool PRO, bool GEN>
 int cs_launch_gen(const ImagenIgemmParams& p, hipStream_t s) {
-  auto kern = conv_stream_kernel<NCH, PRO, GEN>;
+  constexpr auto kern = conv_stream_kernel<NCH, PRO, GEN>;
   constexpr size_t lds = cs_lds_bytes(NCH);
-  static bool attr_done[16] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 16 || !attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { imagen_set_error("conv_stream: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-    if (dev >= 0 && dev < 16) attr_done[dev] = true;
-  }
+  if (int e = conv_max_dynamic_lds<kern>("conv_stream")) return e;
   const int tilesX = (p.OW + CS_TW - 1) / CS_TW, tilesY = (p.OH + CS_TH - 1) / CS_TH;
-  const int total = p.B * tilesX * tilesY;
-  int cus = 256;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const int per_cu = NCH == 1 ? 2 : 1;
-  const int resident = std::max(1, std::max(1, cus) * per_cu);
-  int gx = total;
-  if (total > resident) {   // even rounds: every workgroup walks the same number of tiles (+-1)
-    const int rounds = (total + resident - 1) / resident;
-    gx = (total + rounds - 1) / rounds;
-  }
+  const int gx = conv_even_rounds_grid(p.B * tilesX * tilesY, conv_num_cus() * (NCH == 1 ? 2 : 1));
   hipLaunchKernelGGL(kern, dim3(gx), dim3(64 * CS_NW), lds, s, p);
   return imagen_hip_status("conv_stream launch");
 }
 
-}  // namespace
-
 // ---- family interface (igemm.hip lists this family behind the all-DMA one)
-int imagen_conv_stream_num_configs() { return 1; }
-
-int imagen_conv_stream_config_info(int idx, int* tile_pixels, int* tile_cout, int* kgroups) {
-  if (idx != 0) return -1;
-  if (tile_pixels) *tile_pixels = CS_TH * CS_TW;
-  if (tile_cout) *tile_cout = 32;
-  if (kgroups) *kgroups = 4;
-  return 0;
+int cs_info(int idx, int* tile_pixels, int* tile_cout, int* kgroups) {
+  return idx != 0 ? -1 : conv_cfg_info(CS_TH * CS_TW, 32, 4, tile_pixels, tile_cout, kgroups);
 }
 
-long imagen_conv_stream_lds_bytes(int idx, int KH, int KW, int TH, int TW) {
+long cs_lds(int idx, int KH, int KW, int TH, int TW) {   // (of the two-input instantiation: the larger one)
   if (idx != 0 || KH != 3 || KW != 3 || TH != CS_TH || TW != CS_TW) return -1;
   return (long)cs_lds_bytes(2);
 }
 
-int launch_conv_stream(const ImagenIgemmParams* pp, int idx, hipStream_t s) {
+int cs_launch(const ImagenIgemmParams* pp, int idx, hipStream_t s) {
   const ImagenIgemmParams& p = *pp;
   IMAGEN_CHECK(idx == 0, "conv_stream: bad cfg");
   IMAGEN_CHECK(p.TH == CS_TH && p.TW == CS_TW, "conv_stream: 16x16 tiles (got %dx%d)", p.TH, p.TW);
@@ -439,15 +413,8 @@ int launch_conv_stream(const ImagenIgemmParams* pp, int idx, hipStream_t s) {
   const bool pro = p.ssq_a != nullptr || p.pa != nullptr || p.ps != nullptr || p.act_in != IMAGEN_ACT_NONE;
   IMAGEN_CHECK(!pro || (p.ssq_a && p.pa && (p.act_in == IMAGEN_ACT_NONE || p.act_in == IMAGEN_ACT_SILU)),
                "conv_stream: the prologue needs ssq_a and pa (act_in NONE | SILU)");
-  IMAGEN_CHECK(p.out_mode == IMAGEN_OUT_NCHW_F32 || p.Cout % 4 == 0, "conv_stream: Cout %d must be a multiple of 4", p.Cout);
-  IMAGEN_CHECK(p.out_mode != IMAGEN_OUT_PIXEL_SHUFFLE || p.Cout % 16 == 0, "conv_stream: pixel-shuffle needs Cout %% 16 == 0");
-  IMAGEN_CHECK(!p.post_pa || (p.post_ps && p.out_mode == IMAGEN_OUT_NHWC && !p.addend && !p.res && !p.ssq_out && p.act_out == IMAGEN_ACT_NONE && p.Cout % 4 == 0),
-               "conv_stream: post_pa needs post_ps and a plain NHWC output");
-  IMAGEN_CHECK(!(p.addend && p.res), "conv_stream: addend and residual are mutually exclusive");
-  IMAGEN_CHECK(!p.gca_part, "conv_stream: no GlobalContext partials from this family (its eight-wave epilogue with three barriers per tile cost more than the pass it replaced: round 4, call F) — families 2, 5, 7, 8 emit them");
-  IMAGEN_CHECK(!p.ssq_out || p.out_mode == IMAGEN_OUT_NHWC, "conv_stream: ssq_out needs NHWC output");
-  const bool plain = p.act_out == IMAGEN_ACT_NONE && p.out_mode == IMAGEN_OUT_NHWC && !p.addend && !p.res;
-  const int key = (p.C2 ? 4 : 0) | (pro ? 2 : 0) | (plain ? 0 : 1);
+  if (int r = conv_epilogue_contract("conv_stream", p, 32, CONV_EP_NO_GCA)) return r;
+  const int key = (p.C2 ? 4 : 0) | (pro ? 2 : 0) | (conv_plain_epilogue(p) ? 0 : 1);
   switch (key) {
     case 0: return cs_launch_gen<1, false, false>(p, s);
     case 1: return cs_launch_gen<1, false, true>(p, s);
@@ -459,3 +426,7 @@ int launch_conv_stream(const ImagenIgemmParams* pp, int idx, hipStream_t s) {
     default: return cs_launch_gen<2, true, true>(p, s);
   }
 }
+
+}  // namespace
+
+CONV_FAMILY(kConvStream, 3, 1, cs_info, cs_lds, cs_launch, 3, 3, nullptr);

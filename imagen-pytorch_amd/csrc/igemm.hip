@@ -12,13 +12,8 @@
 // The k dimension runs over channel chunks of 8*G channels; inside a chunk over (tap, 8-channel group) pairs; two consecutive
 // groups (lane>>5 selects) feed one K=16 MFMA.  A "phase" = (tile, chunk); one s_barrier per phase hands an LDS buffer from the
 // producers to the consumers.
-#include <algorithm>
-#include <cstdio>
 #include <cstdlib>
-#include <type_traits>
-#include <utility>
-#include "common.h"
-#include "conv_families.h"
+#include "conv_launch.h"
 
 namespace {
 
@@ -62,20 +57,14 @@ constexpr TileCfg kCfgs[] = {
 };
 constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
 
-// compile-time loop: f(std::integral_constant<int, I>) for I in [0, N) — keeps every register-array index static
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  static_for_impl(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
-}
-
+constexpr int stage_pixel_bytes(int G) { return G == 1 ? 16 : G * 16 + 16; }   // LDS bytes per staged pixel (16B pad: conflict-free ds_read_b128)
 template <int G> struct Geo {
   static constexpr int KC = 8 * G;                          // channels per chunk
-  static constexpr int PS = (G == 1) ? 16 : (G * 16 + 16);  // LDS bytes per staged pixel (16B pad: conflict-free ds_read_b128)
+  static constexpr int PS = stage_pixel_bytes(G);
 };
+
+// dynamic LDS bytes of a launch: the staging double buffer of IT halo pixels + epilogue scratch + bias + dummy
+constexpr long igemm_lds_bytes(int IT, int G, int MI) { return 2L * IT * stage_pixel_bytes(G) + (long)(4 * 32 * MI + kBiasLds) * (long)sizeof(float) + 16; }
 
 // KSC > 0: the number of K=16 steps per channel chunk is a compile-time constant (18 for 3x3 convs with 32-channel
 // chunks, 2 for 1x1 / linear, 8 for the 2x2 stride-2 downsample): the k-loop is fully unrolled so the weight-fragment ring is
@@ -241,7 +230,7 @@ __global__ __launch_bounds__(512, (MI * NI <= 2 ? 4 : 2)) void igemm_kernel(cons
       const int ld = from1 ? ld1_s : ld2_s;
       const int sp0 = b * (p.H * p.W);
       int iy = iy_first, ix = ix_first;
-      static_for<kMaxItems>([&](auto ic) __attribute__((always_inline)) {
+      imagen_static_for<kMaxItems>([&](auto ic) __attribute__((always_inline)) {
         constexpr int it = decltype(ic)::value;
         const int gy = iy0 + iy, gx = ix0 + ix;
         const bool ok = chan_ok && iy < ITH && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W;   // iy >= ITH: slot beyond the tile
@@ -276,7 +265,7 @@ __global__ __launch_bounds__(512, (MI * NI <= 2 ? 4 : 2)) void igemm_kernel(cons
     const bool use_mu = p.mu != nullptr, use_silu = p.act_in == IMAGEN_ACT_SILU;
     auto write_set = [&](const StageSet& S, char* buf) __attribute__((always_inline)) {
       if (raw_copy) {   // input already activated by its producer (post_pa epilogue) or a plain GEMM operand: zero-fill only
-        static_for<kMaxItems>([&](auto ic) __attribute__((always_inline)) {
+        imagen_static_for<kMaxItems>([&](auto ic) __attribute__((always_inline)) {
           constexpr int it = decltype(ic)::value;
           const int idx = rtid + it * 256;
           const uint4 v = (S.mask & (1u << it)) ? S.raw[it] : make_uint4(0, 0, 0, 0);
@@ -287,7 +276,7 @@ __global__ __launch_bounds__(512, (MI * NI <= 2 ? 4 : 2)) void igemm_kernel(cons
       }
       const float a[8] = {st_a0.x, st_a0.y, st_a0.z, st_a0.w, st_a1.x, st_a1.y, st_a1.z, st_a1.w};
       const float s[8] = {st_s0.x, st_s0.y, st_s0.z, st_s0.w, st_s1.x, st_s1.y, st_s1.z, st_s1.w};
-      static_for<kMaxItems>([&](auto ic) __attribute__((always_inline)) {
+      imagen_static_for<kMaxItems>([&](auto ic) __attribute__((always_inline)) {
         constexpr int it = decltype(ic)::value;
         const int idx = rtid + it * 256;
         const f16x8 in = *reinterpret_cast<const f16x8*>(&S.raw[it]);
@@ -458,7 +447,7 @@ __global__ __launch_bounds__(512, (MI * NI <= 2 ? 4 : 2)) void igemm_kernel(cons
       for (int ni = 0; ni < NI; ++ni) wq[kLookAhead - 1][ni] = wnew[ni];
     };
     if constexpr (KSC > 0) {
-      static_for<KSC>([&](auto ic) __attribute__((always_inline)) { do_step(decltype(ic)::value); });
+      imagen_static_for<KSC>([&](auto ic) __attribute__((always_inline)) { do_step(decltype(ic)::value); });
     } else {
       for (int ks = 0; ks < KS; ++ks) do_step(ks);
     }
@@ -717,9 +706,9 @@ __global__ __launch_bounds__(512, (MI * NI <= 2 ? 4 : 2)) void igemm_kernel(cons
 #pragma unroll
           for (int mi = 0; mi < MI; ++mi) imagen_unpair_quads(raw[ni][qp][mi], E[ni * 4 + qp].ar[mi], E[ni * 4 + qp + 2].ar[mi]);
     } else {
-      static_for<4 * NI>([&](auto gc) __attribute__((always_inline)) { load_group(decltype(gc)::value, E[decltype(gc)::value]); });
+      imagen_static_for<4 * NI>([&](auto gc) __attribute__((always_inline)) { load_group(decltype(gc)::value, E[decltype(gc)::value]); });
     }
-    static_for<4 * NI>([&](auto gc) __attribute__((always_inline)) {
+    imagen_static_for<4 * NI>([&](auto gc) __attribute__((always_inline)) {
       constexpr int g = decltype(gc)::value;
       constexpr int ni = g >> 2, q = g & 3;
       EpiOps& cur = E[g];
@@ -909,23 +898,12 @@ __global__ __launch_bounds__(512, (MI * NI <= 2 ? 4 : 2)) void igemm_kernel(cons
   }
 }
 
-inline int num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-    else n = 256;
-  }
-  return n;
-}
-
 template <int MI, int NI, int WM, int WN, int G, int KSC, bool GEN>
 int launch_gen(const ImagenIgemmParams& p, hipStream_t s);
 
 template <int MI, int NI, int WM, int WN, int G, int KSC>
 int launch_ksc(const ImagenIgemmParams& p, hipStream_t s) {
-  const bool plain = p.act_out == IMAGEN_ACT_NONE && p.out_mode == IMAGEN_OUT_NHWC && !p.addend && !p.res &&
-                     (p.bias == nullptr || p.Cout_pad <= kBiasLds);
+  const bool plain = conv_plain_epilogue(p) && (p.bias == nullptr || p.Cout_pad <= kBiasLds);   // (the plain epilogue keeps the bias in LDS)
   return plain ? launch_gen<MI, NI, WM, WN, G, KSC, false>(p, s) : launch_gen<MI, NI, WM, WN, G, KSC, true>(p, s);
 }
 
@@ -941,25 +919,11 @@ int launch_gen(const ImagenIgemmParams& p, hipStream_t s) {
   IMAGEN_CHECK(p.Cin_pad % (8 * G) == 0, "igemm: Cin_pad %d not a multiple of %d", p.Cin_pad, 8 * G);
   IMAGEN_CHECK(p.C1 % 8 == 0 && p.C2 % 8 == 0 && p.ld1 % 8 == 0 && (p.x2 == nullptr || p.ld2 % 8 == 0),
                "igemm: channel counts / strides must be multiples of 8 (C1=%d C2=%d ld1=%d ld2=%d)", p.C1, p.C2, p.ld1, p.ld2);
-  IMAGEN_CHECK(p.out_mode == IMAGEN_OUT_NCHW_F32 || p.Cout % 4 == 0, "igemm: Cout %d must be a multiple of 4", p.Cout);
-  IMAGEN_CHECK(p.out_mode != IMAGEN_OUT_PIXEL_SHUFFLE || p.Cout % 16 == 0, "igemm: pixel-shuffle needs Cout %% 16 == 0");
-  IMAGEN_CHECK(!p.post_pa || (p.post_ps && p.out_mode == IMAGEN_OUT_NHWC && p.Cout <= BN && !p.addend && !p.res && !p.ssq_out &&
-                              p.act_out == IMAGEN_ACT_NONE && p.Cout % 4 == 0),
-               "igemm: post_pa needs post_ps, a plain NHWC output and one workgroup covering all %d output channels (tile has %d)", p.Cout, BN);
-  IMAGEN_CHECK(!(p.addend && p.res), "igemm: addend and residual are mutually exclusive");
-  IMAGEN_CHECK(!p.ssq_out || (p.out_mode == IMAGEN_OUT_NHWC && p.Cout <= BN),
-               "igemm: ssq_out needs NHWC output and one workgroup covering all %d output channels (tile has %d)", p.Cout, BN);
-  const size_t lds = (size_t)2 * IT * Geo<G>::PS + (size_t)(4 * 32 * MI + kBiasLds) * sizeof(float) + 16;   // staging double buffer + epilogue scratch + bias + dummy
+  if (int r = conv_epilogue_contract("igemm", p, BN, CONV_EP_NO_GCA)) return r;
+  const size_t lds = (size_t)igemm_lds_bytes(IT, G, MI);
   IMAGEN_CHECK(lds <= 160 * 1024, "igemm: LDS tile %zu bytes too large", lds);
-  auto kern = igemm_kernel<MI, NI, WM, WN, G, KSC, GEN>;
-  static bool attr_done[16] = {};   // the attribute is per DEVICE (a process may sample on several GPUs)
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 16 || !attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) { imagen_set_error("igemm: hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-    if (dev >= 0 && dev < 16) attr_done[dev] = true;
-  }
+  constexpr auto kern = igemm_kernel<MI, NI, WM, WN, G, KSC, GEN>;
+  if (int e = conv_max_dynamic_lds<kern>("igemm")) return e;
   // persistent grid: what the chip holds at once (register- and LDS-limited workgroups per CU), evened out over the rounds
   const int tilesX = (p.OW + p.TW - 1) / p.TW, tilesY = (p.OH + p.TH - 1) / p.TH;
   const int total = p.B * tilesX * tilesY * ((p.Cout + BN - 1) / BN);
@@ -973,22 +937,12 @@ int launch_gen(const ImagenIgemmParams& p, hipStream_t s) {
   }
   // (persistent grids capped at ONE workgroup per CU, to leave registers / LDS for the other lanes' kernels, were measured in round 3's
   // call C: sequential +7 %, lanes throughput unchanged — not kept)
-  const int resident = std::max(8, num_cus() * occ_blocks / 8 * 8);
-  int gx;
-  if (total <= resident) {
-    gx = total;
-  } else {
-    const int rounds = (total + resident - 1) / resident;
-    gx = (total + rounds - 1) / rounds;
-    gx = std::min(resident, (gx + 7) / 8 * 8);     // multiple of 8: one contiguous tile range per XCD
-  }
-  // code size of this instantiation (for the kernel's instruction warm-up), looked up once by its mangled name
-  static const unsigned code_q = [] {
-    char name[160];
-    snprintf(name, sizeof(name), "_ZN12_GLOBAL__N_112igemm_kernelILi%dELi%dELi%dELi%dELi%dELi%dELb%dEEEv17ImagenIgemmParams", MI, NI, WM, WN, G, KSC,
-             GEN ? 1 : 0);
-    return std::min(imagen_kernel_code_bytes(name) >> 8, 0xffffu);
-  }();
+  const int resident = std::max(8, conv_num_cus() * occ_blocks / 8 * 8);
+  int gx = conv_even_rounds_grid(total, resident);
+  if (total > resident) gx = std::min(resident, (gx + 7) / 8 * 8);     // multiple of 8: one contiguous tile range per XCD
+  // code size of this instantiation (for the kernel's instruction warm-up), looked up once
+  static const unsigned code_q = std::min(conv_kernel_code_bytes("_ZN12_GLOBAL__N_112igemm_kernelILi%dELi%dELi%dELi%dELi%dELi%dELb%dEEEv17ImagenIgemmParams",
+                                                                 MI, NI, WM, WN, G, KSC, GEN) >> 8, 0xffffu);
   ImagenIgemmParams q = p;
   q.launcher_word = (int)code_q;
   hipLaunchKernelGGL(kern, dim3(gx), dim3(512), lds, s, q);
@@ -1017,35 +971,27 @@ int launch_cfg(const ImagenIgemmParams& p, hipStream_t s) {
 
 // The other kernel families, in tile cfg id order: family 0 owns the ids below kNumCfgs, each of these the next num() ids.  The ids are visible
 // to the planner (imagen_igemm_config_info / _config_family rows): a new family goes at the END.
-static const ConvFamily kFamilies[] = {
-    {2, imagen_conv_dma_num_configs, imagen_conv_dma_config_info, imagen_conv_dma_lds_bytes, launch_conv_dma, 3, 3, imagen_conv_dma_ring},
-    {3, imagen_conv_stream_num_configs, imagen_conv_stream_config_info, imagen_conv_stream_lds_bytes, launch_conv_stream, 3, 3, nullptr},
-    {4, imagen_conv_pw_num_configs, imagen_conv_pw_config_info, imagen_conv_pw_lds_bytes, launch_conv_pw, 1, 1, nullptr},
-    {5, imagen_conv_big_num_configs, imagen_conv_big_config_info, imagen_conv_big_lds_bytes, launch_conv_big, 3, 3, nullptr},
-    {6, imagen_conv_pro_num_configs, imagen_conv_pro_config_info, imagen_conv_pro_lds_bytes, launch_conv_pro, 3, 3, nullptr},
-    {7, imagen_conv_gemm_num_configs, imagen_conv_gemm_config_info, imagen_conv_gemm_lds_bytes, launch_conv_gemm, 1, 1, nullptr},
-    {8, imagen_conv_small_num_configs, imagen_conv_small_config_info, imagen_conv_small_lds_bytes, launch_conv_small, 3, 3, nullptr},   // (3, 3 although the kernel also runs 1x1: imagen_igemm_stage_slots() has always answered 0 for those)
-};
+static const ConvFamily* const kFamilies[] = {&kConvDma, &kConvStream, &kConvPw, &kConvBig, &kConvPro, &kConvGemm, &kConvSmall};
 
 struct CfgRef {
   const ConvFamily* fam;   // nullptr: family 0 (or a negative id)
-  int idx;                 // the family's own index; at or past fam->num() for an id behind the last one (every family's functions range-check it)
+  int idx;                 // the family's own index; at or past fam->num for an id behind the last one (every family's functions range-check it)
 };
 
 static CfgRef cfg_ref(int cfg) {
   CfgRef r = {nullptr, cfg};
   int base = kNumCfgs;
-  for (const ConvFamily& f : kFamilies) {
+  for (const ConvFamily* f : kFamilies) {
     if (cfg < base) break;
-    r = {&f, cfg - base};
-    base += f.num();
+    r = {f, cfg - base};
+    base += f->num;
   }
   return r;
 }
 
 static int cfg_end() {
   int n = kNumCfgs;
-  for (const ConvFamily& f : kFamilies) n += f.num();
+  for (const ConvFamily* f : kFamilies) n += f->num;
   return n;
 }
 
@@ -1081,25 +1027,10 @@ int launch_igemm(const ImagenIgemmParams* pp, hipStream_t s) {
                "igemm: post_pa / post_ps rows must start on 16 bytes (post_pstride %d, %p %p)", p.post_pstride, p.post_pa, p.post_ps);
   const CfgRef r = cfg_ref(p.cfg);
   if (r.fam) return r.fam->launch(pp, r.idx, s);
-  switch (p.cfg) {
-    case 0: return launch_cfg<2, 1, 4, 1, 4>(p, s);
-    case 1: return launch_cfg<4, 1, 1, 4, 4>(p, s);
-    case 2: return launch_cfg<4, 1, 2, 2, 4>(p, s);
-    case 3: return launch_cfg<2, 1, 1, 4, 4>(p, s);
-    case 4: return launch_cfg<1, 1, 4, 1, 4>(p, s);
-    case 5: return launch_cfg<2, 1, 4, 1, 1>(p, s);
-    case 6: return launch_cfg<1, 1, 2, 2, 4>(p, s);
-    case 7: return launch_cfg<1, 2, 2, 2, 1>(p, s);
-    case 8: return launch_cfg<1, 1, 2, 2, 1>(p, s);
-    case 9: return launch_cfg<1, 1, 4, 1, 1>(p, s);
-    case 10: return launch_cfg<2, 1, 1, 4, 16>(p, s);
-    case 11: return launch_cfg<4, 1, 1, 4, 8>(p, s);
-    case 12: return launch_cfg<1, 1, 2, 2, 16>(p, s);
-    case 13: return launch_cfg<1, 1, 4, 1, 8>(p, s);
-    case 14: return launch_cfg<2, 1, 1, 4, 8>(p, s);
-    case 15: return launch_cfg<1, 1, 2, 2, 8>(p, s);
-  }
-  return -1;
+  return cfg_dispatch<kNumCfgs>(p.cfg, [&](auto i) {
+    constexpr TileCfg c = kCfgs[decltype(i)::value];
+    return launch_cfg<c.MI, c.NI, c.WM, c.WN, c.G>(p, s);
+  });
 }
 
 extern "C" int imagen_igemm_num_configs(void) { return cfg_end(); }
@@ -1121,10 +1052,7 @@ extern "C" int imagen_igemm_config_info(int cfg, int* tile_pixels, int* tile_cou
   if (r.fam) return r.fam->info(r.idx, tile_pixels, tile_cout, kgroups);
   if (cfg < 0 || cfg >= kNumCfgs) return -1;
   const TileCfg& c = kCfgs[cfg];
-  if (tile_pixels) *tile_pixels = 32 * c.MI * c.WM;
-  if (tile_cout) *tile_cout = 32 * c.NI * c.WN;
-  if (kgroups) *kgroups = c.G;
-  return 0;
+  return conv_cfg_info(32 * c.MI * c.WM, 32 * c.NI * c.WN, c.G, tile_pixels, tile_cout, kgroups);
 }
 
 static constexpr int ksc_of(int G, int ks) {   // the launch_cfg dispatch, as a function
@@ -1152,8 +1080,7 @@ extern "C" long imagen_igemm_lds_bytes(int cfg, int KH, int KW, int stride, int 
   if (TH * TW != 32 * c.MI * c.WM) return -1;
   const int IT = ((TH - 1) * stride + KH) * ((TW - 1) * stride + KW);
   if (IT * c.G > imagen_igemm_stage_slots(cfg, KH, KW) * 256) return -1;
-  const long PS = c.G == 1 ? 16 : c.G * 16 + 16;
-  const long lds = 2 * IT * PS + (long)(4 * 32 * c.MI + kBiasLds) * (long)sizeof(float) + 16;
+  const long lds = igemm_lds_bytes(IT, c.G, c.MI);
   return lds <= 160 * 1024 ? lds : -1;
 }
 

@@ -340,9 +340,15 @@ def _takes(fam, poke):
 def test_refusals(ops, dev, fam, poke):
     """Just outside: one stride or base of an otherwise valid launch moved off its alignment.  The launch returns an error (checked by status
     only) and nothing is written; the unmoved launch is a passing case of the tests above."""
-    from imagen_pytorch_amd._abi import ImagenHipError
-
     name, ep, Cout, field, delta, needs = poke
+    plan, p, O = _valid_launch(ops, dev, fam, ep, Cout, needs)
+    assert needs != "small" or p.pstride == p.Cin_pad
+    setattr(p, field, (getattr(p, field) or 0) + delta)
+    _refused(plan, O)
+
+
+def _valid_launch(ops, dev, fam, ep, Cout, needs, **kw):
+    """A launch the family takes (a passing case of the tests above), built and not yet run: (plan, params, outputs)."""
     tag, cfg, base = forms(ops, fam)[0]
     c = dict(DEFAULTS, **base)
     c.update(B=2, H=5, W=9, Cout=Cout, epilogue=ep, C2=32 if needs == "two" or fam in (4, 7) else 0)
@@ -352,12 +358,102 @@ def test_refusals(ops, dev, fam, poke):
         c.update(pro_of(fam), pstride_extra=0)
         if fam == 6:
             c.update(SSQ)
+    c.update(kw)
     cid = resolve(ops, fam, cfg, c)
     T = build(c)
-    plan, p, O = launch(ops, dev, c, T, (cid,) + tile_shape(ops, fam, cid, T["OH"], T["OW"], c["K"], 1))
-    assert needs != "small" or p.pstride == p.Cin_pad
-    setattr(p, field, (getattr(p, field) or 0) + delta)
+    return launch(ops, dev, c, T, (cid,) + tile_shape(ops, fam, cid, T["OH"], T["OW"], c["K"], 1))
+
+
+def _refused(plan, O):
+    from imagen_pytorch_amd._abi import ImagenHipError
+
     with pytest.raises(ImagenHipError):
         plan.run()
     torch.cuda.synchronize()
-    O["gy"].check(torch.zeros(O["gy"].numel, dtype=torch.bool))
+    for g in ("gy", "gs", "gg"):
+        if g in O:
+            O[g].check(torch.zeros(O[g].numel, dtype=torch.bool))
+
+
+# ------------------------------------------------------------------------------------------------ the launchers' contract predicates
+
+def _set(**fields):
+    """Poke: fields set to a constant, or (a string) to the value of another field — a pointer to a buffer the launch already holds."""
+    def f(ops, p):
+        for k, v in fields.items():
+            setattr(p, k, getattr(p, v) if isinstance(v, str) else v)
+    return f
+
+
+def _cout_over_tile(ops, p):
+    p.Cout = bn_of(ops, p.cfg) + 4
+
+
+def _gemm_cin_over_2048(ops, p):
+    p.C1, p.Cin_pad = 2080 - p.C2, 2080
+
+
+BASE = (0, 2, 3, 5, 7, 8)          # the families whose epilogue is conv_epilogue.h's contract (family 0: its own restatement of it)
+GCA = (2, 5, 7, 8)                 # ... that emit GlobalContext partials
+SAFE, EMUL = False, True           # EMUL: a launch that would leave its allocations if a launcher took it (geometry, channel counts, padding) — emulation only
+#              name                    families             epilogue  Cout needs   case           poke                                                      emulation only
+CONTRACT = [("act_in_gelu",         (2, 3, 4, 5, 6, 7, 8), "plain",  32, "",     {},            lambda o, p: setattr(p, "act_in", o.ACT_GELU),             SAFE),
+            ("pro_act_in_gelu",     (3, 6, 8),             "plain",  32, "pro",  {},            lambda o, p: setattr(p, "act_in", o.ACT_GELU),             SAFE),
+            ("pro_act_in_none",     (6,),                  "plain",  32, "pro",  {},            lambda o, p: setattr(p, "act_in", o.ACT_NONE),             SAFE),
+            ("act_out_silu",        (4, 6),                "plain",  32, "",     {},            lambda o, p: setattr(p, "act_out", o.ACT_SILU),            SAFE),
+            ("nhwc_cout_3",         BASE,                  "nchw",   3,  "",     {},            lambda o, p: setattr(p, "out_mode", o.OUT_NHWC),           SAFE),
+            ("shuffle_cout_20",     BASE,                  "plain",  20, "",     {},            lambda o, p: setattr(p, "out_mode", o.OUT_PIXEL_SHUFFLE),  SAFE),
+            ("shuffle",             (4, 6),                "plain",  32, "",     {},            lambda o, p: setattr(p, "out_mode", o.OUT_PIXEL_SHUFFLE),  SAFE),
+            ("addend_and_res",      BASE,                  "addend", 20, "",     {},            _set(res="addend", ld_res="ld_add", bs_res="bs_add"),      SAFE),
+            ("pw_addend_and_res",   (4,),                  "addend", 32, "",     {},            _set(res="addend", ld_res="ld_add", bs_res="bs_add"),      SAFE),
+            ("res",                 (6,),                  "plain",  32, "",     {},            _set(res="y", ld_res="ldy", bs_res="bsy"),                 SAFE),
+            ("addend_no_gate",      BASE,                  "addend", 20, "",     {},            _set(gate=0),                                              SAFE),
+            ("pw_addend_no_gate",   (4,),                  "addend", 32, "",     {},            _set(gate=0),                                              SAFE),
+            ("post_no_ps",          BASE + (6,),           "post",   32, "",     {},            _set(post_ps=0),                                           SAFE),
+            ("post_ssq_out",        BASE + (6,),           "post",   32, "",     {},            _set(ssq_out="y"),                                         SAFE),
+            ("post_addend",         BASE + (6,),           "post",   32, "",     {},            _set(addend="y", ld_add="ldy", bs_add="bsy", gate="post_pa", gate_stride="post_pstride"), SAFE),
+            ("post_res",            BASE + (6,),           "post",   32, "",     {},            _set(res="y", ld_res="ldy", bs_res="bsy"),                 SAFE),
+            ("post_act_out",        BASE + (6,),           "post",   32, "",     {},            lambda o, p: setattr(p, "act_out", o.ACT_SILU),            SAFE),
+            ("post",                (4,),                  "plain",  32, "",     {},            _set(post_pa="bias", post_ps="bias"),                      SAFE),
+            ("post_cout_over_tile", (0, 2, 5, 7, 8),       "post",   32, "",     {},            _cout_over_tile,                                           EMUL),
+            ("ssq_cout_over_tile",  (0, 2, 5, 7, 8),       "plain",  32, "",     dict(ssq_out=True), _cout_over_tile,                                      EMUL),
+            ("ssq_nchw",            (0, 2, 3, 4, 5, 6),    "plain",  32, "",     dict(ssq_out=True), lambda o, p: setattr(p, "out_mode", o.OUT_NCHW_F32),  SAFE),
+            ("ssq_64_couts",        (6,),                  "plain",  64, "",     dict(C1=32, C2=32), _set(ssq_out="y"),                                    SAFE),
+            ("gca_no_wk",           GCA,                   "plain",  32, "",     dict(gca=True), _set(gca_wk=0),                                           SAFE),
+            ("gca_shuffle",         GCA,                   "plain",  32, "",     dict(gca=True), lambda o, p: setattr(p, "out_mode", o.OUT_PIXEL_SHUFFLE), SAFE),
+            ("gca_act_out",         GCA,                   "plain",  32, "",     dict(gca=True), lambda o, p: setattr(p, "act_out", o.ACT_SILU),           SAFE),
+            ("gca_cout_over_tile",  GCA,                   "plain",  32, "",     dict(gca=True), _cout_over_tile,                                          EMUL),
+            ("gca_none_emitted",    (0, 3, 4, 6),          "plain",  32, "",     {},            _set(gca_part="y", gca_wk="bias"),                         SAFE),
+            ("mu_without_rs",       (7,),                  "plain",  32, "pro",  {},            _set(rs=0),                                                SAFE),
+            ("small_mu_without_rs", (8,),                  "plain",  32, "pro",  {},            _set(mu="pa"),                                             SAFE),
+            ("mu_rs_beside_ssq_a",  (3, 6),                "plain",  32, "pro",  {},            _set(mu="pa", rs="pa"),                                    SAFE),
+            ("mu_rs_no_prologue",   (2, 4, 5),             "plain",  32, "",     {},            _set(mu="bias", rs="bias"),                                SAFE),
+            ("ssq_b_one_input",     (6,),                  "plain",  32, "pro",  {},            _set(ssq_b="ssq_a"),                                       SAFE),
+            ("no_ssq_b_two_inputs", (6,),                  "plain",  32, "pro",  dict(C2=32),   _set(ssq_b=0),                                             SAFE),
+            ("gemm_ssq_b",          (7,),                  "plain",  32, "pro",  {},            _set(ssq_b="pa"),                                          SAFE),
+            ("tile_shape",          (0, 2, 3, 5, 6, 7, 8), "plain",  32, "",     {},            lambda o, p: setattr(p, "TH", p.TH + 1),                   EMUL),   # (conv_pw walks 256 | 128 consecutive pixels and has never looked at TH x TW)
+            ("stride_2",            (2, 3, 4, 5, 6, 7, 8), "plain",  32, "",     {},            _set(stride=2),                                            EMUL),
+            ("kh_off",              (2, 3, 4, 5, 6, 7, 8), "plain",  32, "",     {},            lambda o, p: setattr(p, "KH", 4 - p.KH),                   EMUL),
+            ("c2_null_x2",          (3, 4, 6, 7, 8),       "plain",  32, "two",  {},            _set(x2=0),                                                EMUL),
+            ("c2_one_input_family", (2, 5),                "plain",  32, "",     {},            _set(C2=32, x2="x1", ld2="ld1", bs2="bs1"),                EMUL),
+            ("c1_off_chunk",        (2, 3, 4, 5, 6, 7, 8), "plain",  32, "",     {},            lambda o, p: setattr(p, "C1", p.C1 - 8),                   EMUL),
+            ("cout_pad_off_tile",   (0, 2, 3, 5, 6, 7, 8), "plain",  32, "",     {},            lambda o, p: setattr(p, "Cout_pad", p.Cout_pad + 16),      EMUL),
+            ("gemm_cin_over_2048",  (7,),                  "plain",  32, "",     {},            _gemm_cin_over_2048,                                       EMUL)]
+
+
+@pytest.mark.parametrize("fam,poke", [pytest.param(f, p, id=f"{f}-{p[0]}") for p in CONTRACT for f in p[1]])
+def test_contract_refusals(ops, dev, fam, poke):
+    """Just outside, clause by clause: every predicate of the eight launchers that the alignment pokes above do not reach — the epilogue contract
+    (csrc/conv_launch.h: Cout against the output mode, addend beside res, what post_pa / ssq_out / gca_part exclude and the one tile over all couts
+    they need), the prologues and activations a family does not build, its tile shape, kernel size, channel chunking and padding.  One field of a
+    launch the family takes is moved; the launch is refused (by status) and nothing is written.  Every poke was seen refused by the launchers as
+    they stood before conv_launch.h; conv_gemm and conv_small take ssq_out beside any output mode (CONV_EP_SSQ_ANY_LAYOUT), so `ssq_nchw` leaves
+    them out."""
+    import os
+
+    name, _, ep, Cout, needs, case, fn, emul_only = poke
+    if emul_only and os.environ.get("IMAGEN_EMUL_TESTS") != "1":
+        pytest.skip("would not stay inside its allocations if a launcher took it: on the emulation only")
+    plan, p, O = _valid_launch(ops, dev, fam, ep, Cout, needs, **case)
+    fn(ops, p)
+    _refused(plan, O)

@@ -34,3 +34,24 @@ def test_misaligned_operands_have_no_route(kw):
 def test_two_byte_output_pitch_has_no_route():
     with pytest.raises(ValueError, match="no conv family takes"):
         _plan(20, y_ld=22)
+
+
+def test_cfg_table_answers_are_those_of_abi15():
+    """What the library tells the planner about every tile cfg id — config_info, _config_family, _config_ring, _stage_slots and _lds_bytes (3x3 and
+    1x1, stride 1 and 2, every tile shape launchable_shapes tries) — is what the launchers answered when each family still stated its tile table
+    and its LDS formula twice (tests/golden/conv_cfg_table_abi15.json, recorded by tools/routing_snapshot.py --write-cfg-table from that library)."""
+    import json
+    import os
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tools"))
+    import routing_snapshot
+
+    with open(routing_snapshot.CFG_TABLE_FIXTURE) as f:
+        want = json.load(f)
+    got = json.loads(json.dumps(routing_snapshot.cfg_table_answers()))
+    assert got["num_configs"] == want["num_configs"]
+    for g, w in zip(got["rows"], want["rows"]):
+        assert g == w, (g["cfg"], [k for k in w if g[k] != w[k]])
+    assert len(got["rows"]) == len(want["rows"])

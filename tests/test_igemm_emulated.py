@@ -117,15 +117,15 @@ def test_emulated_attention_contract():
 def test_emulated_conv_contract():
     """Every conv / GEMM kernel family per pixel against the fp64 restatement of the IGEMM contract and the launch-per-op plan, on strided operands
     in guarded allocations: channel slices, maps smaller than a tile, ragged all-cout epilogues, the shortest persistent tile ranges, the
-    alignment predicates of launch_igemm inside and outside (tests/test_conv_contract_gpu.py: the whole file, about two minutes on the
-    emulation, which holds every family: nothing skips)."""
+    alignment predicates of launch_igemm inside and outside, every other predicate of the eight launchers just outside (tests/test_conv_contract_gpu.py:
+    the whole file, about two minutes on the emulation, which holds every family: nothing skips)."""
     env = dict(os.environ, IMAGEN_LIB_PATH=_lib(""), IMAGEN_EMUL_TESTS="1")
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_conv_contract_gpu.py"), "-q", "-m", "gpu", "-p", "no:cacheprovider"],
                        env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=1500)
     out = r.stdout.decode()
     assert r.returncode == 0 and "failed" not in out, out[-3000:]
     passed = int(out.split(" passed")[0].split()[-1])
-    assert passed == 219 and "skipped" not in out.splitlines()[-1], out[-800:]
+    assert passed == 387 and "skipped" not in out.splitlines()[-1], out[-800:]
 
 
 @pytest.mark.skipif(not os.path.exists(CLANG), reason="host clang of the ROCm toolchain not present")

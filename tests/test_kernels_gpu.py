@@ -4,6 +4,7 @@ Inputs are rounded to fp16 first (the kernels' storage type), so the comparison 
 arithmetic (fp32 accumulate, fp16 rounding of MFMA operands / outputs).  Tolerance: normwise relative error
 <= 1e-3 (BASELINE.json north_star: "within 1e-3 rel fp16/bf16"), integer/selection work (quantile) exact.
 """
+import ctypes
 import math
 
 import pytest
@@ -50,6 +51,20 @@ def test_single_hip_runtime(ops):
 def _run(plan):
     plan.run()
     torch.cuda.synchronize()
+
+
+def test_instruction_warm_up_finds_its_kernels():
+    """The launchers of igemm.hip, conv_big.hip and conv_small.hip hand their kernels the size of their own code (the instruction warm-up of
+    common.h), looked up by the mangled name they build (conv_launch.h: conv_kernel_code_bytes).  A lookup that misses answers 0 and the warm-up
+    is silently off: one instantiation of each, by those names, has to be found in the library's gfx950 code objects."""
+    from imagen_pytorch_amd import _abi
+
+    lib = _abi.load_library()
+    lib.imagen_debug_code_bytes.argtypes = [ctypes.c_char_p]
+    for name in (b"_ZN12_GLOBAL__N_112igemm_kernelILi2ELi1ELi4ELi1ELi4ELi18ELb0EEEv17ImagenIgemmParams",     # cfg 0, 3x3, plain epilogue
+                 b"_ZN12_GLOBAL__N_115conv_big_kernelILi4ELi2ELi1ELi16ELi4ELi2ELb1EEEv17ImagenIgemmParams",  # conv_big cfg 0, generic epilogue
+                 b"_ZN12_GLOBAL__N_117conv_small_kernelILi4ELb1ELb0EEEv17ImagenIgemmParamsj"):              # 128 couts, prologue, plain epilogue
+        assert lib.imagen_debug_code_bytes(name) > 1024, name
 
 
 # ------------------------------------------------------------------------------------------------ igemm

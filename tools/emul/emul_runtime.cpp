@@ -267,21 +267,11 @@ hipError_t hipDeviceGetAttribute(int* v, int attr, int) {
 
 void imagen_set_error(const char* fmt, ...);   // capi.hip
 // ---- what the emulated library does not compile from csrc/: conv_lds.hip (superseded family, hand-scheduled asm throughout)
-#define WEAK __attribute__((weak))   // the other families' translation units override these when they are part of the emulated library
 int imagen_conv_lds_num_configs() { return 0; }
 int imagen_conv_lds_config_info(int, int*, int*, int*) { return -1; }
 int imagen_conv_lds_stage_slots(int, int, int) { return -1; }
 long imagen_conv_lds_lds_bytes(int, int, int, int, int) { return -1; }
 int launch_conv_lds(const ImagenIgemmParams*, int, hipStream_t) { imagen_set_error("emulated library: conv_lds is not emulated"); return -1; }
-WEAK int imagen_conv_dma_num_configs() { return 0; }
-WEAK int imagen_conv_dma_config_info(int, int*, int*, int*) { return -1; }
-WEAK long imagen_conv_dma_lds_bytes(int, int, int, int, int) { return -1; }
-WEAK int imagen_conv_dma_ring(int) { return 0; }
-WEAK int launch_conv_dma(const ImagenIgemmParams*, int, hipStream_t) { return -1; }
-WEAK int imagen_conv_stream_num_configs() { return 0; }
-WEAK int imagen_conv_stream_config_info(int, int*, int*, int*) { return -1; }
-WEAK long imagen_conv_stream_lds_bytes(int, int, int, int, int) { return -1; }
-WEAK int launch_conv_stream(const ImagenIgemmParams*, int, hipStream_t) { return -1; }
 
 // ---- graphs and events for capi.hip: a graph is the list of recorded launches (each with its by-value kernel arguments)
 struct EmulGraph { std::vector<std::function<void()>> nodes; };

@@ -35,6 +35,7 @@ README_U1 = dict(dim=32, cond_dim=512, dim_mults=(1, 2, 4, 8), num_resnet_blocks
                  layer_cross_attns=(False, True, True, True))
 README_U2 = dict(dim=32, cond_dim=512, dim_mults=(1, 2, 4, 8), num_resnet_blocks=(2, 4, 8, 8), layer_attns=(False, False, False, True),
                  layer_cross_attns=(False, False, False, True), lowres_cond=True)
+CFG_TABLE_FIXTURE = os.path.join(GOLDEN, "conv_cfg_table_abi15.json")   # cfg_table_answers() of the library the merged tile tables came from
 C2_BASE = dict(README_U1, dim=128)
 STATIC_TOKENS = 256   # text tokens of the static (once per request) plan, as in tests/test_bench_shapes_gpu.py
 IGEMM_RESULTS = ("ssq_emitted", "post_applied", "gca_chunks")
@@ -207,10 +208,34 @@ def first_difference(old: dict, snap: dict):
     return None
 
 
+def cfg_table_answers() -> dict:
+    """What the library tells the planner about every tile cfg id (tests/golden/conv_cfg_table_abi15.json): config_info, _family, _ring, _stage_slots
+    and _lds_bytes for 3x3 and 1x1 kernels at stride 1 and 2 on every tile shape ops.launchable_shapes() tries (a map of one row included)."""
+    from imagen_pytorch_amd import ops
+
+    lib = ops.load_library()
+    rows = []
+    for cfg in range(-1, lib.imagen_igemm_num_configs() + 1):   # (one id outside on either side)
+        tp, bn, g = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int(-1)
+        rc = lib.imagen_igemm_config_info(cfg, ctypes.byref(tp), ctypes.byref(bn), ctypes.byref(g))
+        shapes = sorted(set(ops._tile_shapes(tp.value, 64, 64) + ops._tile_shapes(tp.value, 1, 64))) if rc == 0 else [(8, 8)]
+        rows.append({"cfg": cfg, "info": [rc, tp.value, bn.value, g.value], "family": lib.imagen_igemm_config_family(cfg), "ring": lib.imagen_igemm_config_ring(cfg),
+                     "stage_slots": [lib.imagen_igemm_stage_slots(cfg, k, k) for k in (3, 1)],
+                     "lds_bytes": [[k, st, th, tw, lib.imagen_igemm_lds_bytes(cfg, k, k, st, th, tw)] for k in (3, 1) for st in (1, 2) for th, tw in shapes]})
+    return {"num_configs": lib.imagen_igemm_num_configs(), "rows": rows}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--write", action="store_true", help="regenerate tests/golden/routing_snapshot.json and routing_wiring.json from this tree")
+    ap.add_argument("--write-cfg-table", action="store_true", help="regenerate tests/golden/conv_cfg_table_abi15.json from the loaded library")
     args = ap.parse_args()
+    if args.write_cfg_table:
+        with open(CFG_TABLE_FIXTURE, "w") as f:
+            json.dump(cfg_table_answers(), f, separators=(",", ":"))
+            f.write("\n")
+        print(f"wrote {CFG_TABLE_FIXTURE}")
+        return 0
     wiring = {}
     snap = snapshot(wiring)
     fams, modes = coverage(snap)
