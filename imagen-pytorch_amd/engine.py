@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import math
 import os
+from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Dict, List, Optional
 
@@ -151,6 +152,97 @@ SPLIT_SMALL_FLOPS = 3.0e9      # 2 * pixels * Cout * (2 K) of the split launch
 TIME_CHAIN_F32 = 1
 
 
+@dataclass(eq=False)
+class AttnSite:
+    """An attention whose keys / values include the conditioning tokens, as the planner's conditioning passes see it (UnetEngine.attn_sites, in
+    the order the traversal meets them: that order is the column order of the batched projections `ctx.self` / `ctx.cross`).  This class is
+    the K^/V^T kinds: `self` (multi-query: ONE head shared by the query heads; key rows [context | null | the tokens themselves]) and
+    `cross` (key rows [null | context]).  A new kind is a subclass that answers the same questions — ctx_wb / width, emit_ctx_rows,
+    emit_null, linctx_job — as LinearSite below does; no consumer asks for `kind`."""
+    kind: str
+    name: str
+    mod: object
+    heads: int                      # K / V heads the buffers hold (the query heads are mod.heads)
+    dh: int
+    J: int                          # key rows in use
+    n_ctx: int = 0                  # ... of which conditioning tokens
+    null_row: int = 0               # ... and where the learned null key / value sits
+    proj: Optional[str] = None      # the batched projection of the conditioning tokens that feeds it: "self" (to_context) | "cross" (to_kv) | None
+    khat: Optional[torch.Tensor] = None
+    vt: Optional[torch.Tensor] = None
+    Jp: int = 0
+    k_strides: tuple = ()
+    vt_strides: tuple = ()
+    src_hs: int = 0                 # distance of the heads' columns inside a projected (k | v) row
+
+    @classmethod
+    def alloc(cls, kind, name, mod, R, J, dev, shared=False, **kw):
+        """The site with its zero-filled pair K^ [R, heads, Jp, dh] / V^T [R, heads, dh, Jp], Jp = J rounded up to the kernels' 32-key tile (they read
+        the padding rows / columns J..Jp-1: zeros), and both (batch, head, row) stride triples.  shared: one K / V head, head stride 0."""
+        heads, dh, Jp = 1 if shared else mod.heads, mod.dim_head, ops._round_up(J, 32)
+        hs = 0 if shared else Jp * dh
+        return cls(kind, name, mod, heads, dh, J, khat=torch.zeros(R, heads, Jp, dh, dtype=torch.float16, device=dev),
+                   vt=torch.zeros(R, heads, dh, Jp, dtype=torch.float16, device=dev), Jp=Jp, k_strides=(heads * Jp * dh, hs, dh),
+                   vt_strides=(heads * dh * Jp, hs, Jp), src_hs=0 if shared else dh, **kw)
+
+    @property
+    def width(self) -> int:
+        """Columns of its slice of the batched projection: (k | v), each heads * dh wide."""
+        return 2 * self.heads * self.dh
+
+    def ctx_wb(self):
+        """(weight, bias) of its slice of the batched projection.  `self`: to_context = LayerNorm(affine) + Linear (ip.py:527), the affine folded
+        into the Linear so that all sites share one normalised input; `cross`: to_kv consumes the tokens directly (ip.py:783)."""
+        if self.proj == "cross":
+            return self.mod.to_kv.weight.detach().float(), None
+        ln, lin = self.mod.to_context[0], self.mod.to_context[1]
+        w = lin.weight.detach().float()
+        return w * ln.weight.detach().float()[None, :], lin.bias.detach().float() + w @ ln.bias.detach().float()
+
+    def kv_prep(self, eng, plan, src, rows, r0, src_bs, src_rs, k_off, v_off=None, hs=None, **kw):
+        """KV_PREP of `rows` source rows per batch entry into key rows [r0, r0 + rows): l2norm(k) * k_scale -> K^, v -> V^T; v sits heads * dh
+        columns behind k unless `v_off` says otherwise."""
+        ops.kv_prep(plan, src, src, eng.W.f32(self.name + ".k_scale", lambda: self.mod.k_scale), self.khat, self.vt, B=eng.R, heads=self.heads,
+                    rows=rows, r0=r0, src_strides=(src_bs, src_rs, self.src_hs if hs is None else hs), k_strides=self.k_strides,
+                    vt_strides=self.vt_strides, k_off=k_off, v_off=k_off + self.heads * self.dh if v_off is None else v_off, head_dim=self.dh, **kw)
+
+    def emit_ctx_rows(self, eng, plan, st: Act, col: int, n: int, r0: int, jobs: list, tag: str):
+        """Its columns [col, col + width) of the n projected rows per batch entry `st` -> key rows [r0, r0 + n): one job of the KV_PREP_MULTI launch."""
+        self.kv_prep(eng, plan, st.t, n, r0, n * st.C, st.C, col, batch=jobs)
+
+    def emit_null(self, eng, plan):
+        """The learned null key / value, one [2, dh] pair for all heads (ip.py:545-547 self: behind the context; ip.py:805-808 cross: first)."""
+        nk = eng.W.f32(self.name + ".null_kv", lambda: self.mod.null_kv)
+        self.kv_prep(eng, plan, nk, 1, self.null_row, 0, 0, 0, v_off=self.dh, hs=0, label=self.name + ".kv_null")
+
+    def linctx_job(self, eng, jobs: list):
+        """Its job of the step plan's LINCTX launch: none."""
+
+
+@dataclass(eq=False)
+class LinearSite(AttnSite):
+    """LinearCrossAttention (ip.py:836-874): the raw projected (k | v) rows `kv` [R, J, 2 * heads * dh] — row 0 the null row, [1, 1 + ntt) the
+    time tokens, then the static tokens; no l2norm, no k_scale — and M = softmax_j(k)^T v [R, heads, dh, dh], which one LINCTX launch per
+    denoiser evaluation reduces from them.  Its to_kv is the cross-attention's Linear (a subclass): it rides in `ctx.cross`."""
+    kv: Optional[torch.Tensor] = None
+    M: Optional[torch.Tensor] = None
+
+    def emit_ctx_rows(self, eng, plan, st: Act, col: int, n: int, r0: int, jobs: list, tag: str):
+        w = self.width
+        ops.rows_copy(plan, st.t, self.kv, B=eng.R, rows=n, C=w, src_bs=n * st.C, src_rs=st.C, dst_bs=self.J * w, dst_rs=w, src_off=col,
+                      dst_off=r0 * w, label=f"ctx.{tag}.linear_rows")
+
+    def emit_null(self, eng, plan):
+        """Row 0, raw (ip.py:849-852): (null k per head | null v per head)."""
+        w = self.width
+        row = eng.W.f16(self.name + ".null_row", lambda: self.mod.null_kv.detach().repeat(1, self.heads).reshape(-1))
+        ops.rows_copy(plan, row, self.kv, B=eng.R, rows=1, C=w, src_bs=0, src_rs=w, dst_bs=self.J * w, dst_rs=w, label=self.name + ".kv_null")
+
+    def linctx_job(self, eng, jobs: list):
+        w = self.width
+        ops.linctx_job(self.kv, self.M, R=eng.R, heads=self.heads, head_dim=self.dh, J=self.J, kv_bs=self.J * w, kv_rs=w, batch=jobs)
+
+
 class UnetEngine:
     def __init__(self, unet, rows: int, src_batch: int, size: int, device, with_text: bool = True, dry: bool = False):
         assert rows % src_batch == 0
@@ -173,7 +265,7 @@ class UnetEngine:
             self.NTX = (unet.attn_pool.latents.shape[0] + unet.attn_pool.num_latents_mean_pooled) if unet.attn_pool is not None else unet.max_text_len
         self.NS = (self.ntt if self.lowres else 0) + self.NTX          # static conditioning tokens
         self.NT = self.ntt + self.NS                                    # all conditioning tokens
-        self.attn_sites: List[dict] = []   # attention K/V buffers + how to fill their conditioning rows
+        self.attn_sites: List[AttnSite] = []   # attention K/V buffers + how to fill their conditioning rows
         self.taps: Dict[str, Act] = {}     # named intermediates (persistent buffers) for per-stage parity checks
         self._static_plans: Dict[int, tuple] = {}   # n_tok -> (plan, te16, mask_u8, negative-prompt projection plan | None)
         self._last_static: List[Plan] = []          # what the last set_conditioning() ran (a dry engine: what is to be run), in order
@@ -736,10 +828,40 @@ class UnetEngine:
             ops.rowstat(plan, a, mode=2, rs=a.ssq, label=label)
         return a.ssq
 
+    # ---- attention over a token view, launch by launch: ONE skeleton for the five sites (cross, linear cross, self, Perceiver, temporal).  A site
+    # keeps what is its own: its record, its K^/V^T rows, its ROWCHAIN shortcut ahead of this, its labels, weight keys and split decisions.
+    def _attn_in(self, plan, tok: Act, nm: str, w_in, g_in, core, in_label: str, b_in=None, stats=None) -> Act:
+        """LayerNorm statistics of the token view (`stats` = (mean, rstd) where its producer emitted them) -> the input projection with the
+        LayerNorm as its prologue -> core(plan, projected rows) -> o."""
+        if stats is None:
+            stats = self.f32buf(tok.rows), self.f32buf(tok.rows)
+            ops.rowstat(plan, tok, mode=1, rs=stats[1], mu=stats[0], eps=1e-5, label=nm + ".norm")
+        proj = self.new(tok.B, tok.H, tok.W, w_in.Cout)
+        ops.igemm(plan, tok, w_in, proj, mu=stats[0], rs=stats[1], pa=g_in, ps=b_in, label=nm + in_label)
+        return core(plan, proj)
+
+    def _attn_out(self, plan, o: Act, res: Act, nm: str, w_out, g_out, dst: Act, b_out=None, **stats_out):
+        """to_out -> LayerNorm + residual `res` -> dst; stats_out: the ssq_out / ln_stats_out the LN_RESIDUAL launch emits for dst's consumer."""
+        y = self.new(o.B, o.H, o.W, res.C)
+        ops.igemm(plan, o, w_out, y, label=nm + ".to_out")
+        ops.ln_residual(plan, y, g_out, dst, beta=b_out, res=res, eps=1e-5, label=nm + ".out_norm", **stats_out)
+
+    def _token_attn(self, plan, tok: Act, nm: str, w_in, g_in, core, w_out, g_out, dst: Act, in_label=".to_q", b_in=None, stats=None, **out_kw):
+        self._attn_out(plan, self._attn_in(plan, tok, nm, w_in, g_in, core, in_label, b_in, stats), tok, nm, w_out, g_out, dst, **out_kw)
+
+    def _attention(self, plan, q: Act, s: AttnSite) -> Act:
+        """Flash attention of the leading heads * dh columns of the rows `q` against the site's K^/V^T pair."""
+        heads, dh, N = s.mod.heads, s.dh, q.H * q.W
+        inner = heads * dh
+        o = self.new(q.B, 1, N, inner)
+        ops.attention(plan, q.t, s.khat, s.vt, o.t, B=q.B, heads=heads, rows=N, J=s.J, q_strides=(N * q.ld, dh, q.ld), k_strides=s.k_strides,
+                      vt_strides=s.vt_strides, o_strides=(N * inner, dh, inner), q_scale=self.W.f32(s.name + ".q_scale", lambda: s.mod.q_scale),
+                      q_mult=SIM_SCALE * LOG2E, label=s.name + ".attn", head_dim=dh,
+                      logit_bound=ops.attention_logit_bound(s.mod.q_scale, s.mod.k_scale, SIM_SCALE * LOG2E))
+        return o
+
     # ---- CrossAttention inside a ResnetBlock (ip.py:745-751, 759-834)
     def _cross_attn(self, plan, h: Act, ca: CrossAttentionP, name: str) -> Act:
-        if getattr(ca, "linear", False):   # (the video path's cross-attention container has no linear form: Unet3D refuses the flag)
-            return self._linear_cross_attn(plan, h, ca, name)
         W, R = self.W, self.R
         N, C = h.H * h.W, h.C
         heads, dh = ca.heads, ca.dim_head
@@ -747,66 +869,40 @@ class UnetEngine:
         tok = h.tokens()
         wq = W.conv(name + ".to_q", ca.to_q, split=SPLIT_1X1 and self._split_small(C, 1, inner, R * N))
         wo = W.conv(name + ".to_out", ca.to_out[0], split=SPLIT_1X1 and self._split_small(inner, 1, C, R * N))
-        J = self.NT + 1
-        Jp = ops._round_up(J, 32)
-        khat = torch.zeros(R, heads, Jp, dh, dtype=torch.float16, device=self.dev)
-        vt = torch.zeros(R, heads, dh, Jp, dtype=torch.float16, device=self.dev)
-        site = dict(kind="cross", name=name, mod=ca, khat=khat, vt=vt, heads=heads, Jp=Jp, dh=dh,
-                    k_strides=(heads * Jp * dh, Jp * dh, dh), vt_strides=(heads * dh * Jp, dh * Jp, Jp))
-        self.attn_sites.append(site)
         out = self.new(R, h.H, h.W, C)
         out.ssq = self.f32buf(R * N)
         g_norm = W.f32(name + ".norm.g", lambda: _pad_vec(ca.norm.g, wq.Cin_pad))
         g_out = W.f32(name + ".out_g", lambda: ca.to_out[1].g)
-        q_scale = W.f32(name + ".q_scale", lambda: ca.q_scale)
-        if ops.rowchain_ok(C, N, heads, dh, wq, wo) and h.ld == C:
-            # the whole cross-attention as ONE launch (ROWCHAIN mode XATTN): its rows only meet constants of their image
-            ops.rowchain_xattn(plan, tok, out.tokens(), wq, g_norm, wo, g_out, khat, vt, heads=heads, J=J, k_strides=site["k_strides"],
-                               vt_strides=site["vt_strides"], q_scale=q_scale, q_mult=SIM_SCALE * LOG2E, rows_per_batch=N, ssq_out=out.ssq,
-                               label=name + ".chain")
-            return out
-        mu, rs = self.f32buf(R * N), self.f32buf(R * N)
-        ops.rowstat(plan, tok, mode=1, rs=rs, mu=mu, eps=1e-5, label=name + ".norm")
-        q = self.new(R, 1, N, inner)
-        ops.igemm(plan, tok, wq, q, mu=mu, rs=rs, pa=g_norm, label=name + ".to_q")
-        o = self.new(R, 1, N, inner)
-        ops.attention(plan, q.t, khat, vt, o.t, B=R, heads=heads, rows=N, J=J, q_strides=(N * inner, dh, inner),
-                      k_strides=site["k_strides"], vt_strides=site["vt_strides"], o_strides=(N * inner, dh, inner),
-                      q_scale=q_scale, q_mult=SIM_SCALE * LOG2E, label=name + ".attn", head_dim=dh,
-                      logit_bound=ops.attention_logit_bound(ca.q_scale, ca.k_scale, SIM_SCALE * LOG2E))
-        y = self.new(R, 1, N, C)
-        ops.igemm(plan, o, wo, y, label=name + ".to_out")
-        ops.ln_residual(plan, y, g_out, out.tokens(), res=tok, eps=1e-5, ssq_out=out.ssq, label=name + ".out_norm")
+        if getattr(ca, "linear", False):   # (the video path's cross-attention container has no linear form: Unet3D refuses the flag)
+            core = self._linear_cross_attn(ca, name, N)
+        else:
+            site = AttnSite.alloc("cross", name, ca, R, self.NT + 1, self.dev, n_ctx=self.NT, proj="cross")
+            self.attn_sites.append(site)
+            if ops.rowchain_ok(C, N, heads, dh, wq, wo) and h.ld == C:
+                # the whole cross-attention as ONE launch (ROWCHAIN mode XATTN): its rows only meet constants of their image
+                ops.rowchain_xattn(plan, tok, out.tokens(), wq, g_norm, wo, g_out, site.khat, site.vt, heads=heads, J=site.J, k_strides=site.k_strides,
+                                   vt_strides=site.vt_strides, q_scale=W.f32(name + ".q_scale", lambda: ca.q_scale), q_mult=SIM_SCALE * LOG2E,
+                                   rows_per_batch=N, ssq_out=out.ssq, label=name + ".chain")
+                return out
+            core = lambda plan, q: self._attention(plan, q, site)
+        self._token_attn(plan, tok, name, wq, g_norm, core, wo, g_out, out.tokens(), ssq_out=out.ssq)
         return out
 
     # ---- LinearCrossAttention inside a ResnetBlock (ip.py:745-751, 836-874; Unet(use_linear_cross_attn=...))
-    def _linear_cross_attn(self, plan, h: Act, ca: CrossAttentionP, name: str) -> Act:
-        """LayerNorm -> to_q -> o = 8 softmax_d(q) M -> to_out -> LayerNorm + residual, one launch each at every resolution (no ROWCHAIN mode
-        for it yet: q and o make one HBM round trip each).  M = softmax_j(k)^T v of the row's conditioning tokens comes from the LINCTX
-        launch at the head of the step plan (_emit_linctx); the site only registers its k | v row buffer here."""
-        W, R = self.W, self.R
-        N, C = h.H * h.W, h.C
-        heads, dh = ca.heads, ca.dim_head
-        inner = heads * dh
-        tok = h.tokens()
-        wq = W.conv(name + ".to_q", ca.to_q, split=SPLIT_1X1 and self._split_small(C, 1, inner, R * N))
-        wo = W.conv(name + ".to_out", ca.to_out[0], split=SPLIT_1X1 and self._split_small(inner, 1, C, R * N))
-        J = self.NT + 1
-        kv = torch.zeros(R, J, 2 * inner, dtype=torch.float16, device=self.dev)    # row 0: null_kv; [1, 1 + ntt): time tokens; then the static tokens
-        M = self.f32buf(R, heads, dh, dh)
-        self.attn_sites.append(dict(kind="linear", name=name, mod=ca, kv=kv, M=M, heads=heads, dh=dh, J=J))
-        out = self.new(R, h.H, h.W, C)
-        out.ssq = self.f32buf(R * N)
-        mu, rs = self.f32buf(R * N), self.f32buf(R * N)
-        ops.rowstat(plan, tok, mode=1, rs=rs, mu=mu, eps=1e-5, label=name + ".norm")
-        q = self.new(R, 1, N, inner)
-        ops.igemm(plan, tok, wq, q, mu=mu, rs=rs, pa=W.f32(name + ".norm.g", lambda: _pad_vec(ca.norm.g, wq.Cin_pad)), label=name + ".to_q")
-        o = self.new(R, 1, N, inner)
-        ops.linear_xattn(plan, q, M, o, heads=heads, head_dim=dh, rows_per_batch=N, label=name + ".linear_attn")
-        y = self.new(R, 1, N, C)
-        ops.igemm(plan, o, wo, y, label=name + ".to_out")
-        ops.ln_residual(plan, y, W.f32(name + ".out_g", lambda: ca.to_out[1].g), out.tokens(), res=tok, eps=1e-5, ssq_out=out.ssq, label=name + ".out_norm")
-        return out
+    def _linear_cross_attn(self, ca: CrossAttentionP, name: str, N: int):
+        """The core of LayerNorm -> to_q -> o = 8 softmax_d(q) M -> to_out -> LayerNorm + residual, one launch each at every resolution (no
+        ROWCHAIN mode for it yet: q and o make one HBM round trip each).  M = softmax_j(k)^T v of the row's conditioning tokens comes from
+        the LINCTX launch at the head of the step plan (_emit_linctx); the site only registers its k | v row buffer here."""
+        R, heads, dh, J = self.R, ca.heads, ca.dim_head, self.NT + 1
+        site = LinearSite("linear", name, ca, heads, dh, J, n_ctx=self.NT, proj="cross", M=self.f32buf(R, heads, dh, dh),
+                          kv=torch.zeros(R, J, 2 * heads * dh, dtype=torch.float16, device=self.dev))
+        self.attn_sites.append(site)
+
+        def core(plan, q: Act) -> Act:
+            o = self.new(R, 1, N, heads * dh)
+            ops.linear_xattn(plan, q, site.M, o, heads=heads, head_dim=dh, rows_per_batch=N, label=name + ".linear_attn")
+            return o
+        return core
 
     # ---- TransformerBlock (ip.py:992-1022): depth x [multi-query self attention + FeedForward]
     def _transformer(self, plan, x: Act, tb: TransformerBlockP, name: str, with_context: bool) -> Act:
@@ -823,9 +919,9 @@ class UnetEngine:
             w_out = W.conv(nm + ".to_out", attn.to_out[0], split=SPLIT_1X1 and self._split_small(inner, 1, C, R * N))
             split_ff = SPLIT_1X1 and self._split_small(2 * C, 1, C, R * N)
             w1, w2 = W.conv(nm + ".ff.w1", ff[1], split=split_ff), W.conv(nm + ".ff.w2", ff[4], split=split_ff)
+            o = self._self_attn(plan, cur.tokens(), attn, nm, with_context, ln_stats=stats_in)
             if ops.rowchain_ok(C, N, heads, dh, w_out, w1, w2, hidden=hidden) and cur.ld == C:
                 # attention out-projection -> LayerNorm + residual -> FeedForward as ONE launch behind the attention (ROWCHAIN mode FF)
-                o = self._self_attn(plan, cur.tokens(), attn, nm, with_context, ln_stats=stats_in, stop_at_attention=True)
                 out = self.new(R, 1, N, C)
                 out.ssq = self.f32buf(R * N)
                 ops.rowchain_ff(plan, o, cur.tokens(), out, w_out, W.f32(nm + ".out_g", lambda: attn.to_out[1].g), w1,
@@ -833,15 +929,14 @@ class UnetEngine:
                                 W.f32(nm + ".ff.g1", lambda: _pad_vec(ff[3].g, w2.Cin_pad)), rows_per_batch=N, ssq_out=out.ssq, label=nm + ".ff.chain")
                 cur = Act(out.t, R, x.H, x.W, C, C, N * C, ssq=out.ssq)
                 continue
-            x1, st = self._self_attn(plan, cur.tokens(), attn, nm, with_context, ln_stats=stats_in, want_stats=True)
+            x1, st = self._self_attn_out(plan, o, cur.tokens(), attn, nm, want_stats=True)
             ffo = self._feed_forward(plan, x1, ff, nm + ".ff", ln_stats=st, split=split_ff)
             cur = Act(ffo.t, R, x.H, x.W, C, C, N * C, ssq=ffo.ssq)
         return cur
 
-    def _self_attn(self, plan, tok: Act, attn, nm: str, with_context: bool, ln_stats: Optional[tuple] = None, want_stats: bool = False,
-                   stop_at_attention: bool = False):
-        """attn(tok) + tok for the (R, 1, N, C) token view `tok` (ip.py:502-591, 1017): LayerNorm -> q | k | v in one GEMM ->
-        K^/V^T rows behind the conditioning and null rows -> flash attention -> to_out -> LayerNorm + residual."""
+    def _self_attn(self, plan, tok: Act, attn, nm: str, with_context: bool, ln_stats: Optional[tuple] = None) -> Act:
+        """attn(tok) + tok for the (R, 1, N, C) token view `tok` (ip.py:502-591, 1017), up to the attention: LayerNorm -> q | k | v in one GEMM ->
+        K^/V^T rows behind the conditioning and null rows -> flash attention -> o.  _self_attn_out, or a ROWCHAIN FF launch, takes it from there."""
         W, R = self.W, self.R
         N, C = tok.H * tok.W, tok.C
         heads, dh = attn.heads, attn.dim_head
@@ -849,44 +944,29 @@ class UnetEngine:
         # q | k | v from ONE GEMM (to_q and to_kv are both bias-free on the same normalised input, ip.py:539)
         wqkv = W.raw(nm + ".qkv", torch.cat((attn.to_q.weight.detach().float(), attn.to_kv.weight.detach().float())), None,
                       split=SPLIT_1X1 and self._split_small(C, 1, inner + 2 * dh, R * N))
-        qkv = self.new(R, 1, N, inner + 2 * dh)
-        ld = inner + 2 * dh
         n_ctx = self.NT if (with_context and attn.to_context is not None) else 0
-        J = n_ctx + 1 + N
-        Jp = ops._round_up(J, 32)
-        khat = torch.zeros(R, Jp, dh, dtype=torch.float16, device=self.dev)
-        vt = torch.zeros(R, dh, Jp, dtype=torch.float16, device=self.dev)
-        k_strides, vt_strides = (Jp * dh, 0, dh), (dh * Jp, 0, Jp)
-        site = dict(kind="self", name=nm, mod=attn, khat=khat, vt=vt, heads=1, Jp=Jp, n_ctx=n_ctx, dh=dh, k_strides=k_strides, vt_strides=vt_strides)
+        site = AttnSite.alloc("self", nm, attn, R, n_ctx + 1 + N, self.dev, shared=True, n_ctx=n_ctx, null_row=n_ctx, proj="self" if n_ctx else None)
         self.attn_sites.append(site)
         g_norm = W.f32(nm + ".norm.g", lambda: _pad_vec(attn.norm.g, wqkv.Cin_pad))
-        k_scale = W.f32(nm + ".k_scale", lambda: attn.k_scale)
         if ops.rowchain_ok(C, N, heads, dh, wqkv) and tok.ld == C:
             # LayerNorm -> q | k | v -> q rows, K^ rows, V^T columns as ONE launch (ROWCHAIN mode QKV); the statistics its producer emitted, if any
-            ops.rowchain_qkv(plan, tok, qkv, wqkv, g_norm, khat, vt, k_scale, heads=heads, r0=n_ctx + 1, k_strides=k_strides, vt_strides=vt_strides,
-                             rows_per_batch=N, ln_stats=ln_stats, label=nm + ".qkv.chain")
-        else:
-            if ln_stats is not None:
-                mu, rs = ln_stats
-            else:
-                mu, rs = self.f32buf(R * N), self.f32buf(R * N)
-                ops.rowstat(plan, tok, mode=1, rs=rs, mu=mu, eps=1e-5, label=nm + ".norm")
-            ops.igemm(plan, tok, wqkv, qkv, mu=mu, rs=rs, pa=g_norm, label=nm + ".qkv")
-            ops.kv_prep(plan, qkv.t, qkv.t, k_scale, khat, vt, B=R, heads=1, rows=N, r0=n_ctx + 1,
-                        src_strides=(N * ld, ld, 0), k_strides=k_strides, vt_strides=vt_strides, k_off=inner, v_off=inner + dh,
-                        label=nm + ".kv_self", head_dim=dh)
-        o = self.new(R, 1, N, inner)
-        ops.attention(plan, qkv.t, khat, vt, o.t, B=R, heads=heads, rows=N, J=J, q_strides=(N * ld, dh, ld), k_strides=k_strides,
-                      vt_strides=vt_strides, o_strides=(N * inner, dh, inner), q_scale=W.f32(nm + ".q_scale", lambda: attn.q_scale),
-                      q_mult=SIM_SCALE * LOG2E, label=nm + ".attn", head_dim=dh,
-                      logit_bound=ops.attention_logit_bound(attn.q_scale, attn.k_scale, SIM_SCALE * LOG2E))
-        if stop_at_attention:       # (the caller runs the out-projection, the LayerNorm + residual and the FeedForward as one ROWCHAIN launch)
-            return o
-        y = self.new(R, 1, N, C)
-        ops.igemm(plan, o, W.conv(nm + ".to_out", attn.to_out[0], split=SPLIT_1X1 and self._split_small(inner, 1, C, R * N)), y, label=nm + ".to_out")
+            qkv = self.new(R, 1, N, inner + 2 * dh)
+            ops.rowchain_qkv(plan, tok, qkv, wqkv, g_norm, site.khat, site.vt, W.f32(nm + ".k_scale", lambda: attn.k_scale), heads=heads, r0=n_ctx + 1,
+                             k_strides=site.k_strides, vt_strides=site.vt_strides, rows_per_batch=N, ln_stats=ln_stats, label=nm + ".qkv.chain")
+            return self._attention(plan, qkv, site)
+
+        def core(plan, qkv: Act) -> Act:
+            site.kv_prep(self, plan, qkv.t, N, n_ctx + 1, N * qkv.ld, qkv.ld, inner, label=nm + ".kv_self")
+            return self._attention(plan, qkv, site)
+        return self._attn_in(plan, tok, nm, wqkv, g_norm, core, ".qkv", stats=ln_stats)
+
+    def _self_attn_out(self, plan, o: Act, tok: Act, attn, nm: str, want_stats: bool = False):
+        """The tail of attn(tok) + tok: to_out -> LayerNorm + residual -> (x1, the LayerNorm statistics of x1 | None)."""
+        R, N, C = self.R, tok.H * tok.W, tok.C
         x1 = self.new(R, 1, N, C)
         st = (self.f32buf(R * N), self.f32buf(R * N)) if (LN_STATS_FUSED and want_stats) else None   # statistics of x1 for a FeedForward's first LayerNorm (a second pass over the row: only where one follows)
-        ops.ln_residual(plan, y, W.f32(nm + ".out_g", lambda: attn.to_out[1].g), x1, res=tok, eps=1e-5, ln_stats_out=st, label=nm + ".out_norm")
+        self._attn_out(plan, o, tok, nm, self.W.conv(nm + ".to_out", attn.to_out[0], split=SPLIT_1X1 and self._split_small(o.C, 1, C, R * N)),
+                       self.W.f32(nm + ".out_g", lambda: attn.to_out[1].g), x1, ln_stats_out=st)
         return x1, st
 
     def _feed_forward(self, plan, x: Act, ff: nn.Sequential, name: str, ln_stats: Optional[tuple] = None, split: bool = False,
@@ -962,68 +1042,37 @@ class UnetEngine:
         return out
 
     # ------------------------------------------------------------------------------------------ conditioning K/V
-    def _ctx_weights(self):
-        """Batched projections of the conditioning tokens for every attention site:
-        self-attention `to_context` = LayerNorm(affine) + Linear (ip.py:527): the LN affine is folded into the Linear, so all
-        sites share one normalised input; cross-attention `to_kv` (ip.py:783) consumes c directly."""
-        selfs = [s for s in self.attn_sites if s["kind"] == "self" and s["n_ctx"] > 0]
-        crosses = [s for s in self.attn_sites if s["kind"] in ("cross", "linear")]   # a linear site's to_kv is the same Linear (ip.py:836: a subclass)
+    def _ctx_weights(self) -> list:
+        """[(which, sites, packed weight)] of the batched projections of the conditioning tokens that have a site, "self" ahead of "cross": each
+        is ONE GEMM over the sites' slices (AttnSite.ctx_wb), concatenated in the order the sites were registered."""
+        out = []
+        for which in ("self", "cross"):
+            sites = [s for s in self.attn_sites if s.proj == which]
 
-        def make_self():
-            ws, bs = [], []
-            for s in selfs:
-                ln, lin = s["mod"].to_context[0], s["mod"].to_context[1]
-                w = lin.weight.detach().float()
-                ws.append(w * ln.weight.detach().float()[None, :])
-                bs.append(lin.bias.detach().float() + w @ ln.bias.detach().float())
-            return ops.pack_weight(torch.cat(ws), torch.cat(bs), self.dev, split=bool(SPLIT_STATIC))
-
-        def make_cross():
-            return ops.pack_weight(torch.cat([s["mod"].to_kv.weight.detach().float() for s in crosses]), None, self.dev, split=bool(SPLIT_STATIC))
-
-        ws = self.W.get("ctx.self", make_self) if selfs else None
-        wc = self.W.get("ctx.cross", make_cross) if crosses else None
-        return selfs, crosses, ws, wc
+            def make():
+                ws, bs = zip(*(s.ctx_wb() for s in sites))
+                return ops.pack_weight(torch.cat(ws), None if bs[0] is None else torch.cat(bs), self.dev, split=bool(SPLIT_STATIC))
+            if sites:
+                out.append((which, sites, self.W.get("ctx." + which, make)))
+        return out
 
     def _emit_context_kv(self, plan, c_rows: Act, rows_per_batch: int, k_row0_self: int, k_row0_cross: int, tag: str):
-        """Project `c_rows` ([1,1,R*rpb,cond], already norm_cond'ed) for every site and write its K^/V^T rows."""
-        R, W = self.R, self.W
-        selfs, crosses, ws, wc = self._ctx_weights()
-        n = rows_per_batch
+        """Project `c_rows` ([1,1,R*rpb,cond], already norm_cond'ed) for every site and write its key / value rows."""
+        R, n = self.R, rows_per_batch
         jobs = []   # one K^/V^T job per site, all run by a single launch after the two projections
         proj = {}   # the projections' output buffers (the per-step table of the sampler refills them: enable_time_table)
-        if selfs:
-            mu, rs = self.f32buf(R * n), self.f32buf(R * n)
-            ops.rowstat(plan, c_rows, mode=1, rs=rs, mu=mu, eps=1e-5, label=f"ctx.{tag}.ln")
-            st = self.new(1, 1, R * n, ws.Cout)
-            ops.igemm(plan, c_rows, ws, st, mu=mu, rs=rs, label=f"ctx.{tag}.self")
-            proj["self"] = st
-            col = 0   # to_context of site i yields (k | v) = 2 * dim_head columns
-            for s in selfs:
-                d_ = s["dh"]
-                ops.kv_prep(plan, st.t, st.t, W.f32(s["name"] + ".k_scale", lambda s=s: s["mod"].k_scale), s["khat"], s["vt"], B=R, heads=1,
-                            rows=n, r0=k_row0_self, src_strides=(n * ws.Cout, ws.Cout, 0), k_strides=s["k_strides"], vt_strides=s["vt_strides"],
-                            k_off=col, v_off=col + d_, batch=jobs, head_dim=d_)
-                col += 2 * d_
-            assert col == ws.Cout
-        if crosses:
-            st = self.new(1, 1, R * n, wc.Cout)
-            ops.igemm(plan, c_rows, wc, st, label=f"ctx.{tag}.cross")
-            proj["cross"] = st
-            col = 0  # sites differ in head count / head dim (the mid blocks are always 8 x 64, ip.py:1380-1382): cumulative column offsets
-            for s in crosses:
-                d_ = s["dh"]
-                inner = s["heads"] * d_
-                if s["kind"] == "linear":   # the projected (k | v) rows as they are, behind the null row of the site's row buffer (no l2norm, no k_scale)
-                    ops.rows_copy(plan, st.t, s["kv"], B=R, rows=n, C=2 * inner, src_bs=n * wc.Cout, src_rs=wc.Cout, dst_bs=s["J"] * 2 * inner,
-                                  dst_rs=2 * inner, src_off=col, dst_off=k_row0_cross * 2 * inner, label=f"ctx.{tag}.linear_rows")
-                    col += 2 * inner
-                    continue
-                ops.kv_prep(plan, st.t, st.t, W.f32(s["name"] + ".k_scale", lambda s=s: s["mod"].k_scale), s["khat"], s["vt"], B=R,
-                            heads=s["heads"], rows=n, r0=k_row0_cross, src_strides=(n * wc.Cout, wc.Cout, d_), k_strides=s["k_strides"],
-                            vt_strides=s["vt_strides"], k_off=col, v_off=col + inner, batch=jobs, head_dim=d_)
-                col += 2 * inner
-            assert col == wc.Cout
+        for which, sites, w in self._ctx_weights():
+            mu = rs = None
+            if which == "self":   # (to_context's LayerNorm: one normalised input for all sites)
+                mu, rs = self.f32buf(R * n), self.f32buf(R * n)
+                ops.rowstat(plan, c_rows, mode=1, rs=rs, mu=mu, eps=1e-5, label=f"ctx.{tag}.ln")
+            proj[which] = st = self.new(1, 1, R * n, w.Cout)
+            ops.igemm(plan, c_rows, w, st, mu=mu, rs=rs, label=f"ctx.{tag}.{which}")
+            col = 0   # sites differ in head count / head dim (the mid blocks are always 8 x 64, ip.py:1380-1382): cumulative column offsets
+            for s in sites:
+                s.emit_ctx_rows(self, plan, st, col, n, k_row0_self if which == "self" else k_row0_cross, jobs, tag)
+                col += s.width
+            assert col == w.Cout
         if jobs:
             ops.kv_prep_multi(plan, jobs, self.dev, label=f"kv_ctx.{tag}")
         return proj
@@ -1033,27 +1082,13 @@ class UnetEngine:
         put the time tokens' rows in place (the static rows and the null row are there since set_conditioning)."""
         jobs = []
         for s in self.attn_sites:
-            if s["kind"] == "linear":
-                inner = s["heads"] * s["dh"]
-                ops.linctx_job(s["kv"], s["M"], R=self.R, heads=s["heads"], head_dim=s["dh"], J=s["J"], kv_bs=s["J"] * 2 * inner, kv_rs=2 * inner, batch=jobs)
+            s.linctx_job(self, jobs)
         if jobs:
             ops.linctx(plan, jobs, self.dev, label="linctx")
 
     def _emit_null_kv(self, plan):
-        """learned null key/value (ip.py:545-547 self: after the context; ip.py:805-808 cross: first)."""
-        R, W = self.R, self.W
         for s in self.attn_sites:
-            if s["kind"] == "linear":   # row 0 of the site's row buffer, raw (ip.py:849-852): (null k per head | null v per head)
-                inner = s["heads"] * s["dh"]
-                row = W.f16(s["name"] + ".null_row", lambda s=s: s["mod"].null_kv.detach().repeat(1, s["heads"]).reshape(-1))
-                ops.rows_copy(plan, row, s["kv"], B=R, rows=1, C=2 * inner, src_bs=0, src_rs=2 * inner, dst_bs=s["J"] * 2 * inner, dst_rs=2 * inner,
-                              label=s["name"] + ".kv_null")
-                continue
-            nk = W.f32(s["name"] + ".null_kv", lambda s=s: s["mod"].null_kv)
-            r0 = s["n_ctx"] if s["kind"] == "self" else 0
-            ops.kv_prep(plan, nk, nk, W.f32(s["name"] + ".k_scale", lambda s=s: s["mod"].k_scale), s["khat"], s["vt"], B=R, heads=s["heads"],
-                        rows=1, r0=r0, src_strides=(0, 0, 0), k_strides=s["k_strides"], vt_strides=s["vt_strides"], k_off=0, v_off=s["dh"],
-                        label=s["name"] + ".kv_null", head_dim=s["dh"])
+            s.emit_null(self, plan)
 
     # ------------------------------------------------------------------------------------------ static plan
     def _build_static_plan(self, n_tok: int):
@@ -1170,11 +1205,9 @@ class UnetEngine:
         ops.rows_copy(plan, W.f16("attn_pool.latents", lambda: pr.latents), lat.t, B=R, rows=nl, C=cd, src_bs=0, src_rs=cd, dst_bs=NL * cd,
                       dst_rs=cd, dst_off=nm * cd, label="attn_pool.latents")
         Jk = L + NL
-        Jp = ops._round_up(Jk, 32)
         for i, (pa, ff) in enumerate(pr.layers):
             nm_ = f"attn_pool.layers.{i}"
-            heads, dh = pa.heads, pa.dim_head
-            inner = heads * dh
+            inner = pa.heads * pa.dim_head
             kv = self.new(R, 1, Jk, 2 * inner)
             wkv = W.conv(nm_ + ".to_kv", pa.to_kv, split=SPLIT_STATIC)
             # k/v of the normalised sequence ...
@@ -1190,24 +1223,15 @@ class UnetEngine:
             lnb = W.f32(nm_ + ".norml.b", lambda pa=pa: _pad_vec(pa.norm_latents.bias, wkv.Cin_pad))
             ops.igemm(plan, lat, wkv, Act(kv.t, R, 1, NL, 2 * inner, 2 * inner, Jk * 2 * inner, off=L * 2 * inner), mu=mul, rs=rsl, pa=lnw, ps=lnb,
                       label=nm_ + ".kv_lat")
-            q = self.new(R, 1, NL, inner)
-            ops.igemm(plan, lat, W.conv(nm_ + ".to_q", pa.to_q, split=SPLIT_STATIC), q, mu=mul, rs=rsl, pa=lnw, ps=lnb, label=nm_ + ".to_q")
-            khat = torch.zeros(R, heads, Jp, dh, dtype=torch.float16, device=self.dev)
-            vt = torch.zeros(R, heads, dh, Jp, dtype=torch.float16, device=self.dev)
-            ks, vs = (heads * Jp * dh, Jp * dh, dh), (heads * dh * Jp, dh * Jp, Jp)
-            ops.kv_prep(plan, kv.t, kv.t, W.f32(nm_ + ".k_scale", lambda pa=pa: pa.k_scale), khat, vt, B=R, heads=heads, rows=Jk, r0=0,
-                        src_strides=(Jk * 2 * inner, 2 * inner, dh), k_strides=ks, vt_strides=vs, k_off=0, v_off=inner, label=nm_ + ".kv_prep",
-                        head_dim=dh)
-            o = self.new(R, 1, NL, inner)
-            ops.attention(plan, q.t, khat, vt, o.t, B=R, heads=heads, rows=NL, J=Jk, q_strides=(NL * inner, dh, inner), k_strides=ks,
-                          vt_strides=vs, o_strides=(NL * inner, dh, inner), q_scale=W.f32(nm_ + ".q_scale", lambda pa=pa: pa.q_scale),
-                          q_mult=SIM_SCALE * LOG2E, label=nm_ + ".attn", head_dim=dh,
-                          logit_bound=ops.attention_logit_bound(pa.q_scale, pa.k_scale, SIM_SCALE * LOG2E))
-            y = self.new(R, 1, NL, cd)
-            ops.igemm(plan, o, W.conv(nm_ + ".to_out", pa.to_out[0], split=SPLIT_STATIC), y, label=nm_ + ".to_out")
+            site = AttnSite.alloc("perceiver", nm_, pa, R, Jk, self.dev)   # (its keys are the sequence and the latents: no conditioning site, never registered)
+
+            def core(plan, q: Act) -> Act:      # (called before the next layer rebinds site / kv)
+                site.kv_prep(self, plan, kv.t, Jk, 0, Jk * kv.C, kv.C, 0, label=nm_ + ".kv_prep")
+                return self._attention(plan, q, site)
             lat2 = self.new(R, 1, NL, cd)
-            ops.ln_residual(plan, y, W.f32(nm_ + ".out.w", lambda pa=pa: pa.to_out[1].weight), lat2,
-                            beta=W.f32(nm_ + ".out.b", lambda pa=pa: pa.to_out[1].bias), res=lat, eps=1e-5, label=nm_ + ".out_norm")
+            self._token_attn(plan, lat, nm_, W.conv(nm_ + ".to_q", pa.to_q, split=SPLIT_STATIC), lnw, core, W.conv(nm_ + ".to_out", pa.to_out[0], split=SPLIT_STATIC),
+                             W.f32(nm_ + ".out.w", lambda pa=pa: pa.to_out[1].weight), lat2, b_in=lnb, stats=(mul, rsl),
+                             b_out=W.f32(nm_ + ".out.b", lambda pa=pa: pa.to_out[1].bias))
             lat = self._feed_forward(plan, lat2, ff, nm_ + ".ff", split=SPLIT_STATIC)
         return lat
 
@@ -1311,8 +1335,8 @@ class UnetEngine:
         # footprint of the tables and of the batched pass's intermediates, per stage and lane (fp32 scale / shift rows, fp16 hiddens, time
         # tokens and K / V projections).  Above the cap (large batches, long schedules, small-memory parts) the per-step chain stays: same
         # results, nine small launches per step.
-        selfs_, crosses_, ws_, wc_ = self._ctx_weights()
-        proj_c = (ws_.Cout if selfs_ else 0) + (wc_.Cout if crosses_ else 0)
+        ctx = [(which, w) for which, _, w in self._ctx_weights()]
+        proj_c = sum(w.Cout for _, w in ctx)
         chain_bytes = (8 * self.Tc + 8 * self.total_c) if TIME_CHAIN_F32 else 2 * (3 * self.Tc + 2 * self.total_c)   # hid, t_const, t, ss rows (fp32 t / ss: LINEAR_F32)
         # per row of the coefficient table: what STAYS for the life of the request (the four tables STEP_SLICE reads) and what the batched pass needs
         # while it runs (hiddens, time tokens, the time MLPs' output — as large as both scale / shift tables together).  The pass runs in chunks of
@@ -1343,16 +1367,9 @@ class UnetEngine:
         ss = self.f32buf(nmax, tw.shape[0]) if TIME_CHAIN_F32 else self.new(1, 1, nmax, tw.shape[0])
         tab_pa, tab_ps = self.f32buf(rows_all, total_c), self.f32buf(rows_all, total_c)
         segments = [(tab_pa, self.pa2), (tab_ps, self.ps2)]
-        selfs, crosses, ws, wc = selfs_, crosses_, ws_, wc_
-        n_tok_rows = rows_all * self.ntt
-        tab_self = tab_cross = mu = rs = None
-        if selfs:
-            mu, rs = self.f32buf(nmax * self.ntt), self.f32buf(nmax * self.ntt)
-            tab_self = self.new(1, 1, n_tok_rows, ws.Cout)
-            segments.append((tab_self.t, self._dyn_proj["self"].t))
-        if crosses:
-            tab_cross = self.new(1, 1, n_tok_rows, wc.Cout)
-            segments.append((tab_cross.t, self._dyn_proj["cross"].t))
+        tabs = {which: self.new(1, 1, rows_all * self.ntt, w.Cout) for which, w in ctx}     # every step's rows of the sites' batched projections
+        mu, rs = (self.f32buf(nmax * self.ntt), self.f32buf(nmax * self.ntt)) if "self" in tabs else (None, None)     # (the LayerNorm of ctx.self)
+        segments += [(tabs[which].t, self._dyn_proj[which].t) for which, _ in ctx]
         for ch in range(nchunks):
             r0 = ch * nmax
             n = min(nmax, rows_all - r0)
@@ -1378,12 +1395,12 @@ class UnetEngine:
                 ss_c = pre(ss, n)
             ops.scale_shift(tt, ss_c, W.f32("timemlp.gam", lambda: gam), W.get("timemlp.isc", lambda: isc.to(self.dev)),
                             W.get("timemlp.ish", lambda: ish.to(self.dev)), tab_pa[r0:r0 + n], tab_ps[r0:r0 + n], label=tag + "scale_shift")
-            if selfs:
-                ops.rowstat(tt, ct, mode=1, rs=rs[:n * self.ntt], mu=mu[:n * self.ntt], eps=1e-5, label=tag + "ctx.ln")
-                ops.igemm(tt, ct, ws, rows_of(tab_self, r0 * self.ntt, n * self.ntt), mu=mu[:n * self.ntt], rs=rs[:n * self.ntt], label=tag + "ctx.self")
-            if crosses:
-                ops.igemm(tt, ct, wc, rows_of(tab_cross, r0 * self.ntt, n * self.ntt), label=tag + "ctx.cross")
-        tt.keep += [tab_pa, tab_ps, times_all, hid, t_all, tok_raw, c_time, ss, tc_all.t, mu, rs] + ([tab_self.t] if selfs else []) + ([tab_cross.t] if crosses else [])
+            for which, w in ctx:
+                ln = dict(mu=mu[:n * self.ntt], rs=rs[:n * self.ntt]) if which == "self" else {}
+                if ln:
+                    ops.rowstat(tt, ct, mode=1, eps=1e-5, label=tag + "ctx.ln", **ln)
+                ops.igemm(tt, ct, w, rows_of(tabs[which], r0 * self.ntt, n * self.ntt), label=f"{tag}ctx.{which}", **ln)
+        tt.keep += [tab_pa, tab_ps, times_all, hid, t_all, tok_raw, c_time, ss, tc_all.t, mu, rs] + [t.t for t in tabs.values()]
         # the step plan with the chain replaced by the copy of the current step's rows
         one = Plan("slice")
         ops.step_slice(one, segments, step_ptr, label="time_table_rows")

@@ -202,7 +202,7 @@ class UnetEngine3D(UnetEngine):
         self.taps['mid_block1'] = x
         if u.mid_attn is not None:                    # Residual(Attention) over all f*h*w tokens, no context, no feed-forward
             tok = self.clip(x, f).tokens()
-            y, _ = self._self_attn(plan, tok, u.mid_attn.fn, "mid_attn.fn", with_context=False)
+            y, _ = self._self_attn_out(plan, self._self_attn(plan, tok, u.mid_attn.fn, "mid_attn.fn", with_context=False), tok, u.mid_attn.fn, "mid_attn.fn")
             x = Act(y.t, x.B, x.H, x.W, x.C, x.C, x.H * x.W * x.C)
         self.taps['mid_attn'] = x
         if not it:
@@ -378,23 +378,20 @@ class UnetEngine3D(UnetEngine):
         nm = name + ".fn.fn"
         C, P = x.C, x.H * x.W
         heads, dh = attn.heads, attn.dim_head
-        inner = heads * dh
         rows = R * f * P
         tok = Act(x.t, 1, 1, rows, C, C, rows * C, x.off)
-        mu, rs = self.f32buf(rows), self.f32buf(rows)
-        ops.rowstat(plan, tok, mode=1, rs=rs, mu=mu, eps=1e-5, label=nm + ".norm")
         wqkv = W.raw(nm + ".qkv", torch.cat((attn.to_q.weight.detach().float(), attn.to_kv.weight.detach().float())), None)
-        qkv = self.new(1, 1, rows, inner + 2 * dh)
-        ops.igemm(plan, tok, wqkv, qkv, mu=mu, rs=rs, pa=W.f32(nm + ".norm.g", lambda: _pad_vec(attn.norm.g, wqkv.Cin_pad)), label=nm + ".qkv")
-        o = self.new(1, 1, rows, inner)
-        ops.temporal_attention(plan, qkv, W.f32(nm + ".null_kv", lambda: attn.null_kv), W.f32(nm + ".q_scale", lambda: attn.q_scale),
-                               W.f32(nm + ".k_scale", lambda: attn.k_scale), W.get(f"{nm}.bias.{f}", lambda: self._position_bias(attn, f).to(self.dev)),
-                               o, B=R, F=f, P=P, heads=heads, causal=attn.causal, scale=SIM_SCALE, head_dim=dh, label=nm + ".attn")
-        y = self.new(1, 1, rows, C)
-        ops.igemm(plan, o, W.conv(nm + ".to_out", attn.to_out[0]), y, label=nm + ".to_out")
+        bias = W.get(f"{nm}.bias.{f}", lambda: self._position_bias(attn, f).to(self.dev))
+
+        def core(plan, qkv: Act) -> Act:
+            o = self.new(1, 1, rows, heads * dh)
+            ops.temporal_attention(plan, qkv, W.f32(nm + ".null_kv", lambda: attn.null_kv), W.f32(nm + ".q_scale", lambda: attn.q_scale),
+                                   W.f32(nm + ".k_scale", lambda: attn.k_scale), bias, o, B=R, F=f, P=P, heads=heads, causal=attn.causal,
+                                   scale=SIM_SCALE, head_dim=dh, label=nm + ".attn")
+            return o
         out = self.new(x.B, x.H, x.W, C)
-        ops.ln_residual(plan, y, W.f32(nm + ".out_g", lambda: attn.to_out[1].g), Act(out.t, 1, 1, rows, C, C, rows * C), res=tok, eps=1e-5,
-                        label=nm + ".out_norm")
+        self._token_attn(plan, tok, nm, wqkv, W.f32(nm + ".norm.g", lambda: _pad_vec(attn.norm.g, wqkv.Cin_pad)), core, W.conv(nm + ".to_out", attn.to_out[0]),
+                         W.f32(nm + ".out_g", lambda: attn.to_out[1].g), Act(out.t, 1, 1, rows, C, C, rows * C), in_label=".qkv")
         return out
 
     # ------------------------------------------------------------------------------------------ TransformerBlock (iv.py:1059-1091)
@@ -402,7 +399,8 @@ class UnetEngine3D(UnetEngine):
         cur = x
         for d, (attn, ff) in enumerate(tb.layers):
             nm = f"{name}.layers.{d}"
-            y, _ = self._self_attn(plan, self.clip(cur, f).tokens(), attn, nm + ".0", with_context=True)
+            tok = self.clip(cur, f).tokens()
+            y, _ = self._self_attn_out(plan, self._self_attn(plan, tok, attn, nm + ".0", with_context=True), tok, attn, nm + ".0")
             cur = Act(y.t, x.B, x.H, x.W, x.C, x.C, x.H * x.W * x.C)
             cur = self._chan_feed_forward(plan, cur, ff, nm + ".1", f)
         return cur

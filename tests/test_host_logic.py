@@ -155,7 +155,7 @@ def test_planner_dry_run_and_state_dict_surface(name):
         assert len(static) > 20
         # every attention site's K buffer has room for [context | null | self] rows
         for s in eng.attn_sites:
-            assert s["Jp"] % 32 == 0
+            assert s.Jp % 32 == 0
     # cast_model_parameters semantics (ip.py:1446-1470)
     same = u.cast_model_parameters(lowres_cond=u.lowres_cond, text_embed_dim=g["kwargs"]["text_embed_dim"], channels=3, channels_out=3,
                                    cond_on_text=True)

@@ -142,8 +142,8 @@ def test_linear_unet_plan_on_cpu_matches_reference_fixture(name, reference_weigh
     assert e_c < 1e-2 and e_n < 1e-2, (e_c, e_n)
     kinds = [k for k, _, _ in eng.step_plan.ops]
     labels = [l for _, _, l in eng.step_plan.ops]
-    sites = [s for s in eng.attn_sites if s["kind"] == "linear"]
-    assert [s["name"] for s in sites] == ["downs.0.1.cross_attn", "ups.1.0.cross_attn"]
+    sites = [s for s in eng.attn_sites if s.kind == "linear"]
+    assert [s.name for s in sites] == ["downs.0.1.cross_attn", "ups.1.0.cross_attn"]
     assert kinds.count(_abi.ENUMS["IMAGEN_OP_LINCTX"]) == 1, "ONE launch covers every linear site"
     assert kinds.count(_abi.ENUMS["IMAGEN_OP_LINEAR_XATTN"]) == len(sites)
     # M is ready before the first site reads it, and after the time tokens' rows are in place

@@ -125,21 +125,26 @@ def first_difference(old: dict, new: dict):
     return None
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--write", action="store_true", help="regenerate tests/golden/sampler_snapshot.json from this tree")
+def write_fixture(path: str, dig: dict) -> None:
+    with open(path, "w") as f:
+        f.write('{"labels": ' + json.dumps(dig["labels"]) + ',\n"plans": {\n'
+                + ",\n".join(f"{json.dumps(n)}: {json.dumps(v, separators=(',', ':'))}" for n, v in dig["plans"].items()) + "\n}}\n")
+    print(f"wrote {path} ({os.path.getsize(path)} bytes)")
+
+
+def main(snap=snapshot, fixture=FIXTURE, what="sampler launch lists"):
+    """The command line of this tool, and of tools/attn_planner_snapshot.py over its own snapshot() and fixture."""
+    ap = argparse.ArgumentParser(description=sys.modules[snap.__module__].__doc__.split("\n")[0])
+    ap.add_argument("--write", action="store_true", help=f"regenerate {os.path.relpath(fixture, ROOT)} from this tree")
     args = ap.parse_args()
-    new = digest(snapshot())
+    new = digest(snap())
     print(f"{len(new['plans'])} plans, {sum(len(p['ops']) for p in new['plans'].values())} ops")
     if args.write:
-        with open(FIXTURE, "w") as f:
-            f.write('{"labels": ' + json.dumps(new["labels"]) + ',\n"plans": {\n'
-                    + ",\n".join(f"{json.dumps(n)}: {json.dumps(v, separators=(',', ':'))}" for n, v in new["plans"].items()) + "\n}}\n")
-        print(f"wrote {FIXTURE} ({os.path.getsize(FIXTURE)} bytes)")
+        write_fixture(fixture, new)
         return 0
-    with open(FIXTURE) as f:
+    with open(fixture) as f:
         diff = first_difference(json.load(f), new)
-    print(diff or "sampler launch lists unchanged")
+    print(diff or what + " unchanged")
     return 1 if diff else 0
 
 
