@@ -25,7 +25,10 @@ constexpr int KT = 32;        // keys per tile
 constexpr int KSTR = 144;     // LDS bytes per K row at head dim 64 (128 + 16: conflict-free ds_read_b128)
 constexpr int VSTR = 72;      // LDS bytes per V^T row (64 + 8: conflict-free ds_read_b64)
 
-// D = head dim: 64 (every README config) or 32 (the reference's UnetConfig default, configs.py:48-49)
+// D = head dim: 64 (every README config), 32 (the reference's UnetConfig default, configs.py:48-49) or 128 (wide heads; also the Perceiver
+// pooling of such a unet).  D = 128 keeps the 128-query x 32-key tile and 256 threads: K tile 32 x 272 B + V^T tile 128 x 72 B = 17.5 KB
+// per stage, 35 KB for the two stages; per wave 4 O^T blocks (64 accumulator registers per lane) and 8 Q fragments (32 registers); a thread
+// stages TWO 16-byte items of K and of V^T per tile (512 of each) where the narrower heads stage one.
 template <int D>
 __global__ __launch_bounds__(256) void attention_kernel(const ImagenAttentionParams p) {
   constexpr int KS = D / 16;            // K=16 steps of the S^T contraction
@@ -64,16 +67,22 @@ __global__ __launch_bounds__(256) void attention_kernel(const ImagenAttentionPar
 
   const f16* kg = reinterpret_cast<const f16*>(p.k) + (size_t)b * p.k_bs + (size_t)hd * p.k_hs;
   const f16* vg = reinterpret_cast<const f16*>(p.vt) + (size_t)b * p.vt_bs + (size_t)hd * p.vt_hs;
-  // staging roles: K tile 32 keys x D/8 groups of 8 dims; V^T tile D dims x 4 groups of 8 keys (D = 32: threads 0-127 only)
+  // staging roles: K tile 32 keys x D/8 groups of 8 dims; V^T tile D dims x 4 groups of 8 keys (D = 32: threads 0-127 only; D = 128: a
+  // second item per thread, 16 keys / 64 dims behind the first)
   const bool stager = tid < 4 * D;
   const int sk_key = tid / (D / 8), sk_dg = tid % (D / 8);
   const int sv_d = (tid >> 2) & (D - 1), sv_kg = tid & 3;
 
   uint4 k_stage = make_uint4(0, 0, 0, 0), v_stage = make_uint4(0, 0, 0, 0);
+  uint4 k_stage1 = make_uint4(0, 0, 0, 0), v_stage1 = make_uint4(0, 0, 0, 0);   // (D = 128 only; named scalars, not arrays: see attention_kernel_w8)
   auto tile_load = [&](int kt0) {
     if (stager) {
       k_stage = *reinterpret_cast<const uint4*>(kg + (size_t)(kt0 + sk_key) * p.k_rs + sk_dg * 8);
       v_stage = *reinterpret_cast<const uint4*>(vg + (size_t)sv_d * p.vt_ds + kt0 + sv_kg * 8);
+      if constexpr (D > 64) {
+        k_stage1 = *reinterpret_cast<const uint4*>(kg + (size_t)(kt0 + sk_key + 16) * p.k_rs + sk_dg * 8);
+        v_stage1 = *reinterpret_cast<const uint4*>(vg + (size_t)(sv_d + 64) * p.vt_ds + kt0 + sv_kg * 8);
+      }
     }
   };
   auto tile_store = [&](char* buf) {
@@ -82,6 +91,12 @@ __global__ __launch_bounds__(256) void attention_kernel(const ImagenAttentionPar
       uint2* vd = reinterpret_cast<uint2*>(buf + KBYTES + sv_d * VSTR + sv_kg * 16);
       vd[0] = make_uint2(v_stage.x, v_stage.y);
       vd[1] = make_uint2(v_stage.z, v_stage.w);
+      if constexpr (D > 64) {
+        *reinterpret_cast<uint4*>(buf + (sk_key + 16) * KSTRD + sk_dg * 16) = k_stage1;
+        uint2* vd1 = reinterpret_cast<uint2*>(buf + KBYTES + (sv_d + 64) * VSTR + sv_kg * 16);
+        vd1[0] = make_uint2(v_stage1.x, v_stage1.y);
+        vd1[1] = make_uint2(v_stage1.z, v_stage1.w);
+      }
     }
   };
 
@@ -615,9 +630,13 @@ int launch_attention(const ImagenAttentionParams* p, hipStream_t s) {
       IMAGEN_CHECK(reinterpret_cast<uintptr_t>(a.ptr) % a.m == 0, "attention: %s = %p must be %d-byte aligned", a.name, a.ptr, a.m);
   }
   IMAGEN_CHECK(p->vt_ds >= ((p->J + 31) & ~31), "attention: vt_ds = %d holds fewer than round_up(J = %d, 32) keys", p->vt_ds, p->J);
-  IMAGEN_CHECK(p->head_dim == 0 || p->head_dim == 64 || p->head_dim == 32, "attention: head_dim %d (64 or 32)", p->head_dim);
+  IMAGEN_CHECK(p->head_dim == 0 || p->head_dim == 64 || p->head_dim == 32 || p->head_dim == 128, "attention: head_dim %d (128, 64 or 32)", p->head_dim);
+  // head dim 128 is planned with the heads side by side inside a token row only: a narrower row would let the 256-byte head slices of
+  // neighbouring rows overlap
+  IMAGEN_CHECK(p->head_dim != 128 || (p->q_rs >= p->heads * 128 && p->o_rs >= p->heads * 128),
+               "attention: head_dim 128 needs row strides of at least heads * 128 = %d elements (q_rs %d, o_rs %d)", p->heads * 128, p->q_rs, p->o_rs);
   IMAGEN_CHECK(p->softmax_mode == 0 || p->softmax_mode == 1, "attention: softmax_mode %d", p->softmax_mode);
-  if (p->head_dim != 32 && p->rows >= 256) {
+  if (p->head_dim != 32 && p->head_dim != 128 && p->rows >= 256) {   // (the 8-wave and bounded-logit tilings are built for head dim 64)
     dim3 grid((p->rows + 255) / 256, p->heads, p->B);
     auto launch = [&](auto kern, int lds, int threads = 512) {
       static bool attr_done[16] = {};   // (per kernel instantiation: one lambda instantiation per `kern` type; per device)
@@ -642,6 +661,7 @@ int launch_attention(const ImagenAttentionParams* p, hipStream_t s) {
   }
   dim3 grid((p->rows + 127) / 128, p->heads, p->B);
   if (p->head_dim == 32) hipLaunchKernelGGL(attention_kernel<32>, grid, dim3(256), 0, s, *p);
+  else if (p->head_dim == 128) hipLaunchKernelGGL(attention_kernel<128>, grid, dim3(256), 0, s, *p);
   else hipLaunchKernelGGL(attention_kernel<64>, grid, dim3(256), 0, s, *p);
   return imagen_hip_status("attention");
 }

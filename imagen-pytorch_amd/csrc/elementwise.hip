@@ -181,14 +181,13 @@ __global__ __launch_bounds__(256) void ln_residual_kernel(const ImagenLnResidual
 }
 
 // ------------------------------------------------------------------------------------------------ q / kv preparation
-// head_dim / 8 lanes (8 | 4) per head row; each lane owns 8 consecutive dims.
-__device__ __forceinline__ int head_dim_of(int v) { return v == 32 ? 32 : 64; }
+// head_dim / 8 lanes (16 | 8 | 4) per head row; each lane owns 8 consecutive dims.  The launchers give a workgroup 32 head rows (the grid
+// of a KV_PREP_MULTI launch is one for jobs of every head dim): at head dim 128 its 256 threads hold 16 rows at a time and make two passes,
+// at 64 one pass of 32, at 32 one pass of 64 (half of that grid's workgroups find no rows).
+__device__ __forceinline__ int head_dim_of(int v) { return v == 32 ? 32 : v == 128 ? 128 : 64; }
+__device__ __forceinline__ int head_dim_shift(int D) { return D == 128 ? 4 : D == 64 ? 3 : 2; }   // log2(D / 8)
 
-__global__ __launch_bounds__(256) void qnorm_kernel(const ImagenQnormParams p) {
-  const int D = head_dim_of(p.head_dim), lpr = D >> 3, sh = D == 64 ? 3 : 2;
-  const int item = blockIdx.x * (256 >> sh) + (threadIdx.x >> sh);  // (row, head)
-  const int dg = threadIdx.x & (lpr - 1);
-  if (item >= p.rows * p.heads) return;
+__device__ __forceinline__ void qnorm_item(const ImagenQnormParams& p, int item, int dg, int D, int lpr) {
   const int row = item / p.heads, hd = item - row * p.heads;
   f16* q = reinterpret_cast<f16*>(p.q) + (size_t)row * p.ld + hd * D + dg * 8;
   const f16x8 v = *reinterpret_cast<const f16x8*>(q);
@@ -203,13 +202,31 @@ __global__ __launch_bounds__(256) void qnorm_kernel(const ImagenQnormParams p) {
   *reinterpret_cast<f16x8*>(q) = o;
 }
 
+__global__ __launch_bounds__(256) void qnorm_kernel(const ImagenQnormParams p) {
+  const int D = head_dim_of(p.head_dim), lpr = D >> 3, sh = head_dim_shift(D);
+  const int ipp = 256 >> sh;                                   // (row, head) items per pass
+  const int base = blockIdx.x * (ipp > 32 ? ipp : 32) + (threadIdx.x >> sh);
+  const int dg = threadIdx.x & (lpr - 1);
+  for (int i0 = 0; i0 < 32; i0 += ipp) {                       // (the lanes of an item leave together)
+    const int item = base + i0;
+    if (item < p.rows * p.heads) qnorm_item(p, item, dg, D, lpr);
+  }
+}
+
+__device__ __forceinline__ void kv_prep_row(const ImagenKvPrepParams& p, int b, int hd, int row, int dg, int lpr);
+
 __device__ __forceinline__ void kv_prep_body(const ImagenKvPrepParams& p, int bx, int bh) {
   if (bh >= p.B * p.heads) return;
   const int b = bh / p.heads, hd = bh - b * p.heads;
-  const int D = head_dim_of(p.head_dim), lpr = D >> 3, sh = D == 64 ? 3 : 2;
-  const int row = bx * (256 >> sh) + (threadIdx.x >> sh);
+  const int D = head_dim_of(p.head_dim), lpr = D >> 3, sh = head_dim_shift(D);
+  const int rpp = 256 >> sh;                                   // rows per pass
+  const int base = bx * (rpp > 32 ? rpp : 32) + (threadIdx.x >> sh);
   const int dg = threadIdx.x & (lpr - 1);
-  if (row >= p.rows) return;
+  for (int r0 = 0; r0 < 32; r0 += rpp)                         // (the lanes of a row leave together)
+    if (base + r0 < p.rows) kv_prep_row(p, b, hd, base + r0, dg, lpr);
+}
+
+__device__ __forceinline__ void kv_prep_row(const ImagenKvPrepParams& p, int b, int hd, int row, int dg, int lpr) {
   const size_t soff = (size_t)b * p.src_bs + (size_t)row * p.src_rs + (size_t)hd * p.src_hs + dg * 8;
   float kv[8], vv[8];
   if (p.src_is_f32) {
@@ -1034,8 +1051,8 @@ int launch_ln_residual(const ImagenLnResidualParams* p, hipStream_t s) {
 
 int launch_qnorm(const ImagenQnormParams* p, hipStream_t s) {
   IMAGEN_CHECK(p->q && p->q_scale && p->rows > 0 && p->heads > 0, "qnorm: null tensors / empty problem");
-  IMAGEN_CHECK(p->head_dim == 0 || p->head_dim == 32 || p->head_dim == 64, "qnorm: head_dim %d", p->head_dim);
-  IMAGEN_CHECK(al8(p->ld) && al16(p->q) && p->ld >= p->heads * (p->head_dim == 32 ? 32 : 64), "qnorm: row stride %d must be a multiple of 8 covering the %d heads, rows 16-byte aligned",
+  IMAGEN_CHECK(p->head_dim == 0 || p->head_dim == 32 || p->head_dim == 64 || p->head_dim == 128, "qnorm: head_dim %d", p->head_dim);
+  IMAGEN_CHECK(al8(p->ld) && al16(p->q) && p->ld >= p->heads * (p->head_dim == 0 ? 64 : p->head_dim), "qnorm: row stride %d must be a multiple of 8 covering the %d heads, rows 16-byte aligned",
                p->ld, p->heads);
   IMAGEN_CHECK((long)p->rows * p->heads <= kIntMax - 64, "qnorm: rows * heads does not fit an int");
   const int items = p->rows * p->heads;
@@ -1048,7 +1065,7 @@ int launch_qnorm(const ImagenQnormParams* p, hipStream_t s) {
 static int check_kv_prep(const ImagenKvPrepParams* p) {
   IMAGEN_CHECK(p->rows > 0 && p->B > 0 && p->heads > 0 && p->r0 >= 0, "kv_prep: empty");
   IMAGEN_CHECK(p->k_src && p->v_src && p->k_scale && p->khat && p->vt, "kv_prep: null pointer");
-  IMAGEN_CHECK(p->head_dim == 0 || p->head_dim == 32 || p->head_dim == 64, "kv_prep: head_dim %d", p->head_dim);
+  IMAGEN_CHECK(p->head_dim == 0 || p->head_dim == 32 || p->head_dim == 64 || p->head_dim == 128, "kv_prep: head_dim %d", p->head_dim);
   IMAGEN_CHECK(al8(p->k_bs) && al8(p->k_hs) && al8(p->k_rs) && al16(p->khat), "kv_prep: K-hat strides must be multiples of 8, rows 16-byte aligned (%d %d %d)",
                p->k_bs, p->k_hs, p->k_rs);
   IMAGEN_CHECK(p->src_is_f32 || (al8(p->src_bs) && al8(p->src_rs) && al8(p->src_hs) && al16(p->k_src) && al16(p->v_src)),

@@ -24,17 +24,14 @@ constexpr float kLog2e = 1.4426950408889634f;
 constexpr int kTileRows = 256;   // pixels per workgroup: 4 waves x 2 sub-tiles of 32
 
 // ---------------------------------------------------------------------------------------------- LINCTX
-__global__ __launch_bounds__(256) void linctx_kernel(const ImagenLinCtxParams m) {
-  const ImagenLinCtxJob job = m.jobs[blockIdx.z];
-  const int bh = blockIdx.x;
-  if (bh >= job.R * job.heads) return;   // (the grid covers the largest job; uniform over the workgroup)
+// MAXNA: the rows of M a thread owns, D^2 / 256 at most (head dim 64: 16, 32: 4; 128: 64 — two threads share a column and M, 64 KB per
+// (row, head), goes from the threads' accumulators straight to global memory: the LDS holds the 256 partial reductions and two D-vectors)
+template <int MAXNA>
+__device__ __forceinline__ void linctx_body(const ImagenLinCtxJob& job, int bh, float* red, float* cmax, float* crcp) {
   const int D = job.head_dim, J = job.J, rs = job.kv_rs;
   const int r = bh / job.heads, h = bh % job.heads;
   const f16* kcol = static_cast<const f16*>(job.kv) + (size_t)r * job.kv_bs + h * D;
   const f16* vcol = kcol + job.heads * D;
-  __shared__ float red[256];
-  __shared__ float cmax[64];
-  __shared__ float crcp[64];
   const int t = threadIdx.x, d = t % D, g = t / D, G = 256 / D;
   // column maxima and sums of exp over the tokens: G partial reductions per column, merged through LDS
   float mx = -INFINITY;
@@ -59,15 +56,15 @@ __global__ __launch_bounds__(256) void linctx_kernel(const ImagenLinCtxParams m)
   }
   __syncthreads();
   // M[a][b] = sum_j w[j][a] v[j][b]: this thread owns column b = d of the rows a = g, g + G, ... (D / G = D^2 / 256 of them)
-  float acc[16];
+  float acc[MAXNA];
 #pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  for (int i = 0; i < MAXNA; ++i) acc[i] = 0.f;
   const int NA = D / G;
   for (int j = 0; j < J; ++j) {
     const float vb = (float)vcol[(size_t)j * rs + d];
     const f16* krow = kcol + (size_t)j * rs;
 #pragma unroll
-    for (int i = 0; i < 16; ++i)
+    for (int i = 0; i < MAXNA; ++i)
       if (i < NA) {
         const int a = g + G * i;
         acc[i] += __builtin_amdgcn_exp2f(((float)krow[a] - cmax[a]) * kLog2e) * vb;
@@ -75,39 +72,54 @@ __global__ __launch_bounds__(256) void linctx_kernel(const ImagenLinCtxParams m)
   }
   float* M = job.M + (size_t)bh * D * D;
 #pragma unroll
-  for (int i = 0; i < 16; ++i)
+  for (int i = 0; i < MAXNA; ++i)
     if (i < NA) {
       const int a = g + G * i;
       M[a * D + d] = acc[i] * crcp[a];
     }
 }
 
+__global__ __launch_bounds__(256) void linctx_kernel(const ImagenLinCtxParams m) {
+  const ImagenLinCtxJob job = m.jobs[blockIdx.z];
+  const int bh = blockIdx.x;
+  if (bh >= job.R * job.heads) return;   // (the grid covers the largest job; uniform over the workgroup)
+  __shared__ float red[256];
+  __shared__ float cmax[128];
+  __shared__ float crcp[128];
+  if (job.head_dim == 128) linctx_body<64>(job, bh, red, cmax, crcp);   // (uniform over the workgroup: the barriers inside are met by all)
+  else linctx_body<16>(job, bh, red, cmax, crcp);
+}
+
 // ---------------------------------------------------------------------------------------------- LINEAR_XATTN
 template <int D>
 __global__ __launch_bounds__(256) void linear_xattn_kernel(const ImagenLinearXattnParams p) {
   constexpr int KS = D / 16, DB = D / 32;
+  // D = 128: M^T as hi + lo A fragments is 8 x 4 x 2 x 4 = 256 registers a lane.  NS = 2 waves share a sub-tile of 32 pixels, each with DBW = 2
+  // of the 4 column blocks of o (128 registers of fragments, 32 of accumulators, 64 of P); both compute the pixel's softmax.  D <= 64: NS = 1.
+  constexpr int NS = D > 64 ? 2 : 1, DBW = DB / NS;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, half = lane >> 5;
   const int h = blockIdx.y, r = blockIdx.z;
   const int n0 = blockIdx.x * kTileRows;          // a tile lies inside ONE image: the grid is (tiles of an image, head, image)
   const int nvalid = min(kTileRows, p.rows - n0);
-  if (wave * 32 >= nvalid) return;                // (wave-uniform; no workgroup barrier follows)
+  const int wsub = wave / NS, db0 = (wave % NS) * DBW;
+  if (wsub * 32 >= nvalid) return;                // (wave-uniform; no workgroup barrier follows)
 
   // A fragments: row b = 32 db + l31 of M^T, k = a = 16 s + 8 half + i
   const float* M = p.M + (size_t)(r * p.heads + h) * D * D;
-  f16x8 mh[KS][DB], ml[KS][DB];
+  f16x8 mh[KS][DBW], ml[KS][DBW];
 #pragma unroll
   for (int s = 0; s < KS; ++s)
 #pragma unroll
-    for (int db = 0; db < DB; ++db)
+    for (int db = 0; db < DBW; ++db)
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
-        const float v = M[(16 * s + 8 * half + i) * D + 32 * db + l31];
+        const float v = M[(16 * s + 8 * half + i) * D + 32 * (db0 + db) + l31];
         const f16 hi = (f16)v;
         mh[s][db][i] = hi;
         ml[s][db][i] = (f16)(v - (float)hi);
       }
 
-  for (int sub = wave; sub * 32 < nvalid; sub += 4) {
+  for (int sub = wsub; sub * 32 < nvalid; sub += 4 / NS) {
     const int n = n0 + sub * 32 + l31;
     const bool ok = n < p.rows;
     const size_t row = (size_t)r * p.rows + (ok ? n : p.rows - 1);   // lanes past the image read its last row and store nothing
@@ -136,9 +148,9 @@ __global__ __launch_bounds__(256) void linear_xattn_kernel(const ImagenLinearXat
     sum += __shfl_xor(sum, 32);
     const float sc = 8.0f / sum;   // ip.py:869 (scale = 8) and the softmax denominator, on the fp32 accumulator
 
-    f32x16 acc[DB];
+    f32x16 acc[DBW];
 #pragma unroll
-    for (int db = 0; db < DB; ++db) {
+    for (int db = 0; db < DBW; ++db) {
 #pragma unroll
       for (int k = 0; k < 16; ++k) acc[db][k] = 0.f;
 #pragma unroll
@@ -150,9 +162,9 @@ __global__ __launch_bounds__(256) void linear_xattn_kernel(const ImagenLinearXat
     }
     // D register k of a lane = column b = 32 db + 8 (k / 4) + 4 half + k % 4 of its pixel: quads qd and qd + 2 are exchanged between the
     // half-waves (imagen_pair_quads, all lanes), one 16-byte store per lane and pair
-    f16* op = static_cast<f16*>(p.o) + row * p.ld_o + h * D + 16 * half;
+    f16* op = static_cast<f16*>(p.o) + row * p.ld_o + h * D + 32 * db0 + 16 * half;
 #pragma unroll
-    for (int db = 0; db < DB; ++db)
+    for (int db = 0; db < DBW; ++db)
 #pragma unroll
       for (int qd = 0; qd < 2; ++qd) {
         f16x4 a, b;
@@ -178,7 +190,7 @@ int launch_linctx(const ImagenLinCtxParams* p, hipStream_t s) {
 
 int launch_linear_xattn(const ImagenLinearXattnParams* p, hipStream_t s) {
   IMAGEN_CHECK(p->q && p->M && p->o, "linear_xattn: null pointer");
-  IMAGEN_CHECK(p->head_dim == 64 || p->head_dim == 32, "linear_xattn: head_dim %d (the kernel is built for 64 and 32)", p->head_dim);
+  IMAGEN_CHECK(p->head_dim == 64 || p->head_dim == 32 || p->head_dim == 128, "linear_xattn: head_dim %d (the kernel is built for 128, 64 and 32)", p->head_dim);
   IMAGEN_CHECK(p->R > 0 && p->R <= 65535 && p->heads > 0 && p->heads <= 65535 && p->rows > 0, "linear_xattn: bad shape (R %d, heads %d, rows %d)",
                p->R, p->heads, p->rows);
   const int inner = p->heads * p->head_dim;
@@ -187,6 +199,7 @@ int launch_linear_xattn(const ImagenLinearXattnParams* p, hipStream_t s) {
   IMAGEN_CHECK(((size_t)p->q & 15) == 0 && ((size_t)p->o & 15) == 0 && ((size_t)p->M & 3) == 0, "linear_xattn: q / o rows must be 16-byte aligned");
   const dim3 grid((unsigned)((p->rows + kTileRows - 1) / kTileRows), (unsigned)p->heads, (unsigned)p->R);
   if (p->head_dim == 64) hipLaunchKernelGGL(linear_xattn_kernel<64>, grid, dim3(256), 0, s, *p);
+  else if (p->head_dim == 128) hipLaunchKernelGGL(linear_xattn_kernel<128>, grid, dim3(256), 0, s, *p);
   else hipLaunchKernelGGL(linear_xattn_kernel<32>, grid, dim3(256), 0, s, *p);
   return imagen_hip_status("linear_xattn");
 }

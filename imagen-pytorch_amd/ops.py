@@ -798,6 +798,7 @@ def rowstat(plan: Plan, x1: Act, *, mode: int, rs: torch.Tensor, mu: Optional[to
     return p
 
 
+HEAD_DIMS = (32, 64, 128)   # what ATTENTION / QNORM / KV_PREP / LINCTX / LINEAR_XATTN are built for (the temporal kernels and ROWCHAIN: fewer)
 ATTN_BOUNDED = 1   # (module constant; 0: always the online softmax)
 ATTN_BOUND_MAX = 14.0    # log2 units: exp2(s) of every key stays inside fp16's normal range (2^-14 .. 2^14) while |s| <= 14
 
@@ -812,10 +813,10 @@ def attention_logit_bound(q_scale: torch.Tensor, k_scale: torch.Tensor, q_mult: 
 def attention(plan: Plan, q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, o: torch.Tensor, *, B, heads, rows, J,
               q_strides, k_strides, vt_strides, o_strides, q_scale: Optional[torch.Tensor] = None, q_mult: float = 0.0, label: str = "",
               head_dim: int = 64, logit_bound: Optional[float] = None):
-    """q_scale / q_mult: fuse QNORM into the q load (q rows raw); None: q was normalised by a QNORM op.  head_dim: 64 or 32.
+    """q_scale / q_mult: fuse QNORM into the q load (q rows raw); None: q was normalised by a QNORM op.  head_dim: 64, 32 or 128.
     logit_bound: an upper bound of |q . k| in the kernel's log2 units (`attention_logit_bound`); bounds up to ATTN_BOUND_MAX select the
     bounded-logit softmax (no running maximum; softmax_mode 1 of include/imagen_hip.h), larger ones or None the online softmax."""
-    assert head_dim in (32, 64), f"attention head dim {head_dim}: the kernels are built for 64 and 32"
+    assert head_dim in HEAD_DIMS, f"attention head dim {head_dim}: the kernels are built for 64, 32 and 128"
     p = STRUCTS["ImagenAttentionParams"]()
     p.head_dim = head_dim
     if ATTN_BOUNDED and logit_bound is not None and logit_bound <= ATTN_BOUND_MAX:
@@ -836,7 +837,7 @@ def kv_prep(plan: Plan, k_src: torch.Tensor, v_src: torch.Tensor, k_scale: torch
             batch: Optional[list] = None, head_dim: int = 64):
     """k_off / v_off: element offsets of the k and v columns inside the source rows.  With `batch` the job is appended to that
     list instead of the plan; kv_prep_multi(plan, batch) then runs all of them in one launch."""
-    assert head_dim in (32, 64)
+    assert head_dim in HEAD_DIMS
     p = STRUCTS["ImagenKvPrepParams"]()
     p.head_dim = head_dim
     es = k_src.element_size()
@@ -862,7 +863,7 @@ def _check_kv_job(p, i: int):
         refuse("empty")
     if not (p.k_src and p.v_src and p.k_scale and p.khat and p.vt):
         refuse("null pointer")
-    if p.head_dim not in (0, 32, 64):
+    if p.head_dim not in (0,) + HEAD_DIMS:
         refuse(f"head_dim {p.head_dim}")
     if p.k_bs % 8 or p.k_hs % 8 or p.k_rs % 8 or p.khat % 16:
         refuse(f"K-hat strides must be multiples of 8, rows 16-byte aligned ({p.k_bs} {p.k_hs} {p.k_rs})")
@@ -896,8 +897,8 @@ def linctx_job(kv: torch.Tensor, M: torch.Tensor, *, R, heads, head_dim, J, kv_b
     [R, heads, head_dim, head_dim].  The launcher sees the jobs in device memory only, so the checks are made here."""
     def refuse(msg):
         raise _abi.ImagenHipError(f"linctx: job {len(batch)}: {msg}")
-    if head_dim not in (32, 64):
-        refuse(f"head_dim {head_dim}: the kernel is built for 64 and 32")
+    if head_dim not in HEAD_DIMS:
+        refuse(f"head_dim {head_dim}: the kernel is built for 64, 32 and 128")
     if not (R > 0 and heads > 0 and J > 0):
         refuse("empty")
     if kv.dtype != torch.float16 or M.dtype != torch.float32 or not M.is_contiguous() or M.numel() != R * heads * head_dim * head_dim:
@@ -925,7 +926,7 @@ def linctx(plan: Plan, batch: list, device, label: str = ""):
 
 def linear_xattn(plan: Plan, q: Act, M: torch.Tensor, o: Act, *, heads: int, head_dim: int, rows_per_batch: int, label: str = ""):
     """LINEAR_XATTN (include/imagen_hip.h): o = 8 * softmax_d(q) M per (pixel, head); q, o: token rows of R images x rows_per_batch."""
-    assert head_dim in (32, 64), f"linear cross-attention head dim {head_dim}: the kernel is built for 64 and 32"
+    assert head_dim in HEAD_DIMS, f"linear cross-attention head dim {head_dim}: the kernel is built for 64, 32 and 128"
     assert q.rows == o.rows and q.rows % rows_per_batch == 0 and q.C == o.C == heads * head_dim
     assert q.bs == q.H * q.W * q.ld and o.bs == o.H * o.W * o.ld, "rows of consecutive images must be consecutive"
     R = q.rows // rows_per_batch
@@ -938,7 +939,7 @@ def linear_xattn(plan: Plan, q: Act, M: torch.Tensor, o: Act, *, heads: int, hea
 
 
 def qnorm(plan: Plan, q: torch.Tensor, q_scale: torch.Tensor, *, rows, heads, ld, mult, label: str = "", head_dim: int = 64):
-    assert head_dim in (32, 64)
+    assert head_dim in HEAD_DIMS
     p = STRUCTS["ImagenQnormParams"]()
     p.head_dim = head_dim
     p.q, p.q_scale, p.rows, p.heads, p.ld, p.mult = q.data_ptr(), q_scale.data_ptr(), rows, heads, ld, mult

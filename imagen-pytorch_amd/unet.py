@@ -139,9 +139,9 @@ class Unet(nn.Module):
             # positionally (ip.py:1315, 1357, 1366), so dim_out collides with kernel_sizes and Unet(...) raises TypeError — no
             # checkpoint with this flag exists
             _unsupported('cross_embed_downsample')
-        if attn_dim_head not in (32, 64):
-            raise NotImplementedError(f"attn_dim_head = {attn_dim_head}: the attention kernels are built for head dims 64 (every README config) "
-                                      "and 32 (the reference's UnetConfig default, configs.py:48-49)")
+        if attn_dim_head not in (32, 64, 128):
+            raise NotImplementedError(f"attn_dim_head = {attn_dim_head}: the attention kernels are built for head dims 64 (every README config), "
+                                      "32 (the reference's UnetConfig default, configs.py:48-49) and 128 (wide heads)")
 
         self.channels = channels
         self.channels_out = channels_out if channels_out is not None else channels

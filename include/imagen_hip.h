@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define IMAGEN_ABI_VERSION 15 /* 15: TEMPORAL_ATTENTION takes F <= 128 (clips of 33 .. 128 frames run on a tiled kernel; F <= 32 launches what it launched before; no struct changed);  14: LINCTX, LINEAR_XATTN (LinearCrossAttention: Unet(use_linear_cross_attn=...); no struct of before changed);  13: ImagenLincombParams.thr1_out / thr3_out (LINCOMB writes out the thresholded operands it sums: the self-conditioning input of the ElucidatedImagen sampler; NULL = the launch of before);  12: ImagenTemporalAttentionParams.head_dim (the temporal attention of Imagen-Video at head dim 32, the reference's Unet3DConfig default; 0 = 64: plans of before are unchanged);  11: ImagenDdpmUpdateParams.row_keys (per-row Philox key + sample index: requests merged into one batch draw their own noise);  10: ImagenIgemmParams.pad_x1 (a KH x KW window with its own x padding: the causal temporal conv of Imagen-Video as ONE (3 x 1)-tap launch);  9: LINEAR_F32, SCALE_SHIFT ss_f32;  8: ROWCHAIN, the latency probes;  3: head_dim in the attention / QNORM / KV_PREP params; 4: DDPM_UPDATE x0_thr; 5: GCA_TAIL; 6: ACT_PREP self_stat, STEP_SLICE;
+#define IMAGEN_ABI_VERSION 15 /* 15: TEMPORAL_ATTENTION takes F <= 128 (clips of 33 .. 128 frames run on a tiled kernel; F <= 32 launches what it launched before; no struct changed), and head_dim 128 is accepted by ATTENTION / QNORM / KV_PREP / LINCTX / LINEAR_XATTN (Unet(attn_dim_head=128); no struct changed, no new op kind);  14: LINCTX, LINEAR_XATTN (LinearCrossAttention: Unet(use_linear_cross_attn=...); no struct of before changed);  13: ImagenLincombParams.thr1_out / thr3_out (LINCOMB writes out the thresholded operands it sums: the self-conditioning input of the ElucidatedImagen sampler; NULL = the launch of before);  12: ImagenTemporalAttentionParams.head_dim (the temporal attention of Imagen-Video at head dim 32, the reference's Unet3DConfig default; 0 = 64: plans of before are unchanged);  11: ImagenDdpmUpdateParams.row_keys (per-row Philox key + sample index: requests merged into one batch draw their own noise);  10: ImagenIgemmParams.pad_x1 (a KH x KW window with its own x padding: the causal temporal conv of Imagen-Video as ONE (3 x 1)-tap launch);  9: LINEAR_F32, SCALE_SHIFT ss_f32;  8: ROWCHAIN, the latency probes;  3: head_dim in the attention / QNORM / KV_PREP params; 4: DDPM_UPDATE x0_thr; 5: GCA_TAIL; 6: ACT_PREP self_stat, STEP_SLICE;
                                * 7: every launch carries sizeof(its params struct) (a stale mirror of a struct fails loudly), ImagenIgemmParams.dbg -> launcher_word, kernel families 6 and 7, ImagenAttentionParams.softmax_mode */
 
 typedef void* imagen_stream_t; /* hipStream_t */
