@@ -145,14 +145,15 @@ class ElucidatedImagen(Imagen):
 
     # ---- per-stage plans --------------------------------------------------------------------------------------------------
     def _build_stage(self, idx: int, B: int, device, *, cond_scale: float, with_text: bool, inject_noise: bool, sample_offset: int,
-                     resample_times: int = 0, frames: int = 0, prompt_frames: tuple = (0, 0), sigma_overrides: Optional[dict] = None):
+                     resample_times: int = 0, frames: int = 0, prompt_frames: tuple = (0, 0), sigma_overrides: Optional[dict] = None, size=None):
         unet = self.unets[idx]
+        size = self.image_sizes[idx] if size is None else size      # (an int, or (H, W): Imagen.sample(image_shapes=...))
         hp = self.hparams[idx]
         if sigma_overrides is not None:                  # sample(sigma_min=, sigma_max=), el.py:425-426, 647-648
             hp = hp._replace(**{k: v[idx] for k, v in sigma_overrides.items() if v[idx] is not None})
         cfg = cond_scale != 1.
         R = resample_times
-        key = ("edm", idx, B, self.image_sizes[idx], str(device), float(cond_scale), with_text, inject_noise, sample_offset,
+        key = ("edm", idx, B, size, str(device), float(cond_scale), with_text, inject_noise, sample_offset,
                self.dynamic_thresholding[idx], self.dynamic_thresholding_percentile, tuple(hp), frames, prompt_frames, R, self._lane)
         tables = []
 
@@ -163,7 +164,7 @@ class ElucidatedImagen(Imagen):
 
         # (the time table of an image stage has this sampler's 2T evaluation rows: both denoiser evaluations of a step read it)
         st, built = self._new_stage(key, idx, B, device, cfg=cfg, with_text=with_text, inject_noise=inject_noise, sample_offset=sample_offset,
-                                    resample_times=R, frames=frames, prompt_frames=prompt_frames, coef=coef)
+                                    resample_times=R, frames=frames, prompt_frames=prompt_frames, coef=coef, size=size)
         if not built:
             return st
         eng, n, dev, step_ptr, seed_dev, step_plan, noise, final = (st['eng'], st['n'], device, st['step_ptr'], st['seed_dev'], st['step_plan'],
@@ -336,6 +337,7 @@ class ElucidatedImagen(Imagen):
         negative_texts: Optional[List[str]] = None,   # a second prompt on the null rows of guidance, as on Imagen.sample
         negative_text_embeds=None,
         negative_text_masks=None,
+        image_shapes=None,                            # one (H, W) per unet for this call, as on Imagen.sample
     ):
         return self._sample(self._call(**{k: v for k, v in locals().items() if k != 'self'}))   # (the keywords, as given)
 

@@ -1,5 +1,5 @@
 """UnetEngine — the host-side planner that turns a drop-in `Unet` (parameters only) into a static list of
-HIP kernel launches for a fixed (rows, image_size): the MI355X replacement of `Unet.forward`
+HIP kernel launches for a fixed (rows, image size — S x S, or H x W): the MI355X replacement of `Unet.forward`
 (ip.py:1524-1725).  Three plans are built:
 
   * static plan   — everything that does not change over the T timesteps of a sample() call: text projection,
@@ -244,8 +244,12 @@ class LinearSite(AttnSite):
 
 
 class UnetEngine:
-    def __init__(self, unet, rows: int, src_batch: int, size: int, device, with_text: bool = True, dry: bool = False):
+    def __init__(self, unet, rows: int, src_batch: int, size, device, with_text: bool = True, dry: bool = False):
+        """size: S (square, S x S) or (H, W); every map size of the traversal derives from the (H, W) of the level above it."""
         assert rows % src_batch == 0
+        self.HW = (int(size), int(size)) if isinstance(size, int) else tuple(int(v) for v in size)
+        assert len(self.HW) == 2 and min(self.HW) > 0, f"image size {size!r}: an int or (H, W)"
+        size = self.HW[0] if self.HW[0] == self.HW[1] else self.HW      # (S stays the int of a square engine: the video planner's only form)
         self.unet, self.R, self.S, self.dev, self.dry = unet, rows, size, torch.device(device), dry
         self.src_batch = src_batch
         self.fp = _fingerprint(unet)
@@ -289,9 +293,9 @@ class UnetEngine:
         return (torch.zeros if zero else torch.empty)(*shape, dtype=torch.float32, device=self.dev)
 
     def _alloc_io(self):
-        R, S, u = self.R, self.S, self.unet
-        self.x_in = self.f32buf(self.src_batch, u.channels, S, S, zero=True)      # fp32 NCHW staging (or the sampler's state)
-        self.lowres_in = self.f32buf(self.src_batch, u.channels, S, S, zero=True) if self.lowres else None
+        R, (H, Wd), u = self.R, self.HW, self.unet
+        self.x_in = self.f32buf(self.src_batch, u.channels, H, Wd, zero=True)      # fp32 NCHW staging (or the sampler's state)
+        self.lowres_in = self.f32buf(self.src_batch, u.channels, H, Wd, zero=True) if self.lowres else None
         # Extra init-conv inputs, read by the init conv as a second (channel-concatenated) fp16 NHWC tensor `cimg` = [self_cond | cond image]:
         #  * the conditioning image (Unet(cond_images_channels=...), ip.py:1555-1560): fp32 NCHW staging, packed once per
         #    set_cond_images() — it does not change over the timesteps;
@@ -299,14 +303,14 @@ class UnetEngine:
         #    packed at the start of every step from `self_cond_in`, or from the sampler's buffer once bind_self_cond() has been called.
         cc = getattr(u, 'cond_images_channels', 0)
         sc = u.channels if getattr(u, 'self_cond', False) else 0
-        self.cond_in = self.f32buf(self.src_batch, cc, S, S, zero=True) if cc else None
-        self.self_cond_in = self.f32buf(self.src_batch, sc, S, S, zero=True) if sc else None
-        self.cimg = self.new(R, S, S, (sc + cc + 7) // 8 * 8, zero=True) if sc + cc else None
+        self.cond_in = self.f32buf(self.src_batch, cc, H, Wd, zero=True) if cc else None
+        self.self_cond_in = self.f32buf(self.src_batch, sc, H, Wd, zero=True) if sc else None
+        self.cimg = self.new(R, H, Wd, (sc + cc + 7) // 8 * 8, zero=True) if sc + cc else None
         self._cond_pack = None
         self._self_cond_op = None
         self.times = self.f32buf(R, zero=True)          # log-SNR per row (plain forward mode)
         self.lowres_times = self.f32buf(R, zero=True)
-        self.out = self.f32buf(R, u.channels_out, S, S)
+        self.out = self.f32buf(R, u.channels_out, H, Wd)
         self.coef = None
         self.step_ptr = None
         # per-row conditioning produced by the static plan, consumed by the step plan
@@ -405,13 +409,13 @@ class UnetEngine:
                         W.get("timemlp.ish", lambda: ish.to(self.dev)), self.pa2, self.ps2)
 
     def _build_step_plan(self) -> Plan:
-        u, R, S, W = self.unet, self.R, self.S, self.W
+        u, R, (H, Wd), W = self.unet, self.R, self.HW, self.W
         plan = Plan("unet-step")
         self._plan = plan
         # ---- input image (+ low-res conditioning image) -> fp16 NHWC, 8 channels
         cin = u.channels * (2 if self.lowres else 1)
         assert cin <= 8, "init conv packs the input image into 8 channels"
-        self.img = self.new(R, S, S, 8)
+        self.img = self.new(R, H, Wd, 8)
         self._pack_op = ops.pack_image(plan, self.x_in, self.lowres_in, self.img, brep=R // self.src_batch, label="pack_image")
         if self.self_cond_in is not None:
             self._self_cond_op = ops.pack_image(plan, self.self_cond_in, self.cond_in, self.cimg, brep=R // self.src_batch, label="pack_self_cond")
@@ -425,7 +429,7 @@ class UnetEngine:
         self._time_chain_ops = [st for _, st, label in plan.ops[chain_begin:] if label in self._TIME_CHAIN]
 
         # ---- U-net traversal
-        x = self.new(R, S, S, self.lc["init_dim"])
+        x = self.new(R, H, Wd, self.lc["init_dim"])
         self._init_conv(plan, x)
         self.taps['init_conv'] = x
         init_res = x if u.init_conv_to_final_conv_residual else None      # ip.py:1568-1569 (buffers are never overwritten: no clone)
@@ -583,32 +587,32 @@ class UnetEngine:
         writing its channel slice of the concatenated tensor directly.  A non-default flag: nothing here is tuned."""
         u, R = self.unet, self.R
         comb = u.upsample_combiner
-        S, dim = x.H, x.C
+        H, Wd, dim = x.H, x.W, x.C
         douts = [blk.project.weight.shape[0] for blk in comb.fmap_convs]
         Ctot = dim + sum(douts)
         assert Ctot == comb.dim_out and dim % 8 == 0 and all(d % 8 == 0 for d in douts), "combiner slices must be 8-channel aligned"
-        cat = self.new(R, S, S, Ctot)
-        ops.rows_copy(plan, x.t, cat.t, B=1, rows=R * S * S, C=dim, src_bs=0, src_rs=x.ld, dst_bs=0, dst_rs=Ctot, src_off=x.off,
+        cat = self.new(R, H, Wd, Ctot)
+        ops.rows_copy(plan, x.t, cat.t, B=1, rows=R * H * Wd, C=dim, src_bs=0, src_rs=x.ld, dst_bs=0, dst_rs=Ctot, src_off=x.off,
                       label="upsample_combiner.x")
         off = dim
         for i, (f_act, blk, dout) in enumerate(zip(fmaps, comb.fmap_convs, douts)):
             name = f"upsample_combiner.fmap_convs.{i}"
             C = f_act.C
             assert f_act.ld == C and C % 8 == 0
-            if f_act.H != S:
-                assert S % f_act.H == 0 and f_act.H == f_act.W, "nearest resize by an integer factor only"
-                f, h = S // f_act.H, f_act.H
-                up = self.new(R, S, S, C)
-                for dy in range(f):
+            if (f_act.H, f_act.W) != (H, Wd):
+                f, h, w = H // f_act.H, f_act.H, f_act.W
+                assert (h * f, w * f) == (H, Wd), "nearest resize by one integer factor on both axes only"
+                up = self.new(R, H, Wd, C)
+                for dy in range(f):     # (a "batch" of the copy is one input row of w pixels; its output row is f * Wd pixels further on)
                     for dx in range(f):
-                        ops.rows_copy(plan, f_act.t, up.t, B=R * h, rows=h, C=C, src_bs=h * C, src_rs=C, dst_bs=f * S * C, dst_rs=f * C,
-                                      src_off=f_act.off, dst_off=(dy * S + dx) * C, label=f"{name}.resize")
+                        ops.rows_copy(plan, f_act.t, up.t, B=R * h, rows=w, C=C, src_bs=w * C, src_rs=C, dst_bs=f * Wd * C, dst_rs=f * C,
+                                      src_off=f_act.off, dst_off=(dy * Wd + dx) * C, label=f"{name}.resize")
             else:
                 up = f_act
             ssq = self._ssq_of(plan, up, name + ".stat")
             w = self.W.conv(name, blk.project)
             pa = self.W.f32(name + ".pa", lambda blk=blk, C=C, w=w: _pad_vec(blk.norm.gamma.detach().float().flatten().cpu() * math.sqrt(C), w.Cin_pad))
-            dst = Act(cat.t, R, S, S, dout, Ctot, S * S * Ctot, off)
+            dst = Act(cat.t, R, H, Wd, dout, Ctot, H * Wd * Ctot, off)
             ops.igemm(plan, up, w, dst, ssq_a=ssq, pa=pa, pstride=0, act_in=ACT_SILU, label=name)
             off += dout
         return cat
@@ -1439,7 +1443,7 @@ class UnetEngine:
         assert cond_images.shape[0] == self.src_batch, f'cond_images batch {cond_images.shape[0]} != {self.src_batch}'
         ci = cond_images.to(self.dev).float()
         if ci.shape[-2:] != self.cond_in.shape[-2:]:
-            ci = torch.nn.functional.interpolate(ci, self.cond_in.shape[-1], mode=getattr(self.unet, 'resize_mode', 'nearest'))   # ip.py:1559
+            ci = torch.nn.functional.interpolate(ci, tuple(self.cond_in.shape[-2:]), mode=getattr(self.unet, 'resize_mode', 'nearest'))   # ip.py:1559
         self.cond_in.copy_(ci)
         if self._self_cond_op is not None:
             return                                   # packed together with the self-conditioning input at the start of every step

@@ -134,6 +134,7 @@ class _Call:
     negative_texts: Any = None
     negative_text_embeds: Any = None
     negative_text_masks: Any = None
+    image_shapes: Any = None                           # extension: one (H, W) per unet, overriding image_sizes for this call (image cascades)
     # not public keywords: set by sample_requests, the sample_pipelined workers and ElucidatedImagen._call
     negative_rows: Optional[torch.Tensor] = None       # bool [rows]: the samples the merged negative prompt applies to
     pipelined_stage: bool = False                      # one stage of a cascade whose guidance scales sample_pipelined has checked as a whole
@@ -143,6 +144,7 @@ class _Call:
     neg_embeds: Any = None                             # ... resolved and checked (_check_negative)
     neg_masks: Any = None
     neg_rows: Any = None
+    sizes: Any = None                                  # per unet: image_sizes[i] (int, square), or (H, W) where image_shapes says H != W
     frames: int = 0                                    # video_frames of a video cascade, else 0
     known: Any = None                                  # inpainting: the normalised known image / clip (reference layout) and its mask
     known_mask: Any = None
@@ -489,7 +491,7 @@ class Imagen(nn.Module):
             return st
 
     def _new_stage(self, key: tuple, idx: int, B: int, device, *, cfg: bool, with_text: bool, inject_noise: bool, sample_offset: int,
-                   resample_times: int, frames: int, prompt_frames: tuple, coef: Callable):
+                   resample_times: int, frames: int, prompt_frames: tuple, coef: Callable, size=None):
         """What both samplers' `_build_stage` do first.  Returns (the cached stage of `key`, False) while its engine is not stale; else
         (a new stage dict, True): the engine (image or video), the device step counter and seed words, the engine bound to `coef()` — the
         sampler's per-evaluation table, built only now — the per-request time table where it applies, and the buffers every sampler has.
@@ -497,7 +499,7 @@ class Imagen(nn.Module):
         st = self._stages.get(key)
         if st is not None and not st['eng'].stale():
             return st, False
-        unet, S, R = self.unets[idx], self.image_sizes[idx], resample_times
+        unet, S, R = self.unets[idx], self.image_sizes[idx] if size is None else size, resample_times
         rows = 2 * B if cfg else B
         video = isinstance(unet, Unet3D)
         if video:
@@ -530,8 +532,8 @@ class Imagen(nn.Module):
                     noise_renoise=zeros() if R and inject_noise else None), True
 
     def _build_stage(self, idx: int, B: int, device, *, cond_scale: float, with_text: bool, inject_noise: bool, sample_offset: int,
-                     resample_times: int = 0, frames: int = 0, prompt_frames: tuple = (0, 0)):
-        """Build (or fetch) the per-timestep plan + graph of stage `idx` for batch B.
+                     resample_times: int = 0, frames: int = 0, prompt_frames: tuple = (0, 0), size=None):
+        """Build (or fetch) the per-timestep plan + graph of stage `idx` for batch B, at image_sizes[idx] or at `size` (an int, or (H, W)).
 
         resample_times = R > 0 selects the inpainting plan (ip.py:2237-2275): the device counter then counts INNER iterations
         (timestep i, resample r = R-1..0), every coefficient table has one row per inner iteration, and one launch sequence
@@ -541,7 +543,8 @@ class Imagen(nn.Module):
         sched = self.noise_schedulers[idx]
         T, R = sched.num_timesteps, resample_times
         cfg = cond_scale != 1.
-        key = (idx, B, self.image_sizes[idx], str(device), float(cond_scale), with_text, inject_noise, sample_offset, self.dynamic_thresholding[idx],
+        size = self.image_sizes[idx] if size is None else size
+        key = (idx, B, size, str(device), float(cond_scale), with_text, inject_noise, sample_offset, self.dynamic_thresholding[idx],
                self.pred_objectives[idx], self.dynamic_thresholding_percentile, resample_times, frames, prompt_frames, self._lane)
         tables = []
 
@@ -550,7 +553,7 @@ class Imagen(nn.Module):
             return tables[0]
 
         st, built = self._new_stage(key, idx, B, device, cfg=cfg, with_text=with_text, inject_noise=inject_noise, sample_offset=sample_offset,
-                                    resample_times=R, frames=frames, prompt_frames=prompt_frames, coef=coef)
+                                    resample_times=R, frames=frames, prompt_frames=prompt_frames, coef=coef, size=size)
         if not built:
             return st
         eng, n, coef, step_ptr, seed_dev, noise = st['eng'], st['n'], st['coef'], st['step_ptr'], st['seed_dev'], st['noise']
@@ -829,7 +832,8 @@ class Imagen(nn.Module):
         negative_texts: Optional[List[str]] = None,    # extension: a second prompt on the null rows of guidance (batch 1 or the prompts' batch):
         negative_text_embeds=None,                     #   every guided evaluation is neg + (pos - neg) * cond_scale
         negative_text_masks=None,
-    ):
+        image_shapes=None,                             # extension: one (H, W) per unet for this call instead of image_sizes (image cascades):
+    ):                                                 #   rectangular sampling; sides divisible by each unet's downsamples, stages never shrink
         return self._sample(self._call(**{k: v for k, v in locals().items() if k != 'self'}))   # (the keywords, as given)
 
     def _call(self, **kw) -> _Call:
@@ -916,7 +920,29 @@ class Imagen(nn.Module):
         return t.permute(0, 2, 1, 3, 4).contiguous() if self.is_video else t
 
     def _resize(self, im, size):
-        return im if im.shape[-1] == size else F.interpolate(im, size, mode=self.resize_mode)     # ip.py:152-168, 1924
+        """resize_image_to (ip.py:152-168, 1924) to a square `size`, or to size = (H, W)."""
+        hw = (size, size) if isinstance(size, int) else tuple(size)
+        return im if tuple(im.shape[-2:]) == hw else F.interpolate(im, hw, mode=self.resize_mode)
+
+    def _resolve_sizes(self, image_shapes) -> tuple:
+        """The size of every stage of one call: image_sizes, or the call's `image_shapes` — one (H, W) per unet, each divisible by its
+        unet's downsamples, no stage smaller than the one before it on either axis; an image cascade only.  A square entry is the int
+        of that side, so that it meets the stage (and the engine) a square call builds."""
+        if image_shapes is None:
+            return tuple(self.image_sizes)
+        if self.is_video:
+            raise ValueError('image_shapes: rectangular sampling covers image cascades; a video cascade samples square frames')
+        shapes = [tuple(int(v) for v in s) if isinstance(s, (tuple, list, torch.Size)) else s for s in image_shapes]
+        if len(shapes) != len(self.unets):
+            raise ValueError(f'image_shapes: {len(shapes)} entries for {len(self.unets)} unets (one (H, W) per unet)')
+        for i, (s, unet) in enumerate(zip(shapes, self.unets)):
+            if not (isinstance(s, tuple) and len(s) == 2):
+                raise ValueError(f'image_shapes[{i}] = {s!r}: an (H, W) pair per unet')
+            if isinstance(unet, Unet):
+                unet.check_image_size(*s, what=f'image_shapes[{i}]')
+            if i and (s[0] < shapes[i - 1][0] or s[1] < shapes[i - 1][1]):
+                raise ValueError(f'image_shapes[{i}] = {s} is smaller than image_shapes[{i - 1}] = {shapes[i - 1]}: the stages of a cascade only upsample')
+        return tuple(s[0] if s[0] == s[1] else s for s in shapes)
 
     def _resize_clip(self, v, size, f):
         """resize_video_to (iv.py:134-156) of a (b, c, f', h, w) clip to f frames of size x size — nearest over all three axes —
@@ -929,6 +955,7 @@ class Imagen(nn.Module):
         """Everything of sample() (ip.py:2291-2404) up to the stage loop, written back into the record: device, text, batch size, inpainting
         inputs, the per-unet tuples, the seed, the negative prompt with its refusals, the start image.  Builds no stage and launches nothing."""
         c.negative = self._negative_of_call(c.conditioning, c.negative_texts, c.negative_text_embeds, c.negative_text_masks, c.negative_rows)
+        c.sizes = self._resolve_sizes(c.image_shapes)
         if c.conditioning is not None:
             assert c.texts is None and c.text_embeds is None and c.text_masks is None, 'pass either `conditioning` or texts / text_embeds'
             c.text_embeds, c.text_masks = c.conditioning.text_embeds, c.conditioning.text_masks
@@ -999,11 +1026,12 @@ class Imagen(nn.Module):
             assert c.stop_at_unet_number is None or c.start_at_unet_number <= c.stop_at_unet_number
             assert c.start_image_or_video is not None, 'starting image or video must be supplied if only doing upscaling'
             img = self._to_internal(c.start_image_or_video.to(device).float()).contiguous()
-            prev_size = self.image_sizes[c.start_at_unet_number - 2]
+            prev_size = c.sizes[c.start_at_unet_number - 2]
+            prev_hw = (prev_size, prev_size) if isinstance(prev_size, int) else prev_size
             assert img.shape[-3] == self.channels, f'start image must have {self.channels} channels'
-            if img.shape[-1] != prev_size:               # ip.py:2400-2404: first to the PREVIOUS stage's size (lowres_prep then resizes to this one's)
+            if tuple(img.shape[-2:]) != prev_hw:         # ip.py:2400-2404: first to the PREVIOUS stage's size (lowres_prep then resizes to this one's)
                 lead = img.shape[:-3]
-                img = self._resize(img.reshape(-1, *img.shape[-3:]), prev_size).reshape(*lead, self.channels, prev_size, prev_size).contiguous()
+                img = self._resize(img.reshape(-1, *img.shape[-3:]), prev_size).reshape(*lead, self.channels, *prev_hw).contiguous()
             c.img = img
         return c
 
@@ -1029,7 +1057,7 @@ class Imagen(nn.Module):
         st = self._stage(idx, batch_size, device, cond_scale=cs, with_text=with_text, inject_noise=noise_fn is not None,
                          sample_offset=c.sample_offset, resample_times=c.inpaint_resample_times if c.known is not None else 0,
                          frames=c.frames // self.temporal_downsample_factor[idx] if isinstance(unet, Unet3D) else 0,
-                         prompt_frames=tuple(0 if v is None else v.shape[2] for v in prompts), **extra)
+                         prompt_frames=tuple(0 if v is None else v.shape[2] for v in prompts), size=c.sizes[idx], **extra)
         eng = st['eng']
         S = st['S']
         assert not (getattr(unet, 'has_cond_image', False) ^ (c.cond_images is not None)), \
@@ -1064,7 +1092,7 @@ class Imagen(nn.Module):
                 # a stage sampled at a lower frame rate feeds this one: nearest over the frame axis (resize_video_to,
                 # iv.py:134-156); once per stage
                 src = src[:, nearest_indices(src.shape[1], aug.shape[1]).to(src.device)]
-            if self.resize_mode != 'nearest' and src.shape[-1] != S:
+            if self.resize_mode != 'nearest' and tuple(src.shape[-2:]) != tuple(eng.lowres_in.shape[-2:]):
                 # LOWRES_PREP resizes with nearest in-kernel; any other mode is resized here, once per stage, and the kernel's
                 # own resize becomes the identity.  The resize acts on the [0, 1] image as in ip.py:2444-2446 (normalisation after).
                 src = self._resize(img, S) if self.auto_normalize_img else (self._resize(img, S) + 1) * 0.5
@@ -1121,7 +1149,7 @@ class Imagen(nn.Module):
                         dt = _time.perf_counter() - t_stage
                         self.last_stage_seconds = getattr(self, "last_stage_seconds", {})
                         self.last_stage_seconds[idx] = dt
-                        print(f"[imagen] stage {idx} ({S}x{S}, rows {st['eng'].R}): {dt * 1e3:.1f} ms for {st['T'] if c.max_steps is None else min(st['T'], c.max_steps)} steps "
+                        print(f"[imagen] stage {idx} ({'x'.join(str(v) for v in st['eng'].HW)}, rows {st['eng'].R}): {dt * 1e3:.1f} ms for {st['T'] if c.max_steps is None else min(st['T'], c.max_steps)} steps "
                               f"({len(st['plan'])} launches/step)", flush=True, file=__import__('sys').stderr)
                     c.img = out.clone()                  # internal layout (videos: frame-major), feeds the next stage's low-res conditioning
                     if not self.auto_normalize_img:

@@ -352,15 +352,25 @@ def small_cfg(Cout: int, full_cout: bool) -> Optional[int]:
     return next((i for bn, i in fam8 if bn >= Cout), None)
 
 
+SMALL_RAGGED = 1   # (module constant; tests and the A/B tools assign it) family 8 on the non-square maps of SMALL_RAGGED_MAPS (0: their previous launch)
+# the OH x OW maps (either orientation) none of family 8's tiles divides evenly in both senses and that measured faster on it, as blocks
+# with a masked edge, than on the fallback (profiles/rect_conv_small_ab.json: per launch and per step); any other map keeps the fallback
+SMALL_RAGGED_MAPS = ((8, 12), (16, 24))
+
+
 def small_tile(OH: int, OW: int) -> Optional[tuple]:
-    """The 32-pixel output tile of family 8 for an OH x OW map: 4 x 8, 2 x 16 or 1 x 32, dividing the map."""
+    """The 32-pixel output tile of family 8 for an OH x OW map: 4 x 8, 2 x 16 or 1 x 32, dividing the map; on the maps of SMALL_RAGGED_MAPS
+    the one of the three that pads the fewest pixel slots, then stages the fewest halo positions — conv_small.hip masks the part of an
+    edge block that lies outside the map in its staging (zeros) and in every epilogue (no store, no statistics, no GlobalContext weight)."""
     if OW == 8 and OH % 4 == 0:
         return 4, 8
     if OW == 16 and OH % 2 == 0:
         return 2, 16
     if OW % 32 == 0:
         return 1, 32
-    return None
+    if not SMALL_RAGGED or ((OH, OW) not in SMALL_RAGGED_MAPS and (OW, OH) not in SMALL_RAGGED_MAPS):
+        return None
+    return min(((4, 8), (2, 16), (1, 32)), key=lambda t: (math.ceil(OH / t[0]) * math.ceil(OW / t[1]), (t[0] + 2) * (t[1] + 2)))
 
 
 def small_lds_bytes(th: int, tw: int, Cin_pad: int, bn: int) -> int:
@@ -570,7 +580,7 @@ def _route_small(r: ConvReq):
           and r.cout_vec4 and (r.out_mode != OUT_PIXEL_SHUFFLE or r.Cout % 16 == 0)
           and not (r.addend is not None and (r.res is not None or not r.gate))
           and small_lds_bytes(tile[0], tile[1], r.Cin_pad, cfg_table()[sc][1]) <= MAX_LDS_BYTES
-          and (r.rows // 32) * r.Cout_pad * r.Cin_pad * 2 * r.KH * r.KW <= SMALL_MAX_STREAM_MB << 20)
+          and r.tiles(*tile) * r.Cout_pad * r.Cin_pad * 2 * r.KH * r.KW <= SMALL_MAX_STREAM_MB << 20)   # (tiles = rows / 32 where the tile divides the map)
     return (sc, tile[0], tile[1]) if ok else None
 
 

@@ -318,9 +318,28 @@ class Unet(nn.Module):
 
     # ---- execution -------------------------------------------------------------------------------------
 
-    def engine(self, batch_rows: int, src_batch: int, image_size: int, device, with_text: bool = True) -> "UnetEngine":  # noqa: F821
-        """Compiled kernel plan for `batch_rows` denoiser rows (= src_batch, or 2*src_batch with CFG) at image_size^2."""
+    @property
+    def size_divisor(self) -> int:
+        """What both sides of an image must be a multiple of: one halving per level but the last (ip.py:1359-1366), and one in front of
+        EVERY level under `memory_efficient` (ip.py:1353-1355: the last level then downsamples too, and its up level upsamples back)."""
+        n = len(self._layer_cfg["in_out"])
+        return 2 ** (n if self._layer_cfg["memory_efficient"] else n - 1)
+
+    def check_image_size(self, H: int, W: int, what: str = "image"):
+        """ValueError for an H x W the down path does not divide: a level's pixel-unshuffle would drop the odd row / column and the
+        skip connections of the up path would no longer meet maps of their own size."""
+        d = self.size_divisor
+        if H <= 0 or W <= 0 or H % d or W % d:
+            raise ValueError(f"{what} of {H} x {W}: both sides must be positive multiples of {d} (what the downsamples of this unet divide by)")
+
+    def engine(self, batch_rows: int, src_batch: int, image_size, device, with_text: bool = True) -> "UnetEngine":  # noqa: F821
+        """Compiled kernel plan for `batch_rows` denoiser rows (= src_batch, or 2*src_batch with CFG) at image_size^2, or at H x W for
+        image_size = (H, W); (S, S) is the engine of S."""
         from .engine import UnetEngine
+
+        if not isinstance(image_size, int):
+            H, W = (int(v) for v in image_size)
+            image_size = H if H == W else (H, W)
 
         device = torch.device(device)
         if device.type not in _ENGINE_DEVICE_TYPES:
@@ -372,12 +391,12 @@ class Unet(nn.Module):
         if self.training:
             raise RuntimeError("the MI355X path implements sampling (eval mode) only; call .eval() first")
         B, _, H, W = x.shape
-        assert H == W, 'square images only'
+        self.check_image_size(H, W)
         check_negative_prompt(negative_text_embeds, negative_text_mask, B,       # before an engine is built or anything is launched
                               None if text_embeds is None else text_embeds.shape[-1])
         rows = 2 * B if cfg else B
         with_text = bool(self.cond_on_text and text_embeds is not None)
-        eng = self.engine(rows, B, H, x.device, with_text=with_text)
+        eng = self.engine(rows, B, (H, W), x.device, with_text=with_text)
         if cfg:
             keep = torch.cat((torch.ones(B, dtype=torch.bool), torch.zeros(B, dtype=torch.bool)))
         elif cond_drop_prob == 0:

@@ -11,7 +11,7 @@ averaging) or noise.  (Found with the arithmetic this tool automates, round 5: t
 fp16 — 5e-5 normwise on the op, invisible beside the output rounding, 4 % of the C5 denoiser's distance to the oracle.)
 
     python tools/op_audit.py --config c5 [--frames 16 --size 64] [--null] [--emul] [--top 30] [--json out.json]
-    python tools/op_audit.py --config u1 --size 64 --null          (u2: README unet2 with its low-res conditioning, --size 256)
+    python tools/op_audit.py --config u1 --size 64 --null          (u2: README unet2 with its low-res conditioning, --size 256; --size 64 96: a rectangular plan)
 """
 from __future__ import annotations
 
@@ -81,13 +81,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", choices=("c5", "u1", "u2"), default="c5", help="BASELINE C5's Unet3D(dim 64) | README unet1 | README unet2 (lowres_cond)")
     ap.add_argument("--frames", type=int, default=16)
-    ap.add_argument("--size", type=int, default=64)
+    ap.add_argument("--size", type=int, nargs="+", default=[64], help="S, or H W (image configs: a rectangular plan)")
     ap.add_argument("--null", action="store_true", help="the unconditional row (cond_drop_prob = 1) instead of the conditional one")
     ap.add_argument("--emul", action="store_true", help="kernels on the CPU emulation (IMAGEN_LIB_PATH = the emulated library)")
     ap.add_argument("--top", type=int, default=30)
     ap.add_argument("--json", default=None)
     ap.add_argument("--threads", type=int, default=min(os.cpu_count() or 1, 32))
     args = ap.parse_args()
+    assert len(args.size) in (1, 2) and (args.config != "c5" or len(args.size) == 1), "--size S | H W (video: S)"
+    H, W = args.size[0], args.size[-1]
+    args.size = H if H == W else (H, W)
     torch.set_num_threads(args.threads)
 
     from imagen_pytorch_amd import _abi, ops
@@ -125,7 +128,7 @@ def main():
         u = Unet(**kw).eval()
         torch.nn.init.normal_(u.final_conv.weight, std=0.05)
         torch.nn.init.normal_(u.final_conv.bias, std=0.05)
-        x, t = torch.randn(1, 3, args.size, args.size), torch.tensor([0.3])
+        x, t = torch.randn(1, 3, H, W), torch.tensor([0.3])
         te = torch.randn(1, 24, 768)
         mask = torch.ones(1, 24, dtype=torch.bool)
         mask[0, 18:] = False
@@ -134,7 +137,7 @@ def main():
 
     lowres = bool(kw.get("lowres_cond"))
     lnt = torch.full((1,), 0.5) if lowres else None
-    low = torch.randn(1, 3, args.size, args.size) if lowres else None
+    low = torch.randn(1, 3, H, W) if lowres else None
     ops.KEEP_REFERENCE_WEIGHTS = True
     eng_i = make("cpu", True)
     eng_i.set_conditioning(text_embeds=te, text_mask=mask, keep=keep, lowres_noise_times=lnt)

@@ -5,6 +5,7 @@ device copy (weights and inputs as cold as inside the sampling loop).  Durations
 
     rocprofv3 --kernel-trace --output-format csv -d /tmp/sb -- python tools/small_bench.py --list /tmp/small_cases.json
     python tools/small_bench.py --parse /tmp/sb /tmp/small_cases.json        -> one JSON line per case: median us with / without, family picked
+    ... python tools/small_bench.py --rect 64 96 [--batch 2] --list L      -> the launches of README unet1 at 64x96 that take the masked-edge blocks, new tile | fallback
     IMAGEN_LIB_PATH=<a -DCS_TRACE library> python tools/small_bench.py --trace      -> s_memtime phase deltas of conv_small_kernel per case
 
 Cases: (C1, C2, Cout, H, form) at 16 rows of the CFG batch — README unet1's 8^2 / 16^2 layers, C2's 512- / 1024-channel ones, a few 32^2 ones.
@@ -92,6 +93,75 @@ def run(args):
     print(f"small_bench: {len(order)} plans x {args.reps} launches done ({os.path.basename(_abi.LIB_PATH)})", flush=True)
 
 
+def rect_plans(ops, torch, dev, H, W, batch):
+    """The distinct launches of README unet1's step plan at H x W (2 * batch rows) that family 8 takes on blocks with a masked edge, each as
+    a one-launch plan on the operands of the engine that planned it, beside the launch the planner emits for the same layer with the route
+    off: [(name, plan on, (family, tile) on, plan off, (family, tile) off)].  The planner's own bounds stay (SMALL_MAX_ROWS, the weight
+    stream): what is timed is what would switch."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from imagen_pytorch_amd import Unet, _abi
+    from imagen_pytorch_amd.engine import UnetEngine
+    from op_audit import README_U1
+
+    K = _abi.ENUMS["IMAGEN_OP_IGEMM"]
+    torch.manual_seed(0)
+    u = Unet(**README_U1).eval().to(dev)
+    maps, h, w = [], H, W
+    while h % 2 == 0 and w % 2 == 0 and h > 2:
+        maps.append((h, w))
+        h, w = h // 2, w // 2
+    engs = {}
+    keep = ops.SMALL_RAGGED, ops.SMALL_RAGGED_MAPS
+    for on in (1, 0):
+        ops.SMALL_RAGGED, ops.SMALL_RAGGED_MAPS = on, tuple(maps)
+        u.release_engines()
+        engs[on] = UnetEngine(u, 2 * batch, batch, (H, W), dev)
+    ops.SMALL_RAGGED, ops.SMALL_RAGGED_MAPS = keep
+    fam = lambda p: ops.cfg_table()[p.cfg][3]
+    seen, out = set(), []
+    for (k1, p1, l1), (k0, p0, l0) in zip(engs[1].step_plan.ops, engs[0].step_plan.ops):
+        if k1 != K or l1 != l0 or (fam(p1), p1.TH, p1.TW) == (fam(p0), p0.TH, p0.TW):
+            continue
+        sig = (p1.C1, p1.C2, p1.Cout, p1.OH, p1.OW, p1.KH, bool(p1.ssq_a), bool(p1.ps), bool(p1.post_pa), bool(p1.gca_part), bool(p1.addend), bool(p1.res),
+               bool(p1.ssq_out), p1.out_mode, fam(p0))
+        if sig in seen:
+            continue
+        seen.add(sig)
+        plans = []
+        for eng, p, l in ((engs[1], p1, l1), (engs[0], p0, l0)):
+            pl = ops.Plan(l)
+            pl.ops.append((K, p, l))
+            pl.keep.append(eng)
+            plans.append(pl)
+        name = f"{p1.C1}+{p1.C2}->{p1.Cout}@{p1.OH}x{p1.OW}k{p1.KH}:{l1}"
+        tab1, tab0 = ops.cfg_table()[p1.cfg], ops.cfg_table()[p0.cfg]
+        out.append((name, plans[0], (tab1[3], [p1.TH, p1.TW]), plans[1], (tab0[3], [p0.TH, p0.TW])))
+    return out
+
+
+def run_rect(args):
+    """--rect H W [--batch B]: every case alternates blocks of `reps` launches on the new tile and on the fallback, twice (A B A B)."""
+    import torch
+    from imagen_pytorch_amd import _abi, ops
+
+    dev = torch.device("cuda:0")
+    lib = _abi.load_library()
+    flush = flusher(torch, lib, _abi, ops, dev)
+    order = []
+    for name, pl1, t1, pl0, t0 in rect_plans(ops, torch, dev, args.rect[0], args.rect[1], args.batch):
+        for _ in range(2):
+            for small, pl, tab in ((1, pl1, t1), (0, pl0, t0)):
+                pl.run()
+                torch.cuda.synchronize()
+                for _ in range(args.reps):
+                    flush()
+                    pl.run()
+                torch.cuda.synchronize()
+                order.append(dict(case=f"b{args.batch}:{name}", small=small, family=tab[0], tile=tab[1], cfg=[], launches=args.reps + 1))
+    json.dump(dict(tag=args.tag, lib=os.path.basename(_abi.LIB_PATH), cases=order), open(args.list, "w"))
+    print(f"small_bench: {len(order)} blocks x {args.reps} launches done", flush=True)
+
+
 def trace(args):
     import ctypes
 
@@ -139,10 +209,14 @@ def parse(trace_dir, list_path):
         d = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows[i:i + c["launches"]]][1:]   # (the first launch is the warm-up)
         i += c["launches"]
         e = res.setdefault(c["case"], {})
-        e["small_us" if c["small"] else "before_us"] = round(statistics.median(d), 2) if d else None
+        e.setdefault("_small" if c["small"] else "_before", []).extend(d)      # (a case may come in several blocks: --rect alternates the sides)
         e["small_tile" if c["small"] else "before"] = (f"fam{c['family']} {c['tile'][0]}x{c['tile'][1]}")
     assert i == len(rows), (i, len(rows))
     for k, v in res.items():
+        for side, key in (("_small", "small_us"), ("_before", "before_us")):
+            d = v.pop(side, [])
+            v[key] = round(statistics.median(d), 2) if d else None
+            v[key.replace("_us", "_spread_us")] = round(max(d) - min(d), 2) if d else None
         print(json.dumps(dict(case=k, tag=meta["tag"], **v)))
 
 
@@ -152,12 +226,16 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--list", default="/tmp/small_cases.json")
     ap.add_argument("--parse", nargs=2, metavar=("TRACE_DIR", "LIST"))
+    ap.add_argument("--rect", type=int, nargs=2, metavar=("H", "W"), help="the small-map launches of README unet1's plan at H x W that switch to the masked-edge blocks, new tile | fallback")
+    ap.add_argument("--batch", type=int, default=8, help="--rect: images per request (the plan has twice as many rows)")
     ap.add_argument("--trace", action="store_true", help="phase timeline of conv_small_kernel (needs a -DCS_TRACE library)")
     args = ap.parse_args()
     if args.parse:
         parse(*args.parse)
     elif args.trace:
         trace(args)
+    elif args.rect:
+        run_rect(args)
     else:
         run(args)
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Fast A/B timer of the C3 sampling loop: ms per DDPM step of each cascade stage (graph replay, one request at a time).
 
-    python tools/step_time.py [--steps 60] [--batch 8] [--reps 3] [--tag name]
+    python tools/step_time.py [--steps 60] [--batch 8] [--reps 3] [--tag name] [--shapes 64 96 256 384]
 
 Builds the benchmark's Imagen (bench.build_imagen), warms both stages (weight packing + graph capture, 2 steps), then times `reps`
 sample() calls of `steps` DDPM steps per stage with torch.cuda events around each stage's loop (IMAGEN_TIMING prints them too).  A whole
@@ -26,11 +26,19 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--tag", default="")
+    ap.add_argument("--shapes", type=int, nargs=4, metavar=("H1", "W1", "H2", "W2"), help="rectangular stages (sample(image_shapes=...)), e.g. 64 96 256 384")
+    ap.add_argument("--ragged", type=int, default=1, help="ops.SMALL_RAGGED: family 8 on the masked-edge blocks of a rectangular plan (0: the fallback)")
     ap.add_argument("--lanes", type=int, default=0, help="also time N whole cascades side by side (one thread + stream each), `steps` DDPM steps per stage")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     imagen = bench.build_imagen(1000, dev)
+    from imagen_pytorch_amd import ops
+    ops.SMALL_RAGGED = args.ragged
     te = torch.randn(args.batch, 256, 768, generator=torch.Generator().manual_seed(1234)).to(dev)
+    if args.shapes:
+        shapes = (tuple(args.shapes[:2]), tuple(args.shapes[2:]))
+        plain = imagen.sample
+        imagen.sample = lambda **kw: plain(image_shapes=shapes, **kw)
     imagen.sample(text_embeds=te, cond_scale=3.0, use_tqdm=False, seed=1, max_steps=2)
     torch.cuda.synchronize()
     # per-stage times: sample one stage at a time through stop_at / start_at
@@ -70,7 +78,7 @@ def main():
                       "images_per_s_sequential_est": round(args.batch / (best[0] + best[1]), 4),
                       "lanes": args.lanes, "lanes_pair_ms": None if lanes_ms is None else round(lanes_ms, 4),
                       "images_per_s_lanes_est": None if lanes_ms is None else round(args.batch / lanes_ms, 4),
-                      "lib": os.path.basename(_abi.LIB_PATH), "knobs": knobs, "steps": args.steps}), flush=True)
+                      "lib": os.path.basename(_abi.LIB_PATH), "knobs": knobs, "steps": args.steps, "shapes": args.shapes, "ragged": args.ragged}), flush=True)
 
 
 if __name__ == "__main__":
