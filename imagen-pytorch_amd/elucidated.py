@@ -338,11 +338,23 @@ class ElucidatedImagen(Imagen):
         negative_text_embeds=None,
         negative_text_masks=None,
         image_shapes=None,                            # one (H, W) per unet for this call, as on Imagen.sample
+        sampler=None,                                 # Imagen.sample's solver keywords: refused here (ValueError), this class has its own sampler
+        sample_steps=None,
+        eta=None,
     ):
         return self._sample(self._call(**{k: v for k, v in locals().items() if k != 'self'}))   # (the keywords, as given)
 
+    def _solver_of(self, sampler=None, sample_steps=None, eta=None):
+        """Imagen._solver_of: the Karras et al. sampler of this class is the only one it has (num_sample_steps sets its step count)."""
+        given = [k for k, v in (('sampler', sampler), ('sample_steps', sample_steps), ('eta', eta)) if v is not None]
+        if given:
+            raise ValueError(f"{', '.join(given)}: ElucidatedImagen samples with its own second-order sampler (num_sample_steps); "
+                             f"the solver keywords belong to Imagen.sample")
+        return None
+
     def _call(self, sigma_min=None, sigma_max=None, **kw):
         """Imagen._call; this sampler's two extra keywords become the record's per-unet `sigma_overrides`, which `_build_stage` takes."""
+        self._solver_of(kw.get('sampler'), kw.get('sample_steps'), kw.get('eta'))
         n_unets = len(self.unets)
         over = None if sigma_min is None and sigma_max is None else dict(sigma_min=_cast_tuple(sigma_min, n_unets),
                                                                          sigma_max=_cast_tuple(sigma_max, n_unets))

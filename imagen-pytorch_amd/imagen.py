@@ -10,8 +10,10 @@ Implemented options: text embeddings or the T5 hook (`texts=`), classifier-free 
 skip_steps, inpainting (images and videos), cond_images, self-conditioning unets, start/stop_at_unet_number, video cascades (Unet3D
 stages) with cond_video_frames / post_cond_video_frames.  Training (`forward`, p_losses) raises.  Extensions beyond
 the reference signature: `noise_fn`,
-`seed`, `sample_offset` (batch sharding), `conditioning` handles, lanes (`with imagen.lane(i)`), `sample_pipelined` and negative prompts
-(`negative_texts` / `negative_text_embeds` / `negative_text_masks`: a second prompt on the null rows of guidance).
+`seed`, `sample_offset` (batch sharding), `conditioning` handles, lanes (`with imagen.lane(i)`), `sample_pipelined`, negative prompts
+(`negative_texts` / `negative_text_embeds` / `negative_text_masks`: a second prompt on the null rows of guidance) and few-step solvers
+(`sampler='dpmpp_2m' | 'ddim'`, `sample_steps`, `eta`: the same checkpoint in tens of steps — the ancestral update replaced by one or two
+LINCOMB launches on the tables of `schedules.solver_coefficients`).
 """
 from __future__ import annotations
 
@@ -135,6 +137,9 @@ class _Call:
     negative_text_embeds: Any = None
     negative_text_masks: Any = None
     image_shapes: Any = None                           # extension: one (H, W) per unet, overriding image_sizes for this call (image cascades)
+    sampler: Any = None                                # extension: 'ddpm' (None: the same) | 'ddim' | 'dpmpp_2m' — Imagen._solver_of
+    sample_steps: Any = None                           # ... solver steps, an int or one per unet (None: that unet's timesteps)
+    eta: Any = None                                    # ... 'ddim' only, 0 (None: the same) .. 1
     # not public keywords: set by sample_requests, the sample_pipelined workers and ElucidatedImagen._call
     negative_rows: Optional[torch.Tensor] = None       # bool [rows]: the samples the merged negative prompt applies to
     pipelined_stage: bool = False                      # one stage of a cascade whose guidance scales sample_pipelined has checked as a whole
@@ -144,6 +149,7 @@ class _Call:
     neg_embeds: Any = None                             # ... resolved and checked (_check_negative)
     neg_masks: Any = None
     neg_rows: Any = None
+    solver: Any = None                                 # None (the ancestral sampler), or per unet (sampler, steps, eta)
     sizes: Any = None                                  # per unet: image_sizes[i] (int, square), or (H, W) where image_shapes says H != W
     frames: int = 0                                    # video_frames of a video cascade, else 0
     known: Any = None                                  # inpainting: the normalised known image / clip (reference layout) and its mask
@@ -353,7 +359,13 @@ class Imagen(nn.Module):
         `max_steps=`, ...).  Requests with and without a negative prompt merge: the null rows of those without stay the learned ones.  Every row draws the noise of ITS OWN request — that
         request's Philox key and sample indices 0 .. b-1 (ABI 11: ImagenDdpmUpdateParams.row_keys) — so a request's images are the ones
         `sample(**common, **request)` produces up to the fp16 rounding of a different batch's tile configuration.  Returns one tensor per request.
-        Not covered (raise): inpainting, init images, conditioning images / frames, `noise_fn`, `start_image_or_video`."""
+        Not covered (raise): inpainting, init images, conditioning images / frames, `noise_fn`, `start_image_or_video`.  The solver keywords
+        (`sampler=`, `sample_steps=`, `eta=`) are common ones; a stochastic solver (`eta > 0`) is refused: its update (LINCOMB) draws with one
+        key per batch, and the deterministic ones draw nothing after the initial image, which carries every request's own key."""
+        solver = self._solver_of(common.get('sampler'), common.get('sample_steps'), common.get('eta'))
+        if solver is not None and solver[0][2] > 0.:
+            raise ValueError(f"sample_requests(sampler='{solver[0][0]}', eta={solver[0][2]}): merged requests take the deterministic solvers "
+                             f"(eta = 0); the stochastic update has no per-request noise keys")
         for k in ('inpaint_images', 'inpaint_videos', 'inpaint_masks', 'init_images', 'cond_images', 'cond_video_frames', 'post_cond_video_frames',
                   'noise_fn', 'start_image_or_video', 'conditioning', 'return_pil_images', 'return_all_unet_outputs', 'sample_offset'):
             if common.get(k) is not None or any(r.get(k) is not None for r in requests):
@@ -414,6 +426,7 @@ class Imagen(nn.Module):
             if kw.get('seed') is None:                   # the seed must be the same for every stage of a batch (as in one sample() call)
                 kw['seed'] = self._next_seed()
             kw.setdefault('use_tqdm', False)
+            self._solver_of(kw.get('sampler'), kw.get('sample_steps'), kw.get('eta'))   # refusals come before a thread starts
             jobs.append(kw)
         if n_stages == 1 or len(jobs) == 0:
             return [self.sample(**kw) for kw in jobs]
@@ -532,8 +545,15 @@ class Imagen(nn.Module):
                     noise_renoise=zeros() if R and inject_noise else None), True
 
     def _build_stage(self, idx: int, B: int, device, *, cond_scale: float, with_text: bool, inject_noise: bool, sample_offset: int,
-                     resample_times: int = 0, frames: int = 0, prompt_frames: tuple = (0, 0), size=None):
+                     resample_times: int = 0, frames: int = 0, prompt_frames: tuple = (0, 0), size=None, solver: Optional[tuple] = None):
         """Build (or fetch) the per-timestep plan + graph of stage `idx` for batch B, at image_sizes[idx] or at `size` (an int, or (H, W)).
+
+        solver = (sampler, steps, eta) selects a few-step solver in place of the ancestral step: the tables are those of
+        `solver_coefficients` on a grid of `steps` steps, and after CFG_X0 / QUANTILE the update is one LINCOMB launch
+        x = w0 x + w1 thr(x0) + w3 x0_prev (+ the noise term of 'ddim' at eta > 0), which also emits thr(x0) (`thr1_out`: the next step's
+        self-conditioning input and, for 'dpmpp_2m', the history) and the unnormalised image (`final_out`, rewritten every step: the last
+        one's is the stage's).  'dpmpp_2m' hands thr(x0) to `x0_prev` with a second LINCOMB used as a copy — LINCOMB forbids thr1_out
+        aliasing an input of its own launch — so that ONE captured graph serves every step.
 
         resample_times = R > 0 selects the inpainting plan (ip.py:2237-2275): the device counter then counts INNER iterations
         (timestep i, resample r = R-1..0), every coefficient table has one row per inner iteration, and one launch sequence
@@ -541,15 +561,20 @@ class Imagen(nn.Module):
         weights are the identity on the rows where the reference skips it, so a single captured graph covers the whole loop."""
         unet = self.unets[idx]
         sched = self.noise_schedulers[idx]
-        T, R = sched.num_timesteps, resample_times
+        T, R = sched.num_timesteps if solver is None else solver[1], resample_times
+        assert solver is None or not R, 'the solvers do not cover inpainting'
         cfg = cond_scale != 1.
         size = self.image_sizes[idx] if size is None else size
         key = (idx, B, size, str(device), float(cond_scale), with_text, inject_noise, sample_offset, self.dynamic_thresholding[idx],
-               self.pred_objectives[idx], self.dynamic_thresholding_percentile, resample_times, frames, prompt_frames, self._lane)
+               self.pred_objectives[idx], self.dynamic_thresholding_percentile, resample_times, frames, prompt_frames, self._lane, solver)
         tables = []
 
         def coef():
-            tables[:] = [t.to(device) for t in (sched.inpaint_coefficients(R, philox=not inject_noise) if R else (sched.step_coefficients(),))]
+            if solver is not None:
+                host = sched.solver_coefficients(*solver, philox=not inject_noise)
+            else:
+                host = sched.inpaint_coefficients(R, philox=not inject_noise) if R else (sched.step_coefficients(),)
+            tables[:] = [t.to(device) for t in host]
             return tables[0]
 
         st, built = self._new_stage(key, idx, B, device, cfg=cfg, with_text=with_text, inject_noise=inject_noise, sample_offset=sample_offset,
@@ -578,13 +603,33 @@ class Imagen(nn.Module):
         if getattr(unet, 'self_cond', False):            # ip.py:2249: each step conditions on the previous step's thresholded x0
             x0_thr = torch.zeros(B, n, device=device)    # (video: the frame-major clip, as the state)
             eng.bind_self_cond(x0_thr)
-        ops.ddpm_update(plan, eng.x_in, x0, quant if dyn else None, coef, noise, st['final'], step_ptr, B=B, n_per_sample=n,
-                        dynamic_threshold=dyn, total_steps=T * max(R, 1), seed=0, stream_id=idx, sample_offset=sample_offset,
-                        seed_ptr=seed_dev, advance=not R, x0_thr=x0_thr, row_keys=None if inject_noise else row_keys)
+        x0_prev = weights_at = None
+        if solver is not None:
+            sampler, _, eta = solver
+            two = sampler == 'dpmpp_2m'
+            if two:
+                # the history: x0_prev enters the update as t3 (already thresholded: thr(.) with no quantile is the identity on [-1, 1]),
+                # and receives this step's thr(x0) from a copy launch (weights (1, 0, ...) of row 0 of a table of its own)
+                x0_prev = torch.zeros(B, n, device=device)
+                x0_thr = torch.zeros(B, n, device=device) if x0_thr is None else x0_thr
+            ops.lincomb(plan, eng.x_in, eng.x_in, tables[1], step_ptr, B=B, n_per_sample=n, t1=x0, q1=quant if dyn else None,
+                        t2=noise if eta > 0. else None, t3=x0_prev, thr_mode=1 if dyn else 2, thr1_out=x0_thr, final=True, final_out=st['final'],
+                        advance=True, stream_id=idx, sample_offset=sample_offset, seed_ptr=seed_dev, label=f"{sampler}.update")
+            if two:
+                tables.append(torch.tensor([[1., 0., 0., 0., 0., 0., 0., 0.]], device=device))
+                zero_ptr = torch.zeros(1, dtype=torch.int32, device=device)
+                ops.lincomb(plan, x0_thr, x0_prev, tables[2], zero_ptr, B=B, n_per_sample=n, label="dpmpp_2m.history")
+                # the first step of a run has no history: its row is first order, wherever skip_steps starts the run (_run_stage)
+                weights_at = lambda start: sched.solver_coefficients(*solver, philox=not inject_noise, start=start)[1]
+        else:
+            ops.ddpm_update(plan, eng.x_in, x0, quant if dyn else None, coef, noise, st['final'], step_ptr, B=B, n_per_sample=n,
+                            dynamic_threshold=dyn, total_steps=T * max(R, 1), seed=0, stream_id=idx, sample_offset=sample_offset,
+                            seed_ptr=seed_dev, advance=not R, x0_thr=x0_thr, row_keys=None if inject_noise else row_keys)
         if R:
             ops.lincomb(plan, eng.x_in, eng.x_in, tables[2], step_ptr, B=B, n_per_sample=n, t1=st['noise_renoise'], advance=True,
                         stream_id=idx | 0x200, sample_offset=sample_offset, seed_ptr=seed_dev, label="inpaint.renoise")
-        st.update(plan=plan, T=T, row_keys=row_keys, quant=quant, x0=x0, x0_thr=x0_thr, noise_blend=noise_blend)
+        st.update(plan=plan, T=T, row_keys=row_keys, quant=quant, x0=x0, x0_thr=x0_thr, noise_blend=noise_blend, solver=solver,
+                  x0_prev=x0_prev, weights=tables[1] if solver is not None else None, weights_at=weights_at, weights_start=0)
         self._stages[key] = st
         return st
 
@@ -641,7 +686,12 @@ class Imagen(nn.Module):
                 eng.x_in.add_(init_images)              # ip.py:2205-2206
             if st['x0_thr'] is not None:
                 st['x0_thr'].zero_()                    # no x0 estimate yet: the first step self-conditions on zeros (ip.py:2210, 1542)
-            st['step_ptr'].fill_(skip * inner)           # ip.py:2228-2229: the skipped timesteps are simply never run
+            if st['x0_prev'] is not None:               # 'dpmpp_2m': no history yet, and the run's first row is first order
+                st['x0_prev'].zero_()
+                if st['weights_start'] != skip:
+                    st['weights'].copy_(st['weights_at'](skip))
+                    st['weights_start'] = skip
+            st['step_ptr'].fill_(skip * inner)          # ip.py:2228-2229: the skipped timesteps are simply never run
 
         reset_state()
         assert not (R and len(spans) > 1), 'merged requests do not cover inpainting (its re-noising launches take one key per batch)'
@@ -672,7 +722,7 @@ class Imagen(nn.Module):
                         st['noise'].copy_(draw(("step", stage, i, r), st['noise']))
                         if r > 0 and i < T - 1:          # the reference draws no re-noising sample otherwise (ip.py:2268)
                             st['noise_renoise'].copy_(draw(("renoise", stage, i, r), st['noise']))
-                    else:
+                    elif st['solver'] is None or st['solver'][2] > 0.:      # (the deterministic solvers draw nothing after the initial image)
                         st['noise'].copy_(draw(("step", stage, i), st['noise']))
                 if use_graph:
                     st['graph'].launch()
@@ -833,12 +883,46 @@ class Imagen(nn.Module):
         negative_text_embeds=None,                     #   every guided evaluation is neg + (pos - neg) * cond_scale
         negative_text_masks=None,
         image_shapes=None,                             # extension: one (H, W) per unet for this call instead of image_sizes (image cascades):
-    ):                                                 #   rectangular sampling; sides divisible by each unet's downsamples, stages never shrink
+                                                       #   rectangular sampling; sides divisible by each unet's downsamples, stages never shrink
+        sampler: str = 'ddpm',                         # extension: 'ddpm' (the reference's ancestral step, one per training timestep), or a few-step
+        sample_steps=None,                             #   solver on the same checkpoint: 'dpmpp_2m' (DPM-Solver++ 2M) | 'ddim', in `sample_steps`
+        eta: float = 0.,                               #   steps (an int or one per unet; None: the unet's timesteps); eta: 'ddim' only, 0 .. 1
+    ):
         return self._sample(self._call(**{k: v for k, v in locals().items() if k != 'self'}))   # (the keywords, as given)
 
     def _call(self, **kw) -> _Call:
         """The record of one call from sample()'s keywords (+ the private ones of _Call)."""
         return _Call(**kw)
+
+    def _solver_of(self, sampler=None, sample_steps=None, eta=None):
+        """The solver keywords of one call, checked: None for the ancestral sampler ('ddpm', the default: one step per training timestep),
+        else one (sampler, steps, eta) per unet — `sample_steps` an int or one per unet, None meaning that unet's `timesteps`.  Raises
+        ValueError for an unknown sampler, `sample_steps` / `eta` beside 'ddpm', eta outside [0, 1] or beside the deterministic
+        'dpmpp_2m', and fewer steps than the solver's order."""
+        from .schedules import SOLVERS
+
+        sampler = 'ddpm' if sampler is None else sampler
+        eta = 0. if eta is None else float(eta)
+        if sampler == 'ddpm':
+            if sample_steps is not None or eta != 0.:
+                raise ValueError("sample_steps / eta belong to the solvers (sampler='ddim' | 'dpmpp_2m'): the ancestral sampler 'ddpm' runs "
+                                 "every training timestep (Imagen(timesteps=...)) and draws its posterior noise")
+            return None
+        if sampler not in SOLVERS:
+            raise ValueError(f"unknown sampler '{sampler}': 'ddpm', {', '.join(repr(s) for s in SOLVERS)}")
+        if not 0. <= eta <= 1.:
+            raise ValueError(f'eta = {eta} is outside [0, 1]')
+        if sampler == 'dpmpp_2m' and eta != 0.:
+            raise ValueError("sampler='dpmpp_2m' is deterministic: eta must be 0 ('ddim' takes 0 <= eta <= 1)")
+        n = len(self.unets)
+        steps = tuple(sample_steps) if isinstance(sample_steps, (list, tuple)) else (sample_steps,) * n
+        if len(steps) != n:
+            raise ValueError(f'sample_steps: {len(steps)} entries for {n} unets')
+        steps = tuple(sched.num_timesteps if s is None else int(s) for s, sched in zip(steps, self.noise_schedulers))
+        least = 2 if sampler == 'dpmpp_2m' else 1
+        if min(steps) < least:
+            raise ValueError(f"sampler='{sampler}' needs sample_steps >= {least}, got {steps}")
+        return tuple((sampler, s, eta) for s in steps)
 
     def _negative_of_call(self, conditioning, negative_texts, negative_text_embeds, negative_text_masks, negative_rows=None):
         """The negative prompt of one sample() call as given — by keyword, or on the conditioning handle — for _resolve, which resolves and
@@ -955,6 +1039,12 @@ class Imagen(nn.Module):
         """Everything of sample() (ip.py:2291-2404) up to the stage loop, written back into the record: device, text, batch size, inpainting
         inputs, the per-unet tuples, the seed, the negative prompt with its refusals, the start image.  Builds no stage and launches nothing."""
         c.negative = self._negative_of_call(c.conditioning, c.negative_texts, c.negative_text_embeds, c.negative_text_masks, c.negative_rows)
+        c.solver = self._solver_of(c.sampler, c.sample_steps, c.eta)
+        if c.solver is not None and (c.inpaint_images is not None or c.inpaint_videos is not None or c.inpaint_masks is not None):
+            raise ValueError(f"sampler='{c.solver[0][0]}' with inpainting: the resample loop (ip.py:2237-2275) is defined on the ancestral step; "
+                             f"inpaint with sampler='ddpm'")
+        if c.solver is not None and c.solver[0][2] > 0. and isinstance(c.seed, (list, tuple)):
+            raise ValueError('merged requests take the deterministic solvers (eta = 0)')
         c.sizes = self._resolve_sizes(c.image_shapes)
         if c.conditioning is not None:
             assert c.texts is None and c.text_embeds is None and c.text_masks is None, 'pass either `conditioning` or texts / text_embeds'
@@ -1054,6 +1144,8 @@ class Imagen(nn.Module):
                     v = F.interpolate(v.float(), (v.shape[2] // tds, v.shape[-2], v.shape[-1]), mode='nearest')
                 prompts[k] = v
         extra = {} if c.sigma_overrides is None else dict(sigma_overrides=c.sigma_overrides)
+        if c.solver is not None:
+            extra['solver'] = c.solver[idx]
         st = self._stage(idx, batch_size, device, cond_scale=cs, with_text=with_text, inject_noise=noise_fn is not None,
                          sample_offset=c.sample_offset, resample_times=c.inpaint_resample_times if c.known is not None else 0,
                          frames=c.frames // self.temporal_downsample_factor[idx] if isinstance(unet, Unet3D) else 0,

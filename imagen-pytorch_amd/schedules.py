@@ -30,6 +30,7 @@ def log_snr_to_alpha_sigma(log_snr: torch.Tensor):
 
 
 COEF_COLS = 8  # [alpha, sigma, alpha_next, sigma_next, c, nonzero, log_snr, 0] — layout shared with csrc/sampler.hip
+SOLVERS = ('ddim', 'dpmpp_2m')   # the few-step solvers of Imagen.sample(sampler=...); 'ddpm' is the ancestral step of step_coefficients()
 
 
 class GaussianDiffusionContinuousTimes(nn.Module):
@@ -126,6 +127,56 @@ class GaussianDiffusionContinuousTimes(nn.Module):
             nonzero = 0.0 if float(t_next) == 0.0 else 1.0
             rows.append(torch.stack([alpha, sigma, alpha_n, sigma_n, c, torch.tensor(nonzero), l, torch.tensor(0.0)]))
         return torch.stack(rows).float().contiguous()
+
+    def solver_coefficients(self, sampler: str, steps: int, eta: float = 0., *, philox: bool = True, start: int = 0):
+        """Tables of the few-step solvers on the grid linspace(1, 0, steps + 1), which is independent of `num_timesteps`:
+        (step table [steps, 8] in the layout of step_coefficients() — what CFG_X0, the time embedding and the per-request time table
+        read — , weight table [steps, 8] of the LINCOMB update, indexed by the same step counter).
+
+        With l = log_snr(t), (alpha, sigma) from l, lambda = l / 2, h = lambda_next - lambda, c = -expm1(l - l_next):
+          'ddim'      x_next = alpha_n x0 + sqrt(sigma_n^2 - s^2) (x - alpha x0) / sigma + nonzero s z,  s = eta sigma_n sqrt(c), 0 <= eta <= 1
+                      (eta = 1 is the ancestral posterior of step_coefficients() on this grid, eta = 0 the deterministic DDIM step)
+          'dpmpp_2m'  x_next = (sigma_n / sigma) x - alpha_n expm1(-h) D,  D = (1 + 1/(2r)) x0 - (1/(2r)) x0_prev,  r = h_prev / h;
+                      D = x0 (first order) on row `start` — the first step of a run has no history — and on the last row.
+        x0 and x0_prev are the thresholded estimates.  Weight columns: 0 on x, 1 on thr(x0), 3 on x0_prev, and the noise weight
+        nonzero * s in column 4 (the kernel's own Philox draw) when `philox`, else in column 2 (an injected draw passed as t2).
+
+        The grid and its log-SNR are the reference's own fp32 values (get_sampling_timesteps, log_snr): they are what the denoiser is
+        conditioned on, and at t = 1 the cosine schedule is decided by the rounding of cos(pi / 2).  Everything derived from l is
+        evaluated in fp64 and stored as fp32."""
+        if sampler not in SOLVERS:
+            raise ValueError(f"unknown solver '{sampler}': one of {SOLVERS}")
+        steps, eta = int(steps), float(eta)
+        if steps < (2 if sampler == 'dpmpp_2m' else 1):
+            raise ValueError(f"'{sampler}' needs at least {2 if sampler == 'dpmpp_2m' else 1} steps, got {steps}")
+        if not 0. <= eta <= 1.:
+            raise ValueError(f'eta = {eta} is outside [0, 1]')
+        if sampler == 'dpmpp_2m' and eta != 0.:
+            raise ValueError("'dpmpp_2m' is deterministic: eta must be 0")
+        t = torch.linspace(1., 0., steps + 1)
+        l = self.log_snr(t).double()
+        alpha, sigma = log_snr_to_alpha_sigma(l)
+        a, s, a_n, s_n = alpha[:-1], sigma[:-1], alpha[1:], sigma[1:]
+        c = -torch.special.expm1(l[:-1] - l[1:])
+        nonzero = (t[1:] != 0).double()
+        zero = torch.zeros_like(a)
+        step = torch.stack([a, s, a_n, s_n, c, nonzero, l[:-1], zero], dim=1)
+        w = torch.zeros(steps, COEF_COLS, dtype=torch.float64)
+        if sampler == 'ddim':
+            # sigma_n^2 - s^2 = sigma_n^2 (1 - eta^2 c), and 1 - c = exp(l - l_next): no difference of nearly equal numbers at c -> 1
+            w[:, 0] = s_n * torch.sqrt((1. - eta * eta) + eta * eta * torch.exp(l[:-1] - l[1:])) / s
+            w[:, 1] = a_n - a * w[:, 0]
+            w[:, 4 if philox else 2] = nonzero * eta * s_n * torch.sqrt(c)
+        else:
+            h = 0.5 * (l[1:] - l[:-1])
+            g = -a_n * torch.special.expm1(-h)
+            inv_2r = torch.zeros_like(h)
+            inv_2r[1:] = h[1:] / (2. * h[:-1])
+            inv_2r[steps - 1] = 0.
+            if 0 <= start < steps:
+                inv_2r[start] = 0.
+            w[:, 0], w[:, 1], w[:, 3] = s_n / s, g * (1. + inv_2r), -g * inv_2r
+        return step.float().contiguous(), w.float().contiguous()
 
     def inpaint_coefficients(self, resample_times: int, philox: bool):
         """Tables for the inpainting resample loop (ip.py:2237-2275), one row per INNER iteration (timestep i, resample r = R-1..0):
