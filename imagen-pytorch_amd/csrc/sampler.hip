@@ -7,7 +7,7 @@
 
 namespace {
 
-// coef row layout (host-built, fp32): [alpha, sigma, alpha_next, sigma_next, c, nonzero, log_snr, 0]
+// coef row layout (host-built, fp32): [alpha, sigma, alpha_next, sigma_next, c, nonzero, log_snr, guidance scale of the step (cfg == 2) | 0]
 constexpr int kCoefStride = 8;
 
 __global__ __launch_bounds__(256) void cfg_x0_kernel(const ImagenCfgX0Params p) {
@@ -19,7 +19,8 @@ __global__ __launch_bounds__(256) void cfg_x0_kernel(const ImagenCfgX0Params p) 
   float eps;
   if (p.cfg) {
     const float cond = p.pred[i], nul = p.pred[n + i];
-    eps = nul + (cond - nul) * p.cond_scale;  // ip.py:1522
+    const float s = p.cfg == 2 ? cf[7] : p.cond_scale;  // cfg == 2: the step's own scale (a guidance schedule), same arithmetic
+    eps = nul + (cond - nul) * s;  // ip.py:1522
   } else {
     eps = p.pred[i];
   }
@@ -308,6 +309,7 @@ int launch_lincomb(const ImagenLincombParams* p, hipStream_t s) {
 
 int launch_cfg_x0(const ImagenCfgX0Params* p, hipStream_t s) {
   IMAGEN_CHECK(p->step_ptr && p->coef, "cfg_x0: coef table / step counter required");
+  IMAGEN_CHECK(p->cfg >= 0 && p->cfg <= 2, "cfg_x0: cfg is 0 (unguided), 1 (cond_scale) or 2 (the scale of the step's table row)");
   const size_t n = (size_t)p->B * p->n_per_sample;
   hipLaunchKernelGGL(cfg_x0_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, *p);
   return imagen_hip_status("cfg_x0");

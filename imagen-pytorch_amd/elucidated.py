@@ -341,6 +341,8 @@ class ElucidatedImagen(Imagen):
         sampler=None,                                 # Imagen.sample's solver keywords: refused here (ValueError), this class has its own sampler
         sample_steps=None,
         eta=None,
+        guidance_schedule=None,                       # Imagen.sample's guidance keywords: refused here (ValueError)
+        guidance_interval=None,
     ):
         return self._sample(self._call(**{k: v for k, v in locals().items() if k != 'self'}))   # (the keywords, as given)
 
@@ -352,9 +354,19 @@ class ElucidatedImagen(Imagen):
                              f"the solver keywords belong to Imagen.sample")
         return None
 
+    def _guidance_of(self, guidance_schedule=None, guidance_interval=None):
+        """Imagen._guidance_of: refused.  A Heun step evaluates the denoiser twice per table row, so a per-row scale and a per-step choice
+        of plan are not what Imagen's are; this sampler guides with the fixed cond_scale."""
+        given = [k for k, v in (('guidance_schedule', guidance_schedule), ('guidance_interval', guidance_interval)) if v is not None]
+        if given:
+            raise ValueError(f"{', '.join(given)}: ElucidatedImagen evaluates the denoiser twice per step of its second-order sampler; "
+                             f"guidance schedules and intervals belong to Imagen.sample")
+        return None
+
     def _call(self, sigma_min=None, sigma_max=None, **kw):
         """Imagen._call; this sampler's two extra keywords become the record's per-unet `sigma_overrides`, which `_build_stage` takes."""
         self._solver_of(kw.get('sampler'), kw.get('sample_steps'), kw.get('eta'))
+        self._guidance_of(kw.get('guidance_schedule'), kw.get('guidance_interval'))
         n_unets = len(self.unets)
         over = None if sigma_min is None and sigma_max is None else dict(sigma_min=_cast_tuple(sigma_min, n_unets),
                                                                          sigma_max=_cast_tuple(sigma_max, n_unets))

@@ -1434,6 +1434,18 @@ class UnetEngine:
         p.times, p.coef, p.step_ptr = None, coef.data_ptr(), step_ptr.data_ptr()
         self.coef, self.step_ptr = coef, step_ptr
 
+    def share_sampler_state(self, other: "UnetEngine"):
+        """Sampler mode: this engine reads the sampler state of `other` — `x_in` and the low-res conditioning image — in place of its own
+        staging buffers.  `other` is an engine of the same unet, size and source batch with another number of rows (Imagen's guidance
+        schedules: the B-row plan of the unguided steps beside the 2B-row plan of the guided ones, one state).  To be called before
+        enable_time_table(), which copies the step plan."""
+        assert other.unet is self.unet and other.x_in.shape == self.x_in.shape and other.lowres == self.lowres and self._tt_plan is None
+        self.x_in, self._pack_op.a = other.x_in, other.x_in.data_ptr()
+        self.step_plan.keep.append(other.x_in)
+        if self.lowres:
+            self.lowres_in, self._pack_op.b = other.lowres_in, other.lowres_in.data_ptr()
+            self.step_plan.keep.append(other.lowres_in)
+
     def set_cond_images(self, cond_images: torch.Tensor):
         """The conditioning image of the following forward / sampling calls: (src_batch, cond_images_channels, h, w), values as given
         (the reference does not normalise it); nearest-resized to this engine's resolution (ip.py:1558-1559) and packed to fp16 NHWC."""

@@ -140,6 +140,8 @@ class _Call:
     sampler: Any = None                                # extension: 'ddpm' (None: the same) | 'ddim' | 'dpmpp_2m' — Imagen._solver_of
     sample_steps: Any = None                           # ... solver steps, an int or one per unet (None: that unet's timesteps)
     eta: Any = None                                    # ... 'ddim' only, 0 (None: the same) .. 1
+    guidance_schedule: Any = None                      # extension: the guidance scale per step, a callable f(t) | a sequence, one or per unet
+    guidance_interval: Any = None                      # ... (t_lo, t_hi), one or per unet: the steps outside it run unguided — Imagen._guidance_of
     # not public keywords: set by sample_requests, the sample_pipelined workers and ElucidatedImagen._call
     negative_rows: Optional[torch.Tensor] = None       # bool [rows]: the samples the merged negative prompt applies to
     pipelined_stage: bool = False                      # one stage of a cascade whose guidance scales sample_pipelined has checked as a whole
@@ -150,6 +152,7 @@ class _Call:
     neg_masks: Any = None
     neg_rows: Any = None
     solver: Any = None                                 # None (the ancestral sampler), or per unet (sampler, steps, eta)
+    guidance: Any = None                               # per unet: None (cond_scale as it stands) | the fp32 [steps] scales of a schedule that varies
     sizes: Any = None                                  # per unet: image_sizes[i] (int, square), or (H, W) where image_shapes says H != W
     frames: int = 0                                    # video_frames of a video cascade, else 0
     known: Any = None                                  # inpainting: the normalised known image / clip (reference layout) and its mask
@@ -361,8 +364,13 @@ class Imagen(nn.Module):
         `sample(**common, **request)` produces up to the fp16 rounding of a different batch's tile configuration.  Returns one tensor per request.
         Not covered (raise): inpainting, init images, conditioning images / frames, `noise_fn`, `start_image_or_video`.  The solver keywords
         (`sampler=`, `sample_steps=`, `eta=`) are common ones; a stochastic solver (`eta > 0`) is refused: its update (LINCOMB) draws with one
-        key per batch, and the deterministic ones draw nothing after the initial image, which carries every request's own key."""
+        key per batch, and the deterministic ones draw nothing after the initial image, which carries every request's own key.  The guidance
+        keywords (`guidance_schedule=`, `guidance_interval=`) are common ones too, as `cond_scale=` is: inside a request they are refused."""
         solver = self._solver_of(common.get('sampler'), common.get('sample_steps'), common.get('eta'))
+        self._guidance_of(common.get('guidance_schedule'), common.get('guidance_interval'))
+        for k in ('guidance_schedule', 'guidance_interval'):
+            if any(k in r for r in requests):
+                raise ValueError(f'sample_requests: {k} inside a request; merged requests run one plan, so it is a common keyword, as cond_scale is')
         if solver is not None and solver[0][2] > 0.:
             raise ValueError(f"sample_requests(sampler='{solver[0][0]}', eta={solver[0][2]}): merged requests take the deterministic solvers "
                              f"(eta = 0); the stochastic update has no per-request noise keys")
@@ -426,7 +434,10 @@ class Imagen(nn.Module):
             if kw.get('seed') is None:                   # the seed must be the same for every stage of a batch (as in one sample() call)
                 kw['seed'] = self._next_seed()
             kw.setdefault('use_tqdm', False)
-            self._solver_of(kw.get('sampler'), kw.get('sample_steps'), kw.get('eta'))   # refusals come before a thread starts
+            solver = self._solver_of(kw.get('sampler'), kw.get('sample_steps'), kw.get('eta'))   # refusals come before a thread starts
+            self._guidance_vectors(self._guidance_of(kw.get('guidance_schedule'), kw.get('guidance_interval')),
+                                   _cast_tuple(kw.get('cond_scale', 1.), n_stages), solver,
+                                   any(kw.get(k) is not None for k in ('inpaint_images', 'inpaint_videos', 'inpaint_masks')), 0, n_stages)
             jobs.append(kw)
         if n_stages == 1 or len(jobs) == 0:
             return [self.sample(**kw) for kw in jobs]
@@ -504,11 +515,13 @@ class Imagen(nn.Module):
             return st
 
     def _new_stage(self, key: tuple, idx: int, B: int, device, *, cfg: bool, with_text: bool, inject_noise: bool, sample_offset: int,
-                   resample_times: int, frames: int, prompt_frames: tuple, coef: Callable, size=None):
+                   resample_times: int, frames: int, prompt_frames: tuple, coef: Callable, size=None, share: Optional[dict] = None):
         """What both samplers' `_build_stage` do first.  Returns (the cached stage of `key`, False) while its engine is not stale; else
         (a new stage dict, True): the engine (image or video), the device step counter and seed words, the engine bound to `coef()` — the
         sampler's per-evaluation table, built only now — the per-request time table where it applies, and the buffers every sampler has.
-        EVERY key the run side reads is present (None where unused); the sampler adds its plan(s), tables and buffers and files the stage."""
+        EVERY key the run side reads is present (None where unused); the sampler adds its plan(s), tables and buffers and files the stage.
+        share: the stage whose sampler state this one runs on (the unguided sibling of a stage with a guidance schedule): its engine reads
+        that stage's `x_in` / low-res image, and the step counter, seed words, noise and output buffers are that stage's."""
         st = self._stages.get(key)
         if st is not None and not st['eng'].stale():
             return st, False
@@ -526,8 +539,12 @@ class Imagen(nn.Module):
         else:
             from . import engine
             eng = engine.UnetEngine(unet, rows, B, S, device, with_text=with_text)
-        step_ptr = torch.zeros(1, dtype=torch.int32, device=device)
-        seed_dev = torch.zeros(2, dtype=torch.int32, device=device)
+        if share is not None:
+            eng.share_sampler_state(share['eng'])
+            step_ptr, seed_dev = share['step_ptr'], share['seed_dev']
+        else:
+            step_ptr = torch.zeros(1, dtype=torch.int32, device=device)
+            seed_dev = torch.zeros(2, dtype=torch.int32, device=device)
         coef = coef()
         eng.bind_step_counter(coef, step_ptr)
         # image stages without inpainting resampling: the timestep-only conditioning chain of the denoiser is evaluated for all steps at
@@ -537,15 +554,24 @@ class Imagen(nn.Module):
         if TIME_TABLE and not R:
             step_plan = eng.enable_time_table(coef, step_ptr) or step_plan
         zeros = lambda: torch.zeros_like(eng.x_in)
+        if share is not None:
+            assert not R, 'a shared sampler state does not cover the inpainting plan'
+            noise, final = share['noise'], share['final']
+        else:
+            noise, final = torch.empty_like(eng.x_in) if inject_noise else None, torch.empty_like(eng.x_in)
+        # (key / tables / scales / sibling: the cache key, the sampler's device tables, and — Imagen's guidance schedules — the per-step scales
+        # and the unguided sibling stage; None for every stage without a schedule, under both samplers)
         return dict(eng=eng, step_plan=step_plan, plan=None, graph=None, coef=coef, step_ptr=step_ptr, seed_dev=seed_dev,
+                    key=key, tables=None, scales=None, sibling=None,
                     n=eng.x_in[0].numel(), S=S, R=R, video=video, frames=frames, sample_offset=sample_offset,
-                    noise=torch.empty_like(eng.x_in) if inject_noise else None, final=torch.empty_like(eng.x_in),
+                    noise=noise, final=final,
                     # inpainting: the known image (video: frame-major clip), normalised, at this stage's size; 1.0 where it is kept
                     known=zeros() if R else None, mask=zeros() if R else None,
                     noise_renoise=zeros() if R and inject_noise else None), True
 
     def _build_stage(self, idx: int, B: int, device, *, cond_scale: float, with_text: bool, inject_noise: bool, sample_offset: int,
-                     resample_times: int = 0, frames: int = 0, prompt_frames: tuple = (0, 0), size=None, solver: Optional[tuple] = None):
+                     resample_times: int = 0, frames: int = 0, prompt_frames: tuple = (0, 0), size=None, solver: Optional[tuple] = None,
+                     guidance: Optional[torch.Tensor] = None, share: Optional[dict] = None):
         """Build (or fetch) the per-timestep plan + graph of stage `idx` for batch B, at image_sizes[idx] or at `size` (an int, or (H, W)).
 
         solver = (sampler, steps, eta) selects a few-step solver in place of the ancestral step: the tables are those of
@@ -558,31 +584,49 @@ class Imagen(nn.Module):
         resample_times = R > 0 selects the inpainting plan (ip.py:2237-2275): the device counter then counts INNER iterations
         (timestep i, resample r = R-1..0), every coefficient table has one row per inner iteration, and one launch sequence
         [blend known pixels at level t -> denoiser -> posterior step -> re-noise t_next -> t] serves all of them: the re-noising
-        weights are the identity on the rows where the reference skips it, so a single captured graph covers the whole loop."""
+        weights are the identity on the rows where the reference skips it, so a single captured graph covers the whole loop.
+
+        guidance = the fp32 [T] guidance scales of a schedule that varies (Imagen._resolve_guidance): the stage is the
+        guided one (2B rows) with CFG_X0 at cfg = 2, which reads the step's scale from column 7 of the step table; `cond_scale` is not
+        used.  Where the schedule has steps at exactly 1 — outside a guidance interval — st['sibling'] is the stage `cond_scale = 1`
+        builds (B rows, cfg = 0), built here with share = this stage: it runs on this stage's sampler state (x, step counter, tables,
+        seed words, self-conditioning / history / noise / output buffers) and `_run_stage` replays it on those steps."""
         unet = self.unets[idx]
         sched = self.noise_schedulers[idx]
         T, R = sched.num_timesteps if solver is None else solver[1], resample_times
         assert solver is None or not R, 'the solvers do not cover inpainting'
-        cfg = cond_scale != 1.
+        assert guidance is None or (share is None and not R and tuple(guidance.shape) == (T,) and guidance.dtype == torch.float32)
+        assert share is None or (cond_scale == 1. and not R)
+        cfg = 2 if guidance is not None else int(cond_scale != 1.)
         size = self.image_sizes[idx] if size is None else size
         key = (idx, B, size, str(device), float(cond_scale), with_text, inject_noise, sample_offset, self.dynamic_thresholding[idx],
                self.pred_objectives[idx], self.dynamic_thresholding_percentile, resample_times, frames, prompt_frames, self._lane, solver)
+        if guidance is not None:                         # (a call without a schedule keeps the key it always had)
+            key += (('guidance', guidance.numpy().tobytes()),)
+        if share is not None:
+            key += (('shares', share['key']),)
         tables = []
 
         def coef():
+            if share is not None:                        # the tables of the stage whose state this one runs on, the very tensors
+                tables[:] = share['tables']
+                return tables[0]
             if solver is not None:
                 host = sched.solver_coefficients(*solver, philox=not inject_noise)
             else:
                 host = sched.inpaint_coefficients(R, philox=not inject_noise) if R else (sched.step_coefficients(),)
+            if guidance is not None:
+                host[0][:, 7] = guidance                 # column 7, the pad slot of the step table: read by CFG_X0 (cfg = 2) alone
             tables[:] = [t.to(device) for t in host]
             return tables[0]
 
-        st, built = self._new_stage(key, idx, B, device, cfg=cfg, with_text=with_text, inject_noise=inject_noise, sample_offset=sample_offset,
-                                    resample_times=R, frames=frames, prompt_frames=prompt_frames, coef=coef, size=size)
+        st, built = self._new_stage(key, idx, B, device, cfg=bool(cfg), with_text=with_text, inject_noise=inject_noise, sample_offset=sample_offset,
+                                    resample_times=R, frames=frames, prompt_frames=prompt_frames, coef=coef, size=size, share=share)
         if not built:
             return st
         eng, n, coef, step_ptr, seed_dev, noise = st['eng'], st['n'], st['coef'], st['step_ptr'], st['seed_dev'], st['noise']
-        row_keys = torch.zeros(B, 4, dtype=torch.int32, device=device)   # (Philox key lo, hi, global sample index, 0) of every row: _run_stage fills it per call
+        # (Philox key lo, hi, global sample index, 0) of every row: _run_stage fills it per call
+        row_keys = torch.zeros(B, 4, dtype=torch.int32, device=device) if share is None else share['row_keys']
         x0 = torch.empty(B, n, device=device)
         absx0 = torch.empty(B, n, device=device)
         quant = torch.empty(B, device=device)
@@ -601,7 +645,7 @@ class Imagen(nn.Module):
             ops.quantile(plan, absx0, quant, scratch, B=B, n=n, q=float(self.dynamic_thresholding_percentile))
         x0_thr = None
         if getattr(unet, 'self_cond', False):            # ip.py:2249: each step conditions on the previous step's thresholded x0
-            x0_thr = torch.zeros(B, n, device=device)    # (video: the frame-major clip, as the state)
+            x0_thr = torch.zeros(B, n, device=device) if share is None else share['x0_thr']    # (video: the frame-major clip, as the state)
             eng.bind_self_cond(x0_thr)
         x0_prev = weights_at = None
         if solver is not None:
@@ -610,13 +654,14 @@ class Imagen(nn.Module):
             if two:
                 # the history: x0_prev enters the update as t3 (already thresholded: thr(.) with no quantile is the identity on [-1, 1]),
                 # and receives this step's thr(x0) from a copy launch (weights (1, 0, ...) of row 0 of a table of its own)
-                x0_prev = torch.zeros(B, n, device=device)
-                x0_thr = torch.zeros(B, n, device=device) if x0_thr is None else x0_thr
+                x0_prev = torch.zeros(B, n, device=device) if share is None else share['x0_prev']
+                x0_thr = x0_thr if x0_thr is not None else torch.zeros(B, n, device=device) if share is None else share['x0_thr']
             ops.lincomb(plan, eng.x_in, eng.x_in, tables[1], step_ptr, B=B, n_per_sample=n, t1=x0, q1=quant if dyn else None,
                         t2=noise if eta > 0. else None, t3=x0_prev, thr_mode=1 if dyn else 2, thr1_out=x0_thr, final=True, final_out=st['final'],
                         advance=True, stream_id=idx, sample_offset=sample_offset, seed_ptr=seed_dev, label=f"{sampler}.update")
             if two:
-                tables.append(torch.tensor([[1., 0., 0., 0., 0., 0., 0., 0.]], device=device))
+                if share is None:
+                    tables.append(torch.tensor([[1., 0., 0., 0., 0., 0., 0., 0.]], device=device))
                 zero_ptr = torch.zeros(1, dtype=torch.int32, device=device)
                 ops.lincomb(plan, x0_thr, x0_prev, tables[2], zero_ptr, B=B, n_per_sample=n, label="dpmpp_2m.history")
                 # the first step of a run has no history: its row is first order, wherever skip_steps starts the run (_run_stage)
@@ -629,8 +674,12 @@ class Imagen(nn.Module):
             ops.lincomb(plan, eng.x_in, eng.x_in, tables[2], step_ptr, B=B, n_per_sample=n, t1=st['noise_renoise'], advance=True,
                         stream_id=idx | 0x200, sample_offset=sample_offset, seed_ptr=seed_dev, label="inpaint.renoise")
         st.update(plan=plan, T=T, row_keys=row_keys, quant=quant, x0=x0, x0_thr=x0_thr, noise_blend=noise_blend, solver=solver,
-                  x0_prev=x0_prev, weights=tables[1] if solver is not None else None, weights_at=weights_at, weights_start=0)
+                  x0_prev=x0_prev, weights=tables[1] if solver is not None else None, weights_at=weights_at, weights_start=0,
+                  tables=tables, scales=None if guidance is None else [float(v) for v in guidance])
         self._stages[key] = st
+        if guidance is not None and 1. in st['scales']:
+            st['sibling'] = self._build_stage(idx, B, device, cond_scale=1., with_text=with_text, inject_noise=inject_noise, sample_offset=sample_offset,
+                                              frames=frames, prompt_frames=prompt_frames, size=size, solver=solver, share=st)
         return st
 
     # ---- what both samplers' `_run_stage` share
@@ -662,8 +711,11 @@ class Imagen(nn.Module):
                       skip_steps: Optional[int] = None):
         """ip.py:2167-2289 for one stage: x_T ~ N(0, I) (+ init_images), the ancestral steps from `skip_steps` on (each run
         `inpaint_resample_times` times when st is an inpainting plan), clamp + unnormalise (done by the last step's kernel) and
-        the final paste of the known pixels."""
+        the final paste of the known pixels.  A stage with a guidance schedule (st['scales']) that has unguided steps replays, on those,
+        its B-row sibling, which runs on the same state: which captured graph a step launches is read from the host-side vector."""
         eng, plan, T, R = st['eng'], st['plan'], st['T'], st['R']
+        scales, sibling = st['scales'], st['sibling']
+        stage_of = (lambda i: st) if sibling is None else (lambda i: sibling if scales[i] == 1. else st)
         B = eng.src_batch
         stream = torch.cuda.current_stream()
         skip = skip_steps or 0
@@ -702,12 +754,13 @@ class Imagen(nn.Module):
             keys[r0:r0 + cnt, 2] = torch.arange(i0, i0 + cnt)
         st['row_keys'].copy_(keys.to(torch.int32))
         steps = T - skip if max_steps is None else min(T - skip, max_steps)
-        if use_graph and st['graph'] is None:
-            plan.run()                                   # warm-up outside capture (sets kernel attributes), then rewind
-            reset_state()
-            torch.cuda.synchronize()
-            st['graph'] = ops.Graph(plan, stream)
         it = range(skip, skip + steps)
+        for s in ([st] if sibling is None else [s for s in (st, sibling) if any(stage_of(i) is s for i in it)]):
+            if use_graph and s['graph'] is None:
+                s['plan'].run()                          # warm-up outside capture (sets kernel attributes), then rewind
+                reset_state()
+                torch.cuda.synchronize()
+                s['graph'] = ops.Graph(s['plan'], stream)
         if use_tqdm:
             try:
                 from tqdm.auto import tqdm
@@ -725,9 +778,9 @@ class Imagen(nn.Module):
                     elif st['solver'] is None or st['solver'][2] > 0.:      # (the deterministic solvers draw nothing after the initial image)
                         st['noise'].copy_(draw(("step", stage, i), st['noise']))
                 if use_graph:
-                    st['graph'].launch()
+                    stage_of(i)['graph'].launch()
                 else:
-                    plan.run()
+                    stage_of(i)['plan'].run()
                 if trace is not None:
                     trace.append(eng.x_in.clone())
         return self._stage_output(st, eng.x_in, skip + steps == T)
@@ -887,12 +940,55 @@ class Imagen(nn.Module):
         sampler: str = 'ddpm',                         # extension: 'ddpm' (the reference's ancestral step, one per training timestep), or a few-step
         sample_steps=None,                             #   solver on the same checkpoint: 'dpmpp_2m' (DPM-Solver++ 2M) | 'ddim', in `sample_steps`
         eta: float = 0.,                               #   steps (an int or one per unet; None: the unet's timesteps); eta: 'ddim' only, 0 .. 1
+        guidance_schedule=None,                        # extension: the guidance scale of every step in place of the fixed cond_scale: a callable
+                                                       #   f(t) -> float (t = 1: pure noise) or a sequence with one entry per denoiser evaluation
+        guidance_interval=None,                        # extension: (t_lo, t_hi): the steps with t outside it run unguided (scale 1, the B-row plan);
+                                                       #   both: one value for every unet, or a tuple with one entry (or None) per unet.
+                                                       #   Every distinct per-step vector is a cached stage of its own (engine, time table, graph;
+                                                       #   with unguided steps also the B-row sibling) that is kept, as every stage is: a sweep
+                                                       #   over many schedules grows the cache — sample from a fresh Imagen, or clear `_stages`
     ):
         return self._sample(self._call(**{k: v for k, v in locals().items() if k != 'self'}))   # (the keywords, as given)
 
     def _call(self, **kw) -> _Call:
         """The record of one call from sample()'s keywords (+ the private ones of _Call)."""
         return _Call(**kw)
+
+    def _guidance_of(self, guidance_schedule=None, guidance_interval=None):
+        """The guidance keywords of one call, per unet and checked as far as that goes without the step counts: None when neither is given,
+        else (schedules, intervals), one entry per unet each — a schedule None, a callable or a list of floats, an interval None or a
+        checked (t_lo, t_hi).  A sequence of numbers is ONE schedule (a pair of numbers ONE interval) and serves every unet; a tuple whose
+        entries are None, callables or sequences holds one per unet.  Raises ValueError where the keywords cannot act: a model trained
+        without conditional dropout, or without a text branch (the conditions of _check_negative)."""
+        from .schedules import check_guidance_interval
+
+        if guidance_schedule is None and guidance_interval is None:
+            return None
+        n = len(self.unets)
+        number = lambda v: isinstance(v, (int, float)) or (isinstance(v, torch.Tensor) and v.ndim == 0)
+        flat = lambda v: isinstance(v, torch.Tensor) and v.ndim == 1 or (isinstance(v, (list, tuple)) and len(v) > 0 and all(number(e) for e in v))
+
+        def per_unet(val, kw):
+            if val is None or callable(val) or flat(val):
+                return (val,) * n
+            if not isinstance(val, (list, tuple)):
+                raise ValueError(f'{kw} = {val!r}: one value, or a tuple with one entry per unet')
+            if len(val) != n:
+                raise ValueError(f'{kw}: {len(val)} entries for {n} unets (one entry, or None, per unet)')
+            return tuple(val)
+
+        schedules = tuple(s if s is None or callable(s) else [float(v) for v in s] if flat(s) else s for s in per_unet(guidance_schedule, 'guidance_schedule'))
+        for i, s in enumerate(schedules):
+            if not (s is None or callable(s) or isinstance(s, list)):
+                raise ValueError(f'guidance_schedule[{i}] = {s!r}: None, a callable f(t) -> float or a sequence of floats')
+        intervals = tuple(None if v is None else check_guidance_interval(v, f'guidance_interval[{i}]')
+                          for i, v in enumerate(per_unet(guidance_interval, 'guidance_interval')))
+        kw = 'guidance_schedule' if guidance_schedule is not None else 'guidance_interval'
+        if not self.can_classifier_guidance:
+            raise ValueError(f'{kw}: imagen was not trained with conditional dropout (cond_drop_prob == 0) and cannot do classifier free guidance')
+        if self.unconditional:
+            raise ValueError(f'{kw}: this model was built with condition_on_text=False, there is no text branch to guide')
+        return schedules, intervals
 
     def _solver_of(self, sampler=None, sample_steps=None, eta=None):
         """The solver keywords of one call, checked: None for the ancestral sampler ('ddpm', the default: one step per training timestep),
@@ -1103,12 +1199,14 @@ class Imagen(nn.Module):
         c.skip_steps = _cast_tuple(c.skip_steps, num_unets)
         c.level = c.lowres_sample_noise_level if c.lowres_sample_noise_level is not None else self.lowres_sample_noise_level
         c.cond_scale = _cast_tuple(c.cond_scale, num_unets)
+        c.guidance = self._resolve_guidance(c)
         if c.seed is None:
             c.seed = self._next_seed()
         # the negative prompt of this call: resolved and checked here, before any stage is built or anything is launched
         if c.negative is not None:
             last = num_unets if c.stop_at_unet_number is None else c.stop_at_unet_number
-            scales = None if c.pipelined_stage else c.cond_scale[c.start_at_unet_number - 1:last]
+            scales = [cs if g is None else None for cs, g in zip(c.cond_scale, c.guidance)]      # (None: a schedule that varies, so not 1)
+            scales = None if c.pipelined_stage else scales[c.start_at_unet_number - 1:last]
             c.neg_embeds, c.neg_masks, c.neg_rows = self._check_negative(c.negative, c.batch_size, scales, device)
 
         if c.start_at_unet_number > 1:
@@ -1124,6 +1222,45 @@ class Imagen(nn.Module):
                 img = self._resize(img.reshape(-1, *img.shape[-3:]), prev_size).reshape(*lead, self.channels, *prev_hw).contiguous()
             c.img = img
         return c
+
+    def _resolve_guidance(self, c: _Call) -> tuple:
+        """`guidance_schedule` / `guidance_interval` of one call (its solver and per-unet cond_scale already resolved) -> per unet None, or
+        the fp32 [steps] guidance scales of a stage whose scale varies (schedules.guidance_scales on the grid of the stage's sampler).  A
+        stage whose resolved scales are all the same is an ordinary stage at that scale: it is written to c.cond_scale[idx] (left as given
+        where it already is that value) and the entry stays None, so a constant schedule meets the stage — and the cache key — of the
+        scalar call.  Only the stages the call runs are resolved; nothing is launched."""
+        last = len(self.unets) if c.stop_at_unet_number is None else c.stop_at_unet_number
+        out, scales = self._guidance_vectors(self._guidance_of(c.guidance_schedule, c.guidance_interval), c.cond_scale, c.solver,
+                                             c.inpaint_images is not None or c.inpaint_masks is not None, c.start_at_unet_number - 1, last)
+        c.cond_scale = scales
+        return out
+
+    def _guidance_vectors(self, given, cond_scale: tuple, solver, inpainting: bool, first: int, last: int):
+        """_resolve_guidance on plain values, for the stages [first, last): (per unet None | the fp32 scales, the per-unet cond_scale with the
+        constant schedules written in).  sample_pipelined checks a whole cascade with it before a thread starts."""
+        from .schedules import guidance_scales
+
+        n = len(self.unets)
+        if given is None:
+            return (None,) * n, tuple(cond_scale)
+        if inpainting:
+            raise ValueError('guidance_schedule / guidance_interval with inpainting: the resample loop (ip.py:2237-2275) runs every table row '
+                             'several times on one captured plan; sample with a fixed cond_scale when inpainting')
+        out, scales = [None] * n, list(cond_scale)
+        for idx in range(first, last):
+            sched, interval = given[0][idx], given[1][idx]
+            if sched is None and interval is None:
+                continue
+            if not getattr(self.unets[idx], 'cond_on_text', False):
+                raise ValueError(f'guidance_schedule / guidance_interval: unet {idx + 1} has no text branch (cond_on_text=False), there is nothing to guide')
+            steps = self.noise_schedulers[idx].num_timesteps if solver is None else solver[idx][1]
+            vec = guidance_scales(steps, scales[idx], sched, interval, what=f'unet {idx + 1}')
+            if bool((vec == vec[0]).all()):
+                if float(torch.tensor(float(scales[idx]), dtype=torch.float32)) != float(vec[0]):
+                    scales[idx] = float(vec[0])
+            else:
+                out[idx] = vec
+        return tuple(out), tuple(scales)
 
     def _prepare_stage(self, c: _Call, idx: int) -> dict:
         """Stage `idx` made ready for `_run_stage`: the prompt frames at its frame rate, the stage itself (built or fetched), its conditioning
@@ -1146,6 +1283,8 @@ class Imagen(nn.Module):
         extra = {} if c.sigma_overrides is None else dict(sigma_overrides=c.sigma_overrides)
         if c.solver is not None:
             extra['solver'] = c.solver[idx]
+        if c.guidance is not None and c.guidance[idx] is not None:
+            extra['guidance'] = c.guidance[idx]
         st = self._stage(idx, batch_size, device, cond_scale=cs, with_text=with_text, inject_noise=noise_fn is not None,
                          sample_offset=c.sample_offset, resample_times=c.inpaint_resample_times if c.known is not None else 0,
                          frames=c.frames // self.temporal_downsample_factor[idx] if isinstance(unet, Unet3D) else 0,
@@ -1154,10 +1293,13 @@ class Imagen(nn.Module):
         S = st['S']
         assert not (getattr(unet, 'has_cond_image', False) ^ (c.cond_images is not None)), \
             'you either requested to condition on an image on the unet, but the conditioning image is not supplied, or vice versa'   # ip.py:1555
-        if c.cond_images is not None:
-            eng.set_cond_images(c.cond_images)
-        if prompts[0] is not None or prompts[1] is not None:
-            eng.set_cond_video_frames(*prompts)
+        # (a stage with a guidance schedule that has unguided steps: its B-row sibling reads the same sampler state, and is conditioned alike)
+        engines = [eng] if st['sibling'] is None else [eng, st['sibling']['eng']]
+        for e in engines:
+            if c.cond_images is not None:
+                e.set_cond_images(c.cond_images)
+            if prompts[0] is not None or prompts[1] is not None:
+                e.set_cond_video_frames(*prompts)
         if c.known is not None and st['video']:
             st['known'].copy_(self._resize_clip(c.known, S, st['frames']))
             st['mask'].copy_(self._resize_clip(c.known_mask, S, st['frames']).bool().expand(-1, -1, self.channels, -1, -1))
@@ -1194,20 +1336,21 @@ class Imagen(nn.Module):
             ops.lowres_prep(prep, as_images(src), as_images(aug), as_images(eng.lowres_in), alpha=a, sigma=s)
             prep.keep += [src, aug, eng.lowres_in]
             prep.run()
-        rows = eng.R
-        keep = torch.ones(rows, dtype=torch.bool)
-        if rows == 2 * batch_size:
-            keep[batch_size:] = False            # second half = null-conditioned CFG branch (cond_drop_prob = 1, ip.py:1521)
         cond = c.conditioning
         stamp = None if cond is None else (cond.token, None if lowres_logsnr is None else float(lowres_logsnr[0]))
-        if stamp is None or getattr(eng, '_cond_stamp', None) != stamp:
-            neg_kw = {}
-            if c.neg_embeds is not None and with_text and rows == 2 * batch_size:     # (a stage at cond_scale 1 has no null rows)
-                neg_kw = dict(negative_text_embeds=c.neg_embeds, negative_text_mask=c.neg_masks, negative_rows=c.neg_rows)
-            eng.set_conditioning(text_embeds=c.text_embeds if with_text else None, text_mask=c.text_masks if with_text else None,
-                                 keep=keep, lowres_noise_times=lowres_logsnr, **neg_kw)
-            eng.static_runs = getattr(eng, 'static_runs', 0) + 1
-        eng._cond_stamp = stamp
+        for eng in engines:
+            rows = eng.R
+            keep = torch.ones(rows, dtype=torch.bool)
+            if rows == 2 * batch_size:
+                keep[batch_size:] = False            # second half = null-conditioned CFG branch (cond_drop_prob = 1, ip.py:1521)
+            if stamp is None or getattr(eng, '_cond_stamp', None) != stamp:
+                neg_kw = {}
+                if c.neg_embeds is not None and with_text and rows == 2 * batch_size:     # (a stage at cond_scale 1 has no null rows)
+                    neg_kw = dict(negative_text_embeds=c.neg_embeds, negative_text_mask=c.neg_masks, negative_rows=c.neg_rows)
+                eng.set_conditioning(text_embeds=c.text_embeds if with_text else None, text_mask=c.text_masks if with_text else None,
+                                     keep=keep, lowres_noise_times=lowres_logsnr, **neg_kw)
+                eng.static_runs = getattr(eng, 'static_runs', 0) + 1
+            eng._cond_stamp = stamp
         return st
 
     @torch.no_grad()

@@ -1363,6 +1363,11 @@ OBJECTIVES = {"noise": 0, "x_start": 1, "v": 2}
 
 def cfg_x0(plan: Plan, x, pred, coef, step_ptr, x0, absx0, *, B, n_per_sample, cfg: bool, cond_scale: float, objective: str = "noise",
            label: str = ""):
+    """cfg: False / 0 unguided, True / 1 guided at `cond_scale`, 2 guided at column 7 of the current row of `coef` (a guidance schedule)."""
+    if int(cfg) not in (0, 1, 2):
+        raise ValueError(f"cfg_x0: cfg = {cfg!r}; 0 (unguided), 1 (cond_scale) or 2 (the scale in column 7 of the step's table row)")
+    if int(cfg) == 2 and not (coef.dtype == torch.float32 and coef.ndim == 2 and coef.shape[1] == 8 and coef.is_contiguous()):
+        raise ValueError("cfg_x0: cfg = 2 reads the scale from a contiguous fp32 [steps, 8] table")
     p = STRUCTS["ImagenCfgX0Params"]()
     p.x, p.pred, p.coef, p.step_ptr, p.x0, p.absx0 = x.data_ptr(), pred.data_ptr(), coef.data_ptr(), step_ptr.data_ptr(), x0.data_ptr(), absx0.data_ptr()
     p.B, p.n_per_sample, p.cfg, p.cond_scale, p.objective = B, n_per_sample, int(cfg), cond_scale, OBJECTIVES[objective]

@@ -29,8 +29,56 @@ def log_snr_to_alpha_sigma(log_snr: torch.Tensor):
     return torch.sqrt(torch.sigmoid(log_snr)), torch.sqrt(torch.sigmoid(-log_snr))
 
 
-COEF_COLS = 8  # [alpha, sigma, alpha_next, sigma_next, c, nonzero, log_snr, 0] — layout shared with csrc/sampler.hip
+COEF_COLS = 8  # [alpha, sigma, alpha_next, sigma_next, c, nonzero, log_snr, guidance scale of the step | 0] — layout shared with csrc/sampler.hip
 SOLVERS = ('ddim', 'dpmpp_2m')   # the few-step solvers of Imagen.sample(sampler=...); 'ddpm' is the ancestral step of step_coefficients()
+
+
+def step_times(steps: int) -> list:
+    """The continuous time t of every row of a [steps, 8] table on the grid linspace(1, 0, steps + 1) — the ancestral table of
+    step_coefficients() and the solver tables alike — as python floats (steps - i) / steps: t = 1 is pure noise, the last row sits at
+    1 / steps.  The quotient of two integers is the double nearest the rational, so a bound a caller writes as 0.2 meets the row at 1 / 5."""
+    return [(steps - i) / steps for i in range(steps)]
+
+
+def check_guidance_interval(interval, what: str = 'guidance_interval') -> tuple:
+    """(t_lo, t_hi) as floats, 0 <= t_lo < t_hi <= 1; ValueError otherwise."""
+    try:
+        lo, hi = (float(v) for v in interval)
+    except (TypeError, ValueError):
+        raise ValueError(f'{what} = {interval!r}: a pair (t_lo, t_hi) of times, t = 1 being pure noise') from None
+    if not (0. <= lo <= 1. and 0. <= hi <= 1.):              # (NaN fails both)
+        raise ValueError(f'{what} = ({lo}, {hi}) lies outside [0, 1]')
+    if not lo < hi:
+        raise ValueError(f'{what} = ({lo}, {hi}) is empty: t_lo < t_hi')
+    return lo, hi
+
+
+def guidance_scales(steps: int, cond_scale: float, schedule=None, interval=None, what: str = 'guidance') -> torch.Tensor:
+    """The guidance scale of every denoiser evaluation of a stage of `steps` steps, as the fp32 [steps] vector that goes into column 7 of
+    the stage's step table (CFG_X0 with cfg == 2).  `schedule`: None (`cond_scale` on every step), a callable f(t) -> float evaluated at
+    step_times(steps), or a sequence of exactly `steps` floats.  `interval` = (t_lo, t_hi): the steps with t outside [t_lo, t_hi] run
+    unguided, at scale 1.  ValueError for a sequence of another length, a value that is not finite, a bad interval."""
+    ts = step_times(steps)
+    if schedule is None:
+        vals = [float(cond_scale)] * steps
+    elif callable(schedule):
+        vals = [float(schedule(t)) for t in ts]
+    else:
+        try:
+            vals = [float(v) for v in schedule]
+        except TypeError:
+            raise ValueError(f'{what}: guidance_schedule is a callable f(t) -> float or a sequence of floats, got {type(schedule).__name__}') from None
+        if len(vals) != steps:
+            raise ValueError(f'{what}: guidance_schedule has {len(vals)} entries, the stage has {steps} denoiser evaluations.  A sequence of '
+                             f'numbers is ONE schedule with an entry per step, for every unet (unlike cond_scale, where a tuple holds one value per '
+                             f'unet); one schedule per unet is a tuple of sequences / callables / None, e.g. ([...], None)')
+    out = torch.tensor(vals, dtype=torch.float64).float()
+    if not bool(torch.isfinite(out).all()):
+        raise ValueError(f'{what}: guidance_schedule gives a scale that is not finite (in fp32): {vals}')
+    if interval is not None:
+        lo, hi = check_guidance_interval(interval, what + ': guidance_interval')
+        out[torch.tensor([not lo <= t <= hi for t in ts])] = 1.
+    return out
 
 
 class GaussianDiffusionContinuousTimes(nn.Module):

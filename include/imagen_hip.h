@@ -383,7 +383,10 @@ typedef struct ImagenPackImageParams {
 
 /* CFG_X0 — ip.py:1522 + 2085-2092: out = null + (cond-null)*s ; x0 = (x - sigma*out)/max(alpha,1e-8) (objective 0 = noise,
  * ip.py:314-318) | out (1 = x_start) | alpha*x - sigma*out (2 = v, ip.py:308-312);
- * writes x0 and |x0| (for the quantile).  pred is [2B,...] (cond first) when cfg != 0, else [B,...]. */
+ * writes x0 and |x0| (for the quantile).  pred is [2B,...] (cond first) when cfg != 0, else [B,...].
+ * cfg: 0 = unguided (out = pred), 1 = guided with s = cond_scale, 2 = guided with s = coef[*step_ptr][7], the step's own scale (a guidance
+ * schedule: slot 7 is the `pad` slot of the row documented at ImagenDdpmUpdateParams, which no other kernel reads; cond_scale is then unused).
+ * The arithmetic of 1 and 2 is the same expression, so a constant column gives the bits of the immediate.  Any other value is refused. */
 typedef struct ImagenCfgX0Params {
   const float* x; const float* pred; const float* coef; const int32_t* step_ptr; float* x0; float* absx0;
   int32_t B, n_per_sample, cfg, objective; float cond_scale;
@@ -398,7 +401,7 @@ typedef struct ImagenQuantileParams {
 #define IMAGEN_QUANTILE_SCRATCH_WORDS (4 * 256 + 8)
 
 /* DDPM_UPDATE — ip.py:2103-2105, 252-270, 2160-2164 and final clamp/unnormalise ip.py:2281-2289.
- * coef table row (per step): [alpha, sigma, alpha_next, sigma_next, c, nonzero, log_snr, pad]. */
+ * coef table row (per step): [alpha, sigma, alpha_next, sigma_next, c, nonzero, log_snr, pad]  (pad: read by CFG_X0 with cfg == 2 only). */
 typedef struct ImagenDdpmUpdateParams {
   float* x; const float* x0; const float* quant; const float* coef; const float* noise; float* final_out;
   int32_t* step_ptr; /* device step counter: read by every sampler kernel of the step, incremented at the end */
