@@ -20,7 +20,6 @@ step's; both go straight into the engine's `self_cond_in`, which every evaluatio
 """
 from __future__ import annotations
 
-import functools
 import math
 from collections import namedtuple
 from typing import Callable, List, Optional
@@ -29,7 +28,7 @@ import torch
 
 from . import ops
 from .unet3d import Unet3D
-from .imagen import DEFAULT_T5_NAME, TAG_INIT, Imagen, _cast_tuple, _out_of_scope
+from .imagen import DEFAULT_T5_NAME, Imagen, _cast_tuple, _out_of_scope
 from .ops import Plan
 
 Hparams_fields = ['num_sample_steps', 'sigma_min', 'sigma_max', 'sigma_data', 'rho', 'P_mean', 'P_std', 'S_churn', 'S_tmin', 'S_tmax', 'S_noise']
@@ -155,16 +154,16 @@ class ElucidatedImagen(Imagen):
         R = resample_times
         key = ("edm", idx, B, size, str(device), float(cond_scale), with_text, inject_noise, sample_offset,
                self.dynamic_thresholding[idx], self.dynamic_thresholding_percentile, tuple(hp), frames, prompt_frames, R, self._lane)
-        tables = []
 
-        def coef():
+        def tables():                                    # `_tables` on the device, then w_init = (sigma_0, 0, ...), the scale of the initial noise
             init_sigma, tabs = self._tables(hp, max(R, 1))
-            tables[:] = [init_sigma] + [t.to(device) for t in tabs]
-            return tables[1]
+            w_init = torch.zeros(1, 8, device=device)
+            w_init[0, 0] = init_sigma
+            return [t.to(device) for t in tabs] + [w_init]
 
         # (the time table of an image stage has this sampler's 2T evaluation rows: both denoiser evaluations of a step read it)
         st, built = self._new_stage(key, idx, B, device, cfg=cfg, with_text=with_text, inject_noise=inject_noise, sample_offset=sample_offset,
-                                    resample_times=R, frames=frames, prompt_frames=prompt_frames, coef=coef, size=size)
+                                    resample_times=R, frames=frames, prompt_frames=prompt_frames, tables=tables, size=size)
         if not built:
             return st
         eng, n, dev, step_ptr, seed_dev, step_plan, noise, final = (st['eng'], st['n'], device, st['step_ptr'], st['seed_dev'], st['step_plan'],
@@ -173,7 +172,7 @@ class ElucidatedImagen(Imagen):
         # it for the Heun evaluation, the Heun op the second one's for the next step (or the next resample of the same timestep)
         sc = eng.self_cond_in if getattr(unet, 'self_cond', False) else None
         assert sc is None or sc.numel() == B * n
-        init_sigma, coef, w_hat, w_euler, w_heun, w_renoise = tables
+        coef, w_hat, w_euler, w_heun, w_renoise, w_init = st['tables']
         if inject_noise:   # the churn noise comes in through t1 (weight col 1) instead of the in-kernel Philox stream (col 4)
             for w in (w_hat, w_renoise):
                 w[:, 1] = w[:, 4]
@@ -224,78 +223,54 @@ class ElucidatedImagen(Imagen):
         ops.lincomb(last, xhat, x, w_euler, step_ptr, t1=x0a, q1=qa if dyn else None, thr_mode=thr, final=True, final_out=final,
                     advance=True, thr1_out=sc if R > 1 else None, label="edm.euler.final", **kw)
 
-        w_init = torch.zeros(1, 8, device=dev)
-        w_init[0, 0] = init_sigma
-        st.update(plan=full, last=last, graph_last=None, T=hp.num_sample_steps, x=x, w_init=w_init, zero_ptr=zero_ptr,
+        init_scale = Plan("edm-init-scale")             # images = init_sigma * randn (el.py:440-442; sigma_0 also when steps are skipped)
+        ops.lincomb(init_scale, x, x, w_init, zero_ptr, B=B, n_per_sample=n)
+        st.update(plan=full, last=last, graph_last=None, T=hp.num_sample_steps, x=x, w_init=w_init, zero_ptr=zero_ptr, init_scale=init_scale,
                   tables=(w_hat, w_euler, w_heun, w_renoise, w_one), self_cond=sc, bufs=(xhat, xnext, x0a, x0b, absx0, qa, qb, scr_a, scr_b))
         self._stages[key] = st
         return st
 
-    @torch.no_grad()
-    def _run_stage(self, st, *, noise_fn: Optional[Callable], stage: int, seed: int, use_graph: bool = True, use_tqdm: bool = False,
-                      max_steps: Optional[int] = None, trace: Optional[list] = None, init_images=None, skip_steps=None):
-        """el.py:393-545 for one stage: x = sigma_0 * randn (+ init_images), the Karras steps from `skip_steps` on (each run
-        `inpaint_resample_times` times when st is an inpainting stage), clamp + unnormalise (the last step's kernel) and the final
-        paste of the known pixels."""
-        eng, T, x, R = st['eng'], st['T'], st['x'], st['R']
-        skip = skip_steps or 0
-        assert 0 <= skip < T, 'skip_steps must leave at least one step'
-        inner = max(R, 1)
-        stream = torch.cuda.current_stream()
-        B = eng.src_batch
-        n = x[0].numel()
+    # ---- what this sampler puts into Imagen._run_stage (el.py:393-545 for one stage) ------------------------------------------------
+    _per_row_noise_keys = False    # the churn and re-noising launches (LINCOMB) take one key per batch
+    _plan_prefix = 'edm-'
+    _step_noun = 'step'
 
-        draw = functools.partial(self._draw, st, noise_fn)
+    def _rewind(self, st, skip: int, init_images):
+        """x = sigma_0 * randn (+ init_images), no x_start, the counter on the first row of step `skip`."""
+        st['init_scale'].run()
+        if init_images is not None:
+            st['x'].add_(init_images)                    # el.py:446-447
+        if st['self_cond'] is not None:
+            st['self_cond'].zero_()                      # el.py:451: x_start = None (also after the warm-up and when steps are skipped)
+        st['step_ptr'].fill_(self._row(skip, max(st['R'], 1) - 1, st['T'], max(st['R'], 1)))   # el.py:477-479: the skipped steps are never run
 
-        def init_state():
-            if noise_fn is not None:
-                x.copy_(draw(("init", stage), x))
-            else:
-                pl = Plan("edm-init-noise")
-                ops.randn(pl, x, seed=seed, stream_id=stage, tag=TAG_INIT, sample_offset=st['sample_offset'])
-                pl.run()
-            pl = Plan("edm-init-scale")                      # images = init_sigma * randn (el.py:440-442; sigma_0 also when steps are skipped)
-            ops.lincomb(pl, x, x, st['w_init'], st['zero_ptr'], B=B, n_per_sample=n)
-            pl.run()
-            if init_images is not None:
-                x.add_(init_images)                          # el.py:446-447
-            if st['self_cond'] is not None:
-                st['self_cond'].zero_()                      # el.py:451: x_start = None (also after the warm-up and when steps are skipped)
-            st['step_ptr'].fill_(self._row(skip, inner - 1, T, inner))   # el.py:477-479: the skipped steps are never run
+    def _plans_of_steps(self, st, steps: range) -> list:
+        """The last step (sigma_next = 0) has no second-order correction: its own plan and graph."""
+        return [(st, 'last' if i == st['T'] - 1 else 'plan') for i in steps]
 
-        st['seed_dev'].copy_(torch.tensor(self._seed_words(seed), dtype=torch.int32))
-        steps = T - skip if max_steps is None else min(T - skip, max_steps)
-        if use_graph and st['graph'] is None:
-            if noise_fn is not None:
-                st['noise'].zero_()
-                if R:
-                    st['noise_renoise'].zero_()
-            init_state()
-            # warm-up outside capture (kernel attributes), then rewind.  Both plans run from table row 0: `plan` advances the device
-            # step counter by its two evaluations, and started from the last timestep's rows (skip_steps = T - 1) `last` would read past
-            # the 2T-row tables (the kernels do not clamp *step_ptr) and `plan` would feed the all-zero final row into CFG_X0
-            st['step_ptr'].zero_()
-            st['plan'].run()
-            st['step_ptr'].zero_()
-            st['last'].run()
-            torch.cuda.synchronize()
-            st['graph'] = ops.Graph(st['plan'], stream)
-            st['graph_last'] = ops.Graph(st['last'], stream)
-        init_state()
-        for i in range(skip, skip + steps):
-            is_last = i == T - 1
-            for r in reversed(range(inner)):
-                if noise_fn is not None:
-                    st['noise'].copy_(draw(("step", stage, i, r) if R else ("step", stage, i), st['noise']))
-                    if R and r > 0 and not is_last:           # the reference draws no re-noising sample otherwise (el.py:532)
-                        st['noise_renoise'].copy_(draw(("renoise", stage, i, r), st['noise']))
-                if use_graph:
-                    (st['graph_last'] if is_last else st['graph']).launch()
-                else:
-                    (st['last'] if is_last else st['plan']).run()
-                if trace is not None:
-                    trace.append(x.clone())
-        return self._stage_output(st, x, skip + steps == T)
+    def _capture(self, st, plans: list, rewind, stream):
+        if st['graph'] is not None:
+            return
+        if st['noise'] is not None:
+            st['noise'].zero_()
+            if st['R']:
+                st['noise_renoise'].zero_()
+        # warm-up outside capture (kernel attributes), then rewind.  Both plans run from table row 0: `plan` advances the device
+        # step counter by its two evaluations, and started from the last timestep's rows (skip_steps = T - 1) `last` would read past
+        # the 2T-row tables (the kernels do not clamp *step_ptr) and `plan` would feed the all-zero final row into CFG_X0
+        st['step_ptr'].zero_()
+        st['plan'].run()
+        st['step_ptr'].zero_()
+        st['last'].run()
+        torch.cuda.synchronize()
+        st['graph'] = ops.Graph(st['plan'], stream)
+        st['graph_last'] = ops.Graph(st['last'], stream)
+        rewind()
+
+    def _draw_step_noise(self, st, draw, stage: int, i: int, r: int):
+        st['noise'].copy_(draw(("step", stage, i, r) if st['R'] else ("step", stage, i), st['noise']))
+        if st['R'] and r > 0 and i < st['T'] - 1:        # the reference draws no re-noising sample otherwise (el.py:532)
+            st['noise_renoise'].copy_(draw(("renoise", stage, i, r), st['noise']))
 
     # ---- public sampling API (el.py:547-745) ---------------------------------------------------------------------------------
     @torch.no_grad()

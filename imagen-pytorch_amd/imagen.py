@@ -378,7 +378,7 @@ class Imagen(nn.Module):
                   'noise_fn', 'start_image_or_video', 'conditioning', 'return_pil_images', 'return_all_unet_outputs', 'sample_offset'):
             if common.get(k) is not None or any(r.get(k) is not None for r in requests):
                 _out_of_scope(f"sample_requests(..., {k}=...)")
-        if type(self)._run_stage is not Imagen._run_stage:
+        if not self._per_row_noise_keys:
             _out_of_scope(f"{type(self).__name__}.sample_requests (its sampler's noise launches take one key per batch)")
         if not requests:
             return []
@@ -514,14 +514,24 @@ class Imagen(nn.Module):
                 torch.cuda.current_stream().synchronize()
             return st
 
+    # The sampler state of a stage: what `_new_stage` allocates or, with share=, adopts (beside the engine's `x_in` / low-res image, adopted
+    # through `eng.share_sampler_state`).  The one list of it: a buffer both plans of a guidance schedule must see is added here alone.
+    SHARED_STATE = ('step_ptr', 'seed_dev', 'row_keys', 'noise', 'final', 'x0_thr', 'x0_prev', 'tables')
+    _per_row_noise_keys = True      # this sampler's noise launches take per-row Philox keys (st['row_keys']): what sample_requests merges on
+    _plan_prefix = ''               # of the names of the plans `_run_stage` builds
+    _step_noun = 'timestep'
+    _GRAPH_OF = {'plan': 'graph', 'last': 'graph_last'}     # the stage entry that holds a plan's captured graph
+
     def _new_stage(self, key: tuple, idx: int, B: int, device, *, cfg: bool, with_text: bool, inject_noise: bool, sample_offset: int,
-                   resample_times: int, frames: int, prompt_frames: tuple, coef: Callable, size=None, share: Optional[dict] = None):
+                   resample_times: int, frames: int, prompt_frames: tuple, tables: Callable, size=None, buffers: tuple = (),
+                   share: Optional[dict] = None):
         """What both samplers' `_build_stage` do first.  Returns (the cached stage of `key`, False) while its engine is not stale; else
-        (a new stage dict, True): the engine (image or video), the device step counter and seed words, the engine bound to `coef()` — the
-        sampler's per-evaluation table, built only now — the per-request time table where it applies, and the buffers every sampler has.
-        EVERY key the run side reads is present (None where unused); the sampler adds its plan(s), tables and buffers and files the stage.
-        share: the stage whose sampler state this one runs on (the unguided sibling of a stage with a guidance schedule): its engine reads
-        that stage's `x_in` / low-res image, and the step counter, seed words, noise and output buffers are that stage's."""
+        (a new stage dict, True): the engine (image or video), the sampler state (SHARED_STATE), the engine bound to the step counter and to
+        `coef` = tables[0], the per-request time table where it applies, the buffers of inpainting.  EVERY key the run side reads is present
+        (None where unused); the sampler adds its plan(s) and files the stage.  tables: () -> the sampler's device tables, [rows, 8] each,
+        the per-evaluation one first; called only on a cache miss.  buffers: which of the optional [B, n] state buffers ('x0_thr',
+        'x0_prev') the step needs.  share: the stage whose sampler state this one runs on (the unguided sibling of a stage with a guidance
+        schedule): the very objects of `share` are this stage's own, and its engine reads that stage's `x_in` / low-res image."""
         st = self._stages.get(key)
         if st is not None and not st['eng'].stale():
             return st, False
@@ -539,13 +549,20 @@ class Imagen(nn.Module):
         else:
             from . import engine
             eng = engine.UnetEngine(unet, rows, B, S, device, with_text=with_text)
+        n = eng.x_in[0].numel()
         if share is not None:
+            assert not R, 'a shared sampler state does not cover the inpainting plan'
             eng.share_sampler_state(share['eng'])
-            step_ptr, seed_dev = share['step_ptr'], share['seed_dev']
+            state = {k: share[k] for k in self.SHARED_STATE}
         else:
-            step_ptr = torch.zeros(1, dtype=torch.int32, device=device)
-            seed_dev = torch.zeros(2, dtype=torch.int32, device=device)
-        coef = coef()
+            per_sample = lambda k: torch.zeros(B, n, device=device) if k in buffers else None   # (video: the frame-major clip, as the state)
+            state = dict(step_ptr=torch.zeros(1, dtype=torch.int32, device=device), seed_dev=torch.zeros(2, dtype=torch.int32, device=device),
+                         # (Philox key lo, hi, global sample index, 0) of every row: _run_stage fills it per call
+                         row_keys=torch.zeros(B, 4, dtype=torch.int32, device=device) if self._per_row_noise_keys else None,
+                         noise=torch.empty_like(eng.x_in) if inject_noise else None, final=torch.empty_like(eng.x_in),
+                         x0_thr=per_sample('x0_thr'), x0_prev=per_sample('x0_prev'), tables=tables())
+            assert tuple(state) == self.SHARED_STATE
+        coef, step_ptr = state['tables'][0], state['step_ptr']
         eng.bind_step_counter(coef, step_ptr)
         # image stages without inpainting resampling: the timestep-only conditioning chain of the denoiser is evaluated for all steps at
         # once per request (engine.enable_time_table: the table has one row per evaluation of `coef`), each step copies its rows; the
@@ -554,33 +571,84 @@ class Imagen(nn.Module):
         if TIME_TABLE and not R:
             step_plan = eng.enable_time_table(coef, step_ptr) or step_plan
         zeros = lambda: torch.zeros_like(eng.x_in)
-        if share is not None:
-            assert not R, 'a shared sampler state does not cover the inpainting plan'
-            noise, final = share['noise'], share['final']
-        else:
-            noise, final = torch.empty_like(eng.x_in) if inject_noise else None, torch.empty_like(eng.x_in)
-        # (key / tables / scales / sibling: the cache key, the sampler's device tables, and — Imagen's guidance schedules — the per-step scales
-        # and the unguided sibling stage; None for every stage without a schedule, under both samplers)
-        return dict(eng=eng, step_plan=step_plan, plan=None, graph=None, coef=coef, step_ptr=step_ptr, seed_dev=seed_dev,
-                    key=key, tables=None, scales=None, sibling=None,
-                    n=eng.x_in[0].numel(), S=S, R=R, video=video, frames=frames, sample_offset=sample_offset,
-                    noise=noise, final=final,
+        # (x: the image the sampler steps.  scales / sibling: Imagen's guidance schedules, None for every stage without one, under both samplers)
+        return dict(eng=eng, step_plan=step_plan, plan=None, graph=None, coef=coef, **state, x=eng.x_in,
+                    key=key, scales=None, sibling=None,
+                    n=n, S=S, R=R, video=video, frames=frames, sample_offset=sample_offset,
                     # inpainting: the known image (video: frame-major clip), normalised, at this stage's size; 1.0 where it is kept
                     known=zeros() if R else None, mask=zeros() if R else None,
                     noise_renoise=zeros() if R and inject_noise else None), True
 
+    def _step_tables(self, idx: int, device, *, solver: Optional[tuple], R: int, inject_noise: bool, guidance: Optional[torch.Tensor]) -> list:
+        """The device tables of a stage of this sampler, the step table (`coef`) first: the ancestral step's, inpainting's three, or a
+        solver's two — for 'dpmpp_2m' followed by the one row (1, 0, ...) its history copy reads."""
+        sched = self.noise_schedulers[idx]
+        if solver is not None:
+            host = sched.solver_coefficients(*solver, philox=not inject_noise)
+        else:
+            host = sched.inpaint_coefficients(R, philox=not inject_noise) if R else (sched.step_coefficients(),)
+        if guidance is not None:
+            host[0][:, 7] = guidance                     # column 7, the pad slot of the step table: read by CFG_X0 (cfg = 2) alone
+        tables = [t.to(device) for t in host]
+        if solver is not None and solver[0] == 'dpmpp_2m':
+            tables.append(torch.tensor([[1., 0., 0., 0., 0., 0., 0., 0.]], device=device))
+        return tables
+
+    def _emit_step(self, plan: Plan, st: dict, idx: int, *, cfg: int, cond_scale: float, inject_noise: bool) -> dict:
+        """One sampling step of stage `st`, on the sampler state it holds, into `plan`:
+
+            [inpaint.blend]  eng.step_plan  CFG_X0  [QUANTILE]  update  [dpmpp_2m.history]  [inpaint.renoise]
+
+        The update is the DDPM_UPDATE launch, or — st['solver'] = (sampler, steps, eta) — one LINCOMB x = w0 x + w1 thr(x0) + w3 x0_prev
+        (+ the noise term of 'ddim' at eta > 0), which also emits thr(x0) (`thr1_out`: the next step's self-conditioning input and, for
+        'dpmpp_2m', the history) and the unnormalised image (`final_out`, rewritten every step: the last one's is the stage's).
+        'dpmpp_2m' hands thr(x0) to `x0_prev` with a second LINCOMB used as a copy — LINCOMB forbids thr1_out aliasing an input of its own
+        launch — so that ONE captured graph serves every step.  Allocates only the scratch of these launches, private to the plan."""
+        eng, n, R, solver, tables, coef, step_ptr, seed_dev = (st[k] for k in ('eng', 'n', 'R', 'solver', 'tables', 'coef', 'step_ptr', 'seed_dev'))
+        B, device = eng.src_batch, coef.device
+        x0, absx0 = (torch.empty(B, n, device=device) for _ in range(2))
+        quant = torch.empty(B, device=device)
+        scratch = torch.empty(B * ops.ENUMS["IMAGEN_QUANTILE_SCRATCH_WORDS"], dtype=torch.int32, device=device)
+        noise_blend = None
+        if R:
+            noise_blend = torch.zeros_like(eng.x_in) if inject_noise else None
+            ops.lincomb(plan, st['known'], eng.x_in, tables[1], step_ptr, B=B, n_per_sample=n, t1=noise_blend, mask=st['mask'], mask_else=eng.x_in,
+                        stream_id=idx | 0x100, sample_offset=st['sample_offset'], seed_ptr=seed_dev, label="inpaint.blend")
+        plan.extend(st['step_plan'])
+        ops.cfg_x0(plan, eng.x_in, eng.out, coef, step_ptr, x0, absx0, B=B, n_per_sample=n, cfg=cfg, cond_scale=float(cond_scale),
+                   objective=self.pred_objectives[idx])
+        dyn = bool(self.dynamic_thresholding[idx])
+        if dyn:
+            ops.quantile(plan, absx0, quant, scratch, B=B, n=n, q=float(self.dynamic_thresholding_percentile))
+        if getattr(self.unets[idx], 'self_cond', False):     # ip.py:2249: each step conditions on the previous step's thresholded x0
+            eng.bind_self_cond(st['x0_thr'])
+        if solver is not None:
+            sampler, _, eta = solver
+            # 'dpmpp_2m', the history: x0_prev enters the update as t3 (already thresholded: thr(.) with no quantile is the identity on
+            # [-1, 1]), and receives this step's thr(x0) from a copy launch (weights (1, 0, ...) of row 0 of a table of its own)
+            ops.lincomb(plan, eng.x_in, eng.x_in, tables[1], step_ptr, B=B, n_per_sample=n, t1=x0, q1=quant if dyn else None,
+                        t2=st['noise'] if eta > 0. else None, t3=st['x0_prev'], thr_mode=1 if dyn else 2, thr1_out=st['x0_thr'], final=True,
+                        final_out=st['final'], advance=True, stream_id=idx, sample_offset=st['sample_offset'], seed_ptr=seed_dev,
+                        label=f"{sampler}.update")
+            if sampler == 'dpmpp_2m':
+                zero_ptr = torch.zeros(1, dtype=torch.int32, device=device)
+                ops.lincomb(plan, st['x0_thr'], st['x0_prev'], tables[2], zero_ptr, B=B, n_per_sample=n, label="dpmpp_2m.history")
+        else:
+            ops.ddpm_update(plan, eng.x_in, x0, quant if dyn else None, coef, st['noise'], st['final'], step_ptr, B=B, n_per_sample=n,
+                            dynamic_threshold=dyn, total_steps=st['T'] * max(R, 1), seed=0, stream_id=idx, sample_offset=st['sample_offset'],
+                            seed_ptr=seed_dev, advance=not R, x0_thr=st['x0_thr'], row_keys=None if inject_noise else st['row_keys'])
+        if R:
+            ops.lincomb(plan, eng.x_in, eng.x_in, tables[2], step_ptr, B=B, n_per_sample=n, t1=st['noise_renoise'], advance=True,
+                        stream_id=idx | 0x200, sample_offset=st['sample_offset'], seed_ptr=seed_dev, label="inpaint.renoise")
+        return dict(quant=quant, x0=x0, noise_blend=noise_blend)
+
     def _build_stage(self, idx: int, B: int, device, *, cond_scale: float, with_text: bool, inject_noise: bool, sample_offset: int,
                      resample_times: int = 0, frames: int = 0, prompt_frames: tuple = (0, 0), size=None, solver: Optional[tuple] = None,
-                     guidance: Optional[torch.Tensor] = None, share: Optional[dict] = None):
-        """Build (or fetch) the per-timestep plan + graph of stage `idx` for batch B, at image_sizes[idx] or at `size` (an int, or (H, W)).
+                     guidance: Optional[torch.Tensor] = None):
+        """Build (or fetch) the per-timestep plan + graph of stage `idx` for batch B, at image_sizes[idx] or at `size` (an int, or (H, W)):
+        form the key, get or make the stage (`_new_stage`), emit its step (`_emit_step`), file it.
 
-        solver = (sampler, steps, eta) selects a few-step solver in place of the ancestral step: the tables are those of
-        `solver_coefficients` on a grid of `steps` steps, and after CFG_X0 / QUANTILE the update is one LINCOMB launch
-        x = w0 x + w1 thr(x0) + w3 x0_prev (+ the noise term of 'ddim' at eta > 0), which also emits thr(x0) (`thr1_out`: the next step's
-        self-conditioning input and, for 'dpmpp_2m', the history) and the unnormalised image (`final_out`, rewritten every step: the last
-        one's is the stage's).  'dpmpp_2m' hands thr(x0) to `x0_prev` with a second LINCOMB used as a copy — LINCOMB forbids thr1_out
-        aliasing an input of its own launch — so that ONE captured graph serves every step.
-
+        solver = (sampler, steps, eta): a few-step solver on the tables of `solver_coefficients` over a grid of `steps` steps.
         resample_times = R > 0 selects the inpainting plan (ip.py:2237-2275): the device counter then counts INNER iterations
         (timestep i, resample r = R-1..0), every coefficient table has one row per inner iteration, and one launch sequence
         [blend known pixels at level t -> denoiser -> posterior step -> re-noise t_next -> t] serves all of them: the re-noising
@@ -589,100 +657,42 @@ class Imagen(nn.Module):
         guidance = the fp32 [T] guidance scales of a schedule that varies (Imagen._resolve_guidance): the stage is the
         guided one (2B rows) with CFG_X0 at cfg = 2, which reads the step's scale from column 7 of the step table; `cond_scale` is not
         used.  Where the schedule has steps at exactly 1 — outside a guidance interval — st['sibling'] is the stage `cond_scale = 1`
-        builds (B rows, cfg = 0), built here with share = this stage: it runs on this stage's sampler state (x, step counter, tables,
-        seed words, self-conditioning / history / noise / output buffers) and `_run_stage` replays it on those steps."""
-        unet = self.unets[idx]
+        builds (B rows, cfg = 0), made here with share = this stage: it runs on this stage's sampler state (SHARED_STATE and the engine's
+        x / low-res image) and `_run_stage` replays it on those steps."""
         sched = self.noise_schedulers[idx]
         T, R = sched.num_timesteps if solver is None else solver[1], resample_times
         assert solver is None or not R, 'the solvers do not cover inpainting'
-        assert guidance is None or (share is None and not R and tuple(guidance.shape) == (T,) and guidance.dtype == torch.float32)
-        assert share is None or (cond_scale == 1. and not R)
-        cfg = 2 if guidance is not None else int(cond_scale != 1.)
+        assert guidance is None or (not R and tuple(guidance.shape) == (T,) and guidance.dtype == torch.float32)
         size = self.image_sizes[idx] if size is None else size
-        key = (idx, B, size, str(device), float(cond_scale), with_text, inject_noise, sample_offset, self.dynamic_thresholding[idx],
-               self.pred_objectives[idx], self.dynamic_thresholding_percentile, resample_times, frames, prompt_frames, self._lane, solver)
-        if guidance is not None:                         # (a call without a schedule keeps the key it always had)
-            key += (('guidance', guidance.numpy().tobytes()),)
-        if share is not None:
-            key += (('shares', share['key']),)
-        tables = []
+        two = solver is not None and solver[0] == 'dpmpp_2m'
+        buffers = ('x0_thr',) * bool(two or getattr(self.unets[idx], 'self_cond', False)) + ('x0_prev',) * two
+        key_at = lambda scale: (idx, B, size, str(device), float(scale), with_text, inject_noise, sample_offset, self.dynamic_thresholding[idx],
+                                self.pred_objectives[idx], self.dynamic_thresholding_percentile, resample_times, frames, prompt_frames,
+                                self._lane, solver)
 
-        def coef():
-            if share is not None:                        # the tables of the stage whose state this one runs on, the very tensors
-                tables[:] = share['tables']
-                return tables[0]
-            if solver is not None:
-                host = sched.solver_coefficients(*solver, philox=not inject_noise)
-            else:
-                host = sched.inpaint_coefficients(R, philox=not inject_noise) if R else (sched.step_coefficients(),)
-            if guidance is not None:
-                host[0][:, 7] = guidance                 # column 7, the pad slot of the step table: read by CFG_X0 (cfg = 2) alone
-            tables[:] = [t.to(device) for t in host]
-            return tables[0]
+        def stage(key, cfg, scale, scales=None, share=None):
+            st, built = self._new_stage(key, idx, B, device, cfg=bool(cfg), with_text=with_text, inject_noise=inject_noise, sample_offset=sample_offset,
+                                        resample_times=R, frames=frames, prompt_frames=prompt_frames, size=size, buffers=buffers, share=share,
+                                        tables=functools.partial(self._step_tables, idx, device, solver=solver, R=R, inject_noise=inject_noise,
+                                                                 guidance=guidance))
+            if built:
+                # ('dpmpp_2m': the first step of a run has no history: its row is first order, wherever skip_steps starts the run — _rewind)
+                st.update(plan=Plan(f"stage{idx}-step"), T=T, solver=solver, scales=scales, weights=st['tables'][1] if solver is not None else None,
+                          weights_at=(lambda start: sched.solver_coefficients(*solver, philox=not inject_noise, start=start)[1]) if two else None,
+                          weights_start=0)
+                st.update(self._emit_step(st['plan'], st, idx, cfg=cfg, cond_scale=scale, inject_noise=inject_noise))
+                self._stages[key] = st
+            return st, built
 
-        st, built = self._new_stage(key, idx, B, device, cfg=bool(cfg), with_text=with_text, inject_noise=inject_noise, sample_offset=sample_offset,
-                                    resample_times=R, frames=frames, prompt_frames=prompt_frames, coef=coef, size=size, share=share)
-        if not built:
-            return st
-        eng, n, coef, step_ptr, seed_dev, noise = st['eng'], st['n'], st['coef'], st['step_ptr'], st['seed_dev'], st['noise']
-        # (Philox key lo, hi, global sample index, 0) of every row: _run_stage fills it per call
-        row_keys = torch.zeros(B, 4, dtype=torch.int32, device=device) if share is None else share['row_keys']
-        x0 = torch.empty(B, n, device=device)
-        absx0 = torch.empty(B, n, device=device)
-        quant = torch.empty(B, device=device)
-        scratch = torch.empty(B * ops.ENUMS["IMAGEN_QUANTILE_SCRATCH_WORDS"], dtype=torch.int32, device=device)
-        plan = Plan(f"stage{idx}-step")
-        noise_blend = None
-        if R:
-            noise_blend = torch.zeros_like(eng.x_in) if inject_noise else None
-            ops.lincomb(plan, st['known'], eng.x_in, tables[1], step_ptr, B=B, n_per_sample=n, t1=noise_blend, mask=st['mask'], mask_else=eng.x_in,
-                        stream_id=idx | 0x100, sample_offset=sample_offset, seed_ptr=seed_dev, label="inpaint.blend")
-        plan.extend(st['step_plan'])
-        ops.cfg_x0(plan, eng.x_in, eng.out, coef, step_ptr, x0, absx0, B=B, n_per_sample=n, cfg=cfg, cond_scale=float(cond_scale),
-                   objective=self.pred_objectives[idx])
-        dyn = bool(self.dynamic_thresholding[idx])
-        if dyn:
-            ops.quantile(plan, absx0, quant, scratch, B=B, n=n, q=float(self.dynamic_thresholding_percentile))
-        x0_thr = None
-        if getattr(unet, 'self_cond', False):            # ip.py:2249: each step conditions on the previous step's thresholded x0
-            x0_thr = torch.zeros(B, n, device=device) if share is None else share['x0_thr']    # (video: the frame-major clip, as the state)
-            eng.bind_self_cond(x0_thr)
-        x0_prev = weights_at = None
-        if solver is not None:
-            sampler, _, eta = solver
-            two = sampler == 'dpmpp_2m'
-            if two:
-                # the history: x0_prev enters the update as t3 (already thresholded: thr(.) with no quantile is the identity on [-1, 1]),
-                # and receives this step's thr(x0) from a copy launch (weights (1, 0, ...) of row 0 of a table of its own)
-                x0_prev = torch.zeros(B, n, device=device) if share is None else share['x0_prev']
-                x0_thr = x0_thr if x0_thr is not None else torch.zeros(B, n, device=device) if share is None else share['x0_thr']
-            ops.lincomb(plan, eng.x_in, eng.x_in, tables[1], step_ptr, B=B, n_per_sample=n, t1=x0, q1=quant if dyn else None,
-                        t2=noise if eta > 0. else None, t3=x0_prev, thr_mode=1 if dyn else 2, thr1_out=x0_thr, final=True, final_out=st['final'],
-                        advance=True, stream_id=idx, sample_offset=sample_offset, seed_ptr=seed_dev, label=f"{sampler}.update")
-            if two:
-                if share is None:
-                    tables.append(torch.tensor([[1., 0., 0., 0., 0., 0., 0., 0.]], device=device))
-                zero_ptr = torch.zeros(1, dtype=torch.int32, device=device)
-                ops.lincomb(plan, x0_thr, x0_prev, tables[2], zero_ptr, B=B, n_per_sample=n, label="dpmpp_2m.history")
-                # the first step of a run has no history: its row is first order, wherever skip_steps starts the run (_run_stage)
-                weights_at = lambda start: sched.solver_coefficients(*solver, philox=not inject_noise, start=start)[1]
-        else:
-            ops.ddpm_update(plan, eng.x_in, x0, quant if dyn else None, coef, noise, st['final'], step_ptr, B=B, n_per_sample=n,
-                            dynamic_threshold=dyn, total_steps=T * max(R, 1), seed=0, stream_id=idx, sample_offset=sample_offset,
-                            seed_ptr=seed_dev, advance=not R, x0_thr=x0_thr, row_keys=None if inject_noise else row_keys)
-        if R:
-            ops.lincomb(plan, eng.x_in, eng.x_in, tables[2], step_ptr, B=B, n_per_sample=n, t1=st['noise_renoise'], advance=True,
-                        stream_id=idx | 0x200, sample_offset=sample_offset, seed_ptr=seed_dev, label="inpaint.renoise")
-        st.update(plan=plan, T=T, row_keys=row_keys, quant=quant, x0=x0, x0_thr=x0_thr, noise_blend=noise_blend, solver=solver,
-                  x0_prev=x0_prev, weights=tables[1] if solver is not None else None, weights_at=weights_at, weights_start=0,
-                  tables=tables, scales=None if guidance is None else [float(v) for v in guidance])
-        self._stages[key] = st
-        if guidance is not None and 1. in st['scales']:
-            st['sibling'] = self._build_stage(idx, B, device, cond_scale=1., with_text=with_text, inject_noise=inject_noise, sample_offset=sample_offset,
-                                              frames=frames, prompt_frames=prompt_frames, size=size, solver=solver, share=st)
+        if guidance is None:
+            return stage(key_at(cond_scale), int(cond_scale != 1.), cond_scale)[0]
+        key = key_at(cond_scale) + (('guidance', guidance.numpy().tobytes()),)   # (a call without a schedule keeps the key it always had)
+        st, built = stage(key, 2, cond_scale, scales=[float(v) for v in guidance])
+        if built and 1. in st['scales']:
+            st['sibling'] = stage(key_at(1.) + (('shares', key),), 0, 1., share=st)[0]
         return st
 
-    # ---- what both samplers' `_run_stage` share
+    # ---- the run loop of both samplers, and what they put into it
     @staticmethod
     def _draw(st, noise_fn, tag, like):
         """Injected Gaussian draw for the internal buffer `like`; videos are drawn in the reference's (b, c, f, h, w) layout."""
@@ -705,85 +715,98 @@ class Imagen(nn.Module):
             out = torch.where(st['mask'] != 0, (st['known'] + 1) * 0.5, out)
         return out
 
+    def _rewind(self, st, skip: int, init_images):
+        """The sampler state behind the fresh x_T ~ N(0, I), for a run that starts at timestep `skip`."""
+        if init_images is not None:
+            st['x'].add_(init_images)                   # ip.py:2205-2206
+        if st['x0_thr'] is not None:
+            st['x0_thr'].zero_()                        # no x0 estimate yet: the first step self-conditions on zeros (ip.py:2210, 1542)
+        if st['x0_prev'] is not None:                   # 'dpmpp_2m': no history yet, and the run's first row is first order
+            st['x0_prev'].zero_()
+            if st['weights_start'] != skip:
+                st['weights'].copy_(st['weights_at'](skip))
+                st['weights_start'] = skip
+        st['step_ptr'].fill_(skip * max(st['R'], 1))    # ip.py:2228-2229: the skipped timesteps are simply never run
+
+    def _plans_of_steps(self, st, steps: range) -> list:
+        """(stage, 'plan' | 'last') of every step: the stage's one plan, but on the unguided steps of a guidance schedule (st['scales'], read
+        on the host) its B-row sibling's, which runs on the same state."""
+        return [(st['sibling'] if st['sibling'] is not None and st['scales'][i] == 1. else st, 'plan') for i in steps]
+
+    def _capture(self, st, plans: list, rewind: Callable, stream):
+        """Warm-up outside capture (sets kernel attributes) from the run's own row, then rewind and capture, for each plan the run launches."""
+        for s in ([st] if st['sibling'] is None else [s for s in (st, st['sibling']) if any(p[0] is s for p in plans)]):
+            if s['graph'] is None:
+                s['plan'].run()
+                rewind()
+                torch.cuda.synchronize()
+                s['graph'] = ops.Graph(s['plan'], stream)
+
+    def _draw_step_noise(self, st, draw: Callable, stage: int, i: int, r: int):
+        """The injected draws that precede inner iteration (i, r); the tags and their order are the contract of `noise_fn`."""
+        if st['R']:
+            st['noise_blend'].copy_(draw(("inpaint", stage, i, r), st['noise']))
+            st['noise'].copy_(draw(("step", stage, i, r), st['noise']))
+            if r > 0 and i < st['T'] - 1:                # the reference draws no re-noising sample otherwise (ip.py:2268)
+                st['noise_renoise'].copy_(draw(("renoise", stage, i, r), st['noise']))
+        elif st['solver'] is None or st['solver'][2] > 0.:          # (the deterministic solvers draw nothing after the initial image)
+            st['noise'].copy_(draw(("step", stage, i), st['noise']))
+
     @torch.no_grad()
     def _run_stage(self, st, *, noise_fn: Optional[Callable], stage: int, seed: int, use_graph: bool = True, use_tqdm: bool = False,
                       max_steps: Optional[int] = None, trace: Optional[list] = None, init_images: Optional[torch.Tensor] = None,
                       skip_steps: Optional[int] = None):
-        """ip.py:2167-2289 for one stage: x_T ~ N(0, I) (+ init_images), the ancestral steps from `skip_steps` on (each run
-        `inpaint_resample_times` times when st is an inpainting plan), clamp + unnormalise (done by the last step's kernel) and
-        the final paste of the known pixels.  A stage with a guidance schedule (st['scales']) that has unguided steps replays, on those,
-        its B-row sibling, which runs on the same state: which captured graph a step launches is read from the host-side vector."""
-        eng, plan, T, R = st['eng'], st['plan'], st['T'], st['R']
-        scales, sibling = st['scales'], st['sibling']
-        stage_of = (lambda i: st) if sibling is None else (lambda i: sibling if scales[i] == 1. else st)
-        B = eng.src_batch
+        """One stage under either sampler (ip.py:2167-2289, el.py:393-545): the initial noise (+ init_images), the steps from `skip_steps`
+        on (each run `inpaint_resample_times` times when st is an inpainting stage), clamp + unnormalise (done by the last step's kernel)
+        and the final paste of the known pixels.  What the samplers differ in: `_rewind` (the state at the start of a run),
+        `_plans_of_steps` (which captured plan a step replays), `_capture` (warm-up and capture), `_draw_step_noise` (the injected draws)."""
+        x, T, R, B = st['x'], st['T'], st['R'], st['eng'].src_batch
         stream = torch.cuda.current_stream()
         skip = skip_steps or 0
-        assert 0 <= skip < T, 'skip_steps must leave at least one timestep'
-        inner = max(R, 1)
-        init = None
+        assert 0 <= skip < T, f'skip_steps must leave at least one {self._step_noun}'
         spans = _seed_spans(seed, B, st['sample_offset'])
-        if noise_fn is None:
-            init = Plan("init-noise")
-            for sd, r0, cnt, i0 in spans:               # (one span per merged request: its own key, its own sample indices)
-                ops.randn(init, eng.x_in[r0:r0 + cnt], seed=sd, stream_id=stage, tag=TAG_INIT, sample_offset=i0)
+        assert not (R and len(spans) > 1), 'merged requests do not cover inpainting (its re-noising launches take one key per batch)'
         draw = functools.partial(self._draw, st, noise_fn)
+        if noise_fn is None:
+            init = Plan(self._plan_prefix + "init-noise")
+            for sd, r0, cnt, i0 in spans:               # (one span per merged request: its own key, its own sample indices)
+                ops.randn(init, x[r0:r0 + cnt], seed=sd, stream_id=stage, tag=TAG_INIT, sample_offset=i0)
 
-        def reset_state():
+        def rewind():
             if noise_fn is not None:
-                eng.x_in.copy_(draw(("init", stage), eng.x_in))
+                x.copy_(draw(("init", stage), x))
             else:
                 init.run()
-            if init_images is not None:
-                eng.x_in.add_(init_images)              # ip.py:2205-2206
-            if st['x0_thr'] is not None:
-                st['x0_thr'].zero_()                    # no x0 estimate yet: the first step self-conditions on zeros (ip.py:2210, 1542)
-            if st['x0_prev'] is not None:               # 'dpmpp_2m': no history yet, and the run's first row is first order
-                st['x0_prev'].zero_()
-                if st['weights_start'] != skip:
-                    st['weights'].copy_(st['weights_at'](skip))
-                    st['weights_start'] = skip
-            st['step_ptr'].fill_(skip * inner)          # ip.py:2228-2229: the skipped timesteps are simply never run
+            self._rewind(st, skip, init_images)
 
-        reset_state()
-        assert not (R and len(spans) > 1), 'merged requests do not cover inpainting (its re-noising launches take one key per batch)'
         st['seed_dev'].copy_(torch.tensor(self._seed_words(spans[0][0]), dtype=torch.int32))
-        keys = torch.zeros(B, 4, dtype=torch.int64)
-        for sd, r0, cnt, i0 in spans:
-            keys[r0:r0 + cnt, 0], keys[r0:r0 + cnt, 1] = self._seed_words(sd)
-            keys[r0:r0 + cnt, 2] = torch.arange(i0, i0 + cnt)
-        st['row_keys'].copy_(keys.to(torch.int32))
+        if st['row_keys'] is not None:
+            keys = torch.zeros(B, 4, dtype=torch.int64)
+            for sd, r0, cnt, i0 in spans:
+                keys[r0:r0 + cnt, 0], keys[r0:r0 + cnt, 1] = self._seed_words(sd)
+                keys[r0:r0 + cnt, 2] = torch.arange(i0, i0 + cnt)
+            st['row_keys'].copy_(keys.to(torch.int32))
         steps = T - skip if max_steps is None else min(T - skip, max_steps)
         it = range(skip, skip + steps)
-        for s in ([st] if sibling is None else [s for s in (st, sibling) if any(stage_of(i) is s for i in it)]):
-            if use_graph and s['graph'] is None:
-                s['plan'].run()                          # warm-up outside capture (sets kernel attributes), then rewind
-                reset_state()
-                torch.cuda.synchronize()
-                s['graph'] = ops.Graph(s['plan'], stream)
+        plans = self._plans_of_steps(st, it)
+        rewind()
+        if use_graph:
+            self._capture(st, plans, rewind, stream)
+        launches = [s[self._GRAPH_OF[p]].launch if use_graph else s[p].run for s, p in plans]
         if use_tqdm:
             try:
                 from tqdm.auto import tqdm
                 it = tqdm(it, desc='sampling loop time step', total=steps)
             except ImportError:
                 pass
-        for i in it:
-            for r in reversed(range(inner)):
+        for i, launch in zip(it, launches):
+            for r in reversed(range(max(R, 1))):
                 if noise_fn is not None:
-                    if R:
-                        st['noise_blend'].copy_(draw(("inpaint", stage, i, r), st['noise']))
-                        st['noise'].copy_(draw(("step", stage, i, r), st['noise']))
-                        if r > 0 and i < T - 1:          # the reference draws no re-noising sample otherwise (ip.py:2268)
-                            st['noise_renoise'].copy_(draw(("renoise", stage, i, r), st['noise']))
-                    elif st['solver'] is None or st['solver'][2] > 0.:      # (the deterministic solvers draw nothing after the initial image)
-                        st['noise'].copy_(draw(("step", stage, i), st['noise']))
-                if use_graph:
-                    stage_of(i)['graph'].launch()
-                else:
-                    stage_of(i)['plan'].run()
+                    self._draw_step_noise(st, draw, stage, i, r)
+                launch()
                 if trace is not None:
-                    trace.append(eng.x_in.clone())
-        return self._stage_output(st, eng.x_in, skip + steps == T)
+                    trace.append(x.clone())
+        return self._stage_output(st, x, skip + steps == T)
 
     # ---- the reference's step-level sampler methods (ip.py:2042-2289) ------------------------------------------------------
     # `sample()` below runs a whole stage as one captured graph per timestep and never calls these.  They are the reference's

@@ -181,6 +181,12 @@ def test_cascade_runs_through_the_interpreter(cpu_backend, sampler, which):
         assert sib["eng"].R == 2 and owner["eng"].R == 4 and sib["eng"].x_in is owner["eng"].x_in and sib["step_ptr"] is owner["step_ptr"]
         assert sib["coef"] is owner["coef"] and sib["seed_dev"] is owner["seed_dev"] and sib["final"] is owner["final"]
         assert sib["eng"].lowres_in is owner["eng"].lowres_in and sib["x0_prev"] is owner["x0_prev"] and sib["x0_thr"] is owner["x0_thr"]
+        # the whole sampler state, from the one list the driver keeps: the sibling holds the owner's very objects
+        assert {"step_ptr", "seed_dev", "row_keys", "noise", "final", "x0_thr", "x0_prev", "tables"} <= set(model.SHARED_STATE)
+        assert all(sib[k] is owner[k] for k in model.SHARED_STATE), [k for k in model.SHARED_STATE if sib[k] is not owner[k]]
+        assert all(owner[k] is not None for k in ("step_ptr", "seed_dev", "row_keys", "noise", "final", "tables"))
+        assert (owner["x0_prev"] is not None) == (owner["x0_thr"] is not None) == (sampler == "dpmpp_2m")
+        assert sib["weights"] is owner["weights"] and all(a is b for a, b in zip(sib["tables"], owner["tables"]))
         assert [l for _, s, l in sib["plan"].ops if l == "cfg_x0" and s.cfg == 0], "the sibling is the stage cond_scale = 1 builds"
 
 

@@ -5,11 +5,14 @@ conditioning, layout conversion — executed end to end with the kernel launcher
 Only test-side patches: `ops.Plan.run` and `ops.Graph` go to the interpreter, the few `torch.cuda` calls of the driver become
 no-ops, and imagen._SAMPLING_DEVICE_TYPES admits 'cpu'.  Nothing of this exists in the product, which has no CPU path; what it buys
 is that every line of the host-side sampling code is exercised without a GPU (the HIP kernels are covered by the -m gpu tests)."""
-import contextlib
 import os
+import sys
 
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import cpu_replay  # noqa: E402
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -18,63 +21,11 @@ def nerr(a, b):
     return float((a.float() - b.float()).norm() / b.float().norm())
 
 
-class _Stream:
-    device = torch.device("cpu")
-    cuda_stream = 0
-
-    def __init__(self, *a, **k):
-        pass
-
-    def synchronize(self):
-        pass
-
-    def wait_stream(self, other):
-        pass
-
-    def wait_event(self, ev):
-        pass
-
-
-class _Event:
-    def __init__(self, *a, **k):
-        pass
-
-    def record(self, stream=None):
-        pass
-
-
 @pytest.fixture()
-def cpu_backend(monkeypatch):
-    from imagen_pytorch_amd import imagen as imagen_mod
-    from imagen_pytorch_amd import ops
-    from imagen_pytorch_amd import unet as unet_mod
-    from plan_interp import Interpreter
-
-    it = Interpreter()
-    ops.KEEP_REFERENCE_WEIGHTS = True
-    monkeypatch.setattr(ops.Plan, "run", lambda self, stream=None: it.run(self))
-
-    class Graph:
-        def __init__(self, plan, stream):
-            self.plan = plan
-
-        def launch(self):
-            self.plan.run()
-
-    monkeypatch.setattr(ops, "Graph", Graph)
-    monkeypatch.setattr(imagen_mod, "_SAMPLING_DEVICE_TYPES", ("cuda", "cpu"))
-    monkeypatch.setattr(unet_mod, "_ENGINE_DEVICE_TYPES", ("cuda", "cpu"))
-    monkeypatch.setattr(torch.cuda, "Stream", _Stream)
-    monkeypatch.setattr(torch.cuda, "Event", _Event)
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: _Stream())
-    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
-    monkeypatch.setattr(torch.cuda, "device", lambda *a, **k: contextlib.nullcontext())
-    monkeypatch.setattr(torch.cuda, "stream", lambda *a, **k: contextlib.nullcontext())
-    try:
+def cpu_backend():
+    """tests/cpu_replay.py for the duration of a test (one that also takes `monkeypatch` names it after this fixture)."""
+    with cpu_replay.cpu_backend() as it:
         yield it
-    finally:
-        ops.KEEP_REFERENCE_WEIGHTS = False
-        ops.REFERENCE_WEIGHTS.clear()
 
 
 def _cascade(g, klass=None, **kw):

@@ -43,6 +43,18 @@ CASES = {
     "cond_images": ("cond_images", 0, {}),
 }
 DDPM_ONLY = ("cond_images",)
+# what the few-step solvers and the guidance schedules build (Imagen only): recorded after the table above, so that its entries keep their place.
+# A guidance vector with steps at exactly 1 also records its unguided sibling: `sibling.plan` and the sibling engine's `sibling.step`.
+LATER_CASES = {
+    "ddim": ("image", dict(solver=("ddim", T, 0.0))),
+    "ddim_eta": ("image", dict(solver=("ddim", T, 0.5))),
+    "dpmpp_2m": ("image", dict(solver=("dpmpp_2m", T, 0.0))),
+    "dpmpp_2m_self_cond": ("self_cond", dict(solver=("dpmpp_2m", T, 0.0))),
+    "dpmpp_2m_philox": ("image", dict(solver=("dpmpp_2m", T, 0.0), inject_noise=False)),
+    "guidance_ramp": ("image", dict(guidance=[3.0, 2.5, 2.0, 1.5])),
+    "guidance_interval": ("image", dict(guidance=[1.0, 3.0, 3.0, 1.0])),
+    "guidance_interval_dpmpp_2m": ("image", dict(guidance=[1.0, 3.0, 3.0, 1.0], solver=("dpmpp_2m", T, 0.0))),
+}
 
 
 def _load(name):
@@ -67,6 +79,29 @@ def _model(which: str, karras: bool):
     return model.eval()
 
 
+def _stage_records(out: dict, name: str, model, idx: int, kw: dict) -> None:
+    """Build stage `idx` of `model` dry, condition its engine(s) and file the records of its plans under `name`."""
+    if kw.get("guidance") is not None:
+        kw = {**kw, "guidance": torch.tensor(kw["guidance"], dtype=torch.float32)}
+    st = model._stage(idx, B, torch.device("cpu"), **{**DEFAULTS, **kw})
+    for prefix, s in ((name, st), (name + ".sibling", st.get("sibling"))):
+        if s is None:
+            continue
+        eng = s["eng"]
+        rows = eng.R
+        keep = torch.ones(rows, dtype=torch.bool)
+        keep[B:] = False
+        eng.set_conditioning(text_embeds=torch.zeros(B, TOKENS, 32), text_mask=None, keep=keep,
+                             lowres_noise_times=torch.full((B,), 0.2) if idx else None)
+        out[prefix + ".plan"] = rs.wired_records(s["plan"])
+        if "last" in s:
+            out[prefix + ".last"] = rs.wired_records(s["last"])
+        out[prefix + ".step"] = rs.wired_records(eng.step_plan)
+        if s is st:
+            for i, pl in enumerate(eng._last_static):
+                out[f"{name}.static{i}"] = rs.wired_records(pl)
+
+
 def snapshot() -> dict:
     """{"<sampler>.<case>.<plan>": [record, ...]}: `plan` (and `last` for Karras) of the stage, `step` and `static<i>` of its engine."""
     from imagen_pytorch_amd import engine, engine3d
@@ -80,22 +115,9 @@ def snapshot() -> dict:
             for case, (which, idx, kw) in CASES.items():
                 if sampler == "karras" and case in DDPM_ONLY:
                     continue
-                model = _model(which, sampler == "karras")
-                kw = {**DEFAULTS, **kw}
-                st = model._stage(idx, B, torch.device("cpu"), **kw)
-                eng = st["eng"]
-                rows = eng.R
-                keep = torch.ones(rows, dtype=torch.bool)
-                keep[B:] = False
-                eng.set_conditioning(text_embeds=torch.zeros(B, TOKENS, 32), text_mask=None, keep=keep,
-                                     lowres_noise_times=torch.full((B,), 0.2) if idx else None)
-                name = f"{sampler}.{case}"
-                out[name + ".plan"] = rs.wired_records(st["plan"])
-                if "last" in st:
-                    out[name + ".last"] = rs.wired_records(st["last"])
-                out[name + ".step"] = rs.wired_records(eng.step_plan)
-                for i, pl in enumerate(eng._last_static):
-                    out[f"{name}.static{i}"] = rs.wired_records(pl)
+                _stage_records(out, f"{sampler}.{case}", _model(which, sampler == "karras"), idx, kw)
+        for case, (which, kw) in LATER_CASES.items():
+            _stage_records(out, f"ddpm.{case}", _model(which, False), 0, kw)
     finally:
         engine.UnetEngine, engine3d.UnetEngine3D = saved
     return out
