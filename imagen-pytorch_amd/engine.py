@@ -28,7 +28,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .modules import CrossAttentionP, ParallelP, PixelShuffleUpsampleP, ResnetBlockP, TransformerBlockP
+from .modules import CrossAttentionP, ParallelP, ResnetBlockP, TransformerBlockP
 from .modules3d import Parallel3dP
 from .ops import ACT_GELU, ACT_SILU, LOG2E, OUT_NCHW_F32, OUT_PIXEL_SHUFFLE, Act, Plan
 
@@ -408,82 +408,123 @@ class UnetEngine:
         ops.scale_shift(plan, ss, W.f32("timemlp.gam", lambda: gam), W.get("timemlp.isc", lambda: isc.to(self.dev)),
                         W.get("timemlp.ish", lambda: ish.to(self.dev)), self.pa2, self.ps2)
 
-    def _build_step_plan(self) -> Plan:
-        u, R, (H, Wd), W = self.unet, self.R, self.HW, self.W
-        plan = Plan("unet-step")
-        self._plan = plan
-        # ---- input image (+ low-res conditioning image) -> fp16 NHWC, 8 channels
-        cin = u.channels * (2 if self.lowres else 1)
-        assert cin <= 8, "init conv packs the input image into 8 channels"
+    # ---- the traversal: ONE walk for the image and the video planner (ip.py:1562-1725; iv.py:1751-1941).  What differs between them is stated
+    # in the attributes and hooks below, whose versions here are the image path's; engine3d.UnetEngine3D overrides them, not the walk.
+    PLAN_NAME = "unet-step"
+    DOWN = dict(pre=0, init=1, blocks=2, attn=3, post=4)     # where a level's modules sit in its ModuleList (the reference's state_dict
+    UP = dict(init=0, blocks=1, attn=2, up=3)                # indices, which are also the op labels: `downs.{i}.4`, `ups.{i}.3`)
+    FINAL_SKIP_SCALE = 1.0   # the skip scale of final_res_block (its skip, if any, is the init conv's output: unscaled)
+
+    def _pack_inputs(self, plan):
+        """The input image (+ low-res conditioning image) -> fp16 NHWC, 8 channels; the self-conditioning input likewise."""
+        R, (H, Wd) = self.R, self.HW
         self.img = self.new(R, H, Wd, 8)
         self._pack_op = ops.pack_image(plan, self.x_in, self.lowres_in, self.img, brep=R // self.src_batch, label="pack_image")
         if self.self_cond_in is not None:
             self._self_cond_op = ops.pack_image(plan, self.self_cond_in, self.cond_in, self.cimg, brep=R // self.src_batch, label="pack_self_cond")
 
+    def _time_chain_args(self) -> dict:
+        return dict(replicas=1, split=SPLIT_STATIC, f32=TIME_CHAIN_F32)
+
+    def _stem(self, plan) -> Act:
+        x = self.new(self.R, *self.HW, self.lc["init_dim"])
+        self._init_conv(plan, x)
+        self.taps['init_conv'] = x
+        return x
+
+    def _level_attn(self, plan, x: Act, tb, name: str, f: int) -> Act:
+        return self._transformer(plan, x, tb, name, with_context=True)
+
+    def _level_temporal(self, plan, x: Act, lvl, idx: dict, name: str, f: int) -> Act:
+        """What follows a level's transformer on the video path: its temporal PEG and temporal attention.  Nothing here."""
+        return x
+
+    def _frames_down(self, plan, x: Act, lvl, i: int, f: int) -> tuple:
+        """(x, frames) behind the temporal downsampling of down level i (ahead of its `post`): as they came, on the image path."""
+        return x, f
+
+    def _frames_up(self, plan, x: Act, lvl, i: int, f: int) -> tuple:
+        """(x, frames) behind the temporal upsampling of up level i (ahead of its first block)."""
+        return x, f
+
+    def _mid(self, plan, x: Act, f: int) -> Act:
+        u = self.unet
+        x = self._resnet(plan, x, None, u.mid_block1, "mid_block1", with_cond=True)
+        if u.mid_attn is not None:
+            x = self._transformer(plan, x, u.mid_attn, "mid_attn", with_context=False)
+        return self._resnet(plan, x, None, u.mid_block2, "mid_block2", with_cond=True)
+
+    def _head(self, plan, x: Act):
+        self.taps['final_res'] = x
+        self._final_conv(plan, x)
+
+    def _build_step_plan(self) -> Plan:
+        u, R = self.unet, self.R
+        plan = Plan(self.PLAN_NAME)
+        self._plan = plan
+        assert u.channels * (2 if self.lowres else 1) <= 8, "init conv packs the input image into 8 channels"
+        self._pack_inputs(plan)
+
         # ---- time conditioning, the batched time MLPs and their scale / shift tables
         chain_begin = len(plan.ops)
-        self._emit_time_chain(plan, replicas=1, split=SPLIT_STATIC, f32=TIME_CHAIN_F32)
+        self._emit_time_chain(plan, **self._time_chain_args())
 
         # ---- conditioning K/V rows that depend on the timestep (filled after the traversal registers the sites)
         self._kv_dynamic_anchor = len(plan.ops)
         self._time_chain_ops = [st for _, st, label in plan.ops[chain_begin:] if label in self._TIME_CHAIN]
 
         # ---- U-net traversal
-        x = self.new(R, H, Wd, self.lc["init_dim"])
-        self._init_conv(plan, x)
-        self.taps['init_conv'] = x
+        D, U, f = self.DOWN, self.UP, self.F          # f: the current number of frames
+        x = self._stem(plan)
         init_res = x if u.init_conv_to_final_conv_residual else None      # ip.py:1568-1569 (buffers are never overwritten: no clone)
         if u.init_resnet_block is not None:
-            x = self._resnet(plan, x, None, u.init_resnet_block, "init_resnet", with_cond=False)
+            x = self._resnet(plan, x, None, u.init_resnet_block, "init_resnet", with_cond=False, f=f)
         hiddens: List[Act] = []
-        n_levels = len(self.lc["in_out"])
-        mem_eff = self.lc["memory_efficient"]
         for i, lvl in enumerate(u.downs):
-            pre, init_block, res_blocks, attn_block, post = lvl
-            if pre is not None:
-                x = self._downsample(plan, x, pre, f"downs.{i}.0")
-            x = self._resnet(plan, x, None, init_block, f"downs.{i}.1", with_cond=True)
-            for j, rb in enumerate(res_blocks):
-                x = self._resnet(plan, x, None, rb, f"downs.{i}.2.{j}", with_cond=False)
+            if lvl[D['pre']] is not None:
+                x = self._downsample(plan, x, lvl[D['pre']], f"downs.{i}.{D['pre']}")
+            x = self._resnet(plan, x, None, lvl[D['init']], f"downs.{i}.{D['init']}", with_cond=True, f=f)
+            for j, rb in enumerate(lvl[D['blocks']]):
+                x = self._resnet(plan, x, None, rb, f"downs.{i}.{D['blocks']}.{j}", with_cond=False, f=f)
                 hiddens.append(x)
-            if isinstance(attn_block, TransformerBlockP):
-                x = self._transformer(plan, x, attn_block, f"downs.{i}.3", with_context=True)
+            if not isinstance(lvl[D['attn']], nn.Identity):
+                x = self._level_attn(plan, x, lvl[D['attn']], f"downs.{i}.{D['attn']}", f)
+            x = self._level_temporal(plan, x, lvl, D, f"downs.{i}", f)
             hiddens.append(x)
             self.taps[f'down{i}'] = x
-            if post is not None:
-                x = self._downsample(plan, x, post, f"downs.{i}.4")
-        x = self._resnet(plan, x, None, u.mid_block1, "mid_block1", with_cond=True)
-        if u.mid_attn is not None:
-            x = self._transformer(plan, x, u.mid_attn, "mid_attn", with_context=False)
-        x = self._resnet(plan, x, None, u.mid_block2, "mid_block2", with_cond=True)
+            x, f = self._frames_down(plan, x, lvl, i, f)
+            if lvl[D['post']] is not None:
+                x = self._downsample(plan, x, lvl[D['post']], f"downs.{i}.{D['post']}")
+        x = self._mid(plan, x, f)
         self.taps['mid'] = x
         up_hiddens: List[Act] = []
         for i, lvl in enumerate(u.ups):
-            init_block, res_blocks, attn_block, upsample = lvl
-            x = self._resnet(plan, x, hiddens.pop(), init_block, f"ups.{i}.0", with_cond=True)
-            for j, rb in enumerate(res_blocks):
-                x = self._resnet(plan, x, hiddens.pop(), rb, f"ups.{i}.1.{j}", with_cond=False)
-            if isinstance(attn_block, TransformerBlockP):
-                x = self._transformer(plan, x, attn_block, f"ups.{i}.2", with_context=True)
+            x, f = self._frames_up(plan, x, lvl, i, f)
+            x = self._resnet(plan, x, hiddens.pop(), lvl[U['init']], f"ups.{i}.{U['init']}", with_cond=True, f=f)
+            for j, rb in enumerate(lvl[U['blocks']]):
+                x = self._resnet(plan, x, hiddens.pop(), rb, f"ups.{i}.{U['blocks']}.{j}", with_cond=False, f=f)
+            if not isinstance(lvl[U['attn']], nn.Identity):
+                x = self._level_attn(plan, x, lvl[U['attn']], f"ups.{i}.{U['attn']}", f)
+            x = self._level_temporal(plan, x, lvl, U, f"ups.{i}", f)
             up_hiddens.append(x)                                            # ip.py:1707
-            if isinstance(upsample, PixelShuffleUpsampleP):
-                x = self._upsample(plan, x, upsample, f"ups.{i}.3")
-            elif isinstance(upsample, nn.Sequential):
-                x = self._upsample_nearest_conv(plan, x, upsample, f"ups.{i}.3")
+            upsample = lvl[U['up']]
+            if isinstance(upsample, nn.Sequential):                         # `Upsample` (pixel_shuffle_upsample=False; the image path only)
+                x = self._upsample_nearest_conv(plan, x, upsample, f"ups.{i}.{U['up']}")
+            elif not isinstance(upsample, nn.Identity):
+                x = self._upsample(plan, x, upsample, f"ups.{i}.{U['up']}")
             self.taps[f'up{i}'] = x
-        assert not hiddens
+        assert not hiddens and f == self.F
         if getattr(u.upsample_combiner, 'enabled', False):
             x = self._combine_upsample_fmaps(plan, x, up_hiddens)
         if u.final_res_block is not None:   # with init_conv_to_final_conv_residual its input is cat(x, init conv output), unscaled (ip.py:1716-1720)
-            x = self._resnet(plan, x, init_res, u.final_res_block, "final_res_block", with_cond=False, skip_scale=1.0)
+            x = self._resnet(plan, x, init_res, u.final_res_block, "final_res_block", with_cond=False, skip_scale=self.FINAL_SKIP_SCALE, f=f)
         elif init_res is not None:          # no final resnet block: final_conv itself reads cat(x, init conv output[, lowres image]) — the two
             cat = self.new(R, x.H, x.W, x.C + init_res.C)      # feature tensors are joined first (two strided row copies), the image rides as x2
             for src, off in ((x, 0), (init_res, x.C)):
                 ops.rows_copy(plan, src.t, cat.t, B=1, rows=R * x.H * x.W, C=src.C, src_bs=0, src_rs=src.ld, dst_bs=0, dst_rs=cat.C,
                               src_off=src.off, dst_off=off, label="final_conv.cat")
             x = cat
-        self.taps['final_res'] = x
-        self._final_conv(plan, x)
+        self._head(plan, x)
 
         # ---- now that every attention site is known: the per-step conditioning K/V ops, spliced in before the traversal
         dyn = Plan("kv-dynamic")

@@ -25,15 +25,15 @@ frames [len(pre), len(pre) + Fx) — two strided row copies around the unchanged
 from __future__ import annotations
 
 import math
-from typing import List, Optional
+from typing import Optional
 
 import torch
 import torch.nn.functional as TF
 
 from . import ops
 from .engine import SIM_SCALE, UnetEngine, _pad_vec, _w2d
-from .modules3d import PixelShuffleUpsample3dP, TransformerBlock3dP
-from .ops import ACT_SILU, OUT_NCHW_F32, Act, Plan
+from .modules3d import TransformerBlock3dP
+from .ops import ACT_SILU, OUT_NCHW_F32, Act
 
 
 def _wb2d(mod):
@@ -130,14 +130,14 @@ class UnetEngine3D(UnetEngine):
         self.cimg.t.view(R, F, S, S, self.cimg.C).copy_(packed[:, None].expand(-1, F, -1, -1, -1))
 
     # ------------------------------------------------------------------------------------------ step plan
-    def _build_step_plan(self) -> Plan:
-        u, R, S, W, F = self.unet, self.R, self.S, self.W, self.F
-        plan = Plan("unet3d-step")
-        self._plan = plan
-        it = self.ignore_time
-        cin = u.channels * (2 if self.lowres else 1)
-        assert cin <= 8, "init conv packs the input frames into 8 channels"
-        Fx = self.Fx
+    # The traversal is engine.UnetEngine._build_step_plan; these are the video path's versions of its hooks (iv.py:1751-1941).
+    PLAN_NAME = "unet3d-step"
+    DOWN = dict(pre=0, init=1, blocks=2, attn=3, peg=4, tattn=5, tdown=6, post=7)
+    UP = dict(init=0, blocks=1, attn=2, peg=3, tattn=4, tup=5, up=6)
+    FINAL_SKIP_SCALE = None  # (no skip there: the value is inert, but it is a field of the launch record, which is pinned with the levels' scale)
+
+    def _pack_inputs(self, plan):
+        u, R, S, F, Fx = self.unet, self.R, self.S, self.F, self.Fx
         self.img = self.new(R * F, S, S, 8, zero=True)
         xin = self.x_in.view(self.src_batch * Fx, u.channels, S, S)
         lin = self.lowres_in.view(self.src_batch * Fx, u.channels, S, S) if self.lowres else None
@@ -161,42 +161,48 @@ class UnetEngine3D(UnetEngine):
                 ops.rows_copy(plan, self.img_x.t, self.fin2.t, B=R, rows=1, C=Fx * fr, src_bs=Fx * fr, src_rs=0, dst_bs=F * fr, dst_rs=0,
                               dst_off=self.Fpre * fr, label="place_lowres_frames")
 
-        # ---- time conditioning: the image Unet's (iv.py:1764-1781), one (scale, shift) row per frame, plain fp16 weights
-        self._emit_time_chain(plan, replicas=F, split=False, f32=TIME_CHAIN_F32)
-        self._kv_dynamic_anchor = len(plan.ops)
+    def _time_chain_args(self) -> dict:
+        """The image Unet's chain (iv.py:1764-1781), one (scale, shift) row per frame, plain fp16 weights."""
+        return dict(replicas=self.F, split=False, f32=TIME_CHAIN_F32)
 
-        # ---- traversal (iv.py:1751-1941)
-        f = F                                         # current number of frames
-        x = self._init_conv3d(plan)
-        if not it:
-            x = self._temporal_peg(plan, x, u.init_temporal_peg, "init_temporal_peg", f)
-            x = self._temporal_attn(plan, x, u.init_temporal_attn, "init_temporal_attn", f)
+    def _temporal(self, plan, x: Act, peg, tattn, peg_name: str, tattn_name: str, f: int, tap: str = None) -> Act:
+        """Temporal PEG, then temporal attention; nothing under `ignore_time`.  `tap`: the prefix of a tap after each."""
+        if self.ignore_time:
+            return x
+        x = self._temporal_peg(plan, x, peg, peg_name, f)
+        if tap:
+            self.taps[tap + '_peg'] = x
+        x = self._temporal_attn(plan, x, tattn, tattn_name, f)
+        if tap:
+            self.taps[tap + '_tattn'] = x
+        return x
+
+    def _stem(self, plan) -> Act:
+        u = self.unet
+        x = self._temporal(plan, self._init_conv3d(plan), u.init_temporal_peg, u.init_temporal_attn, "init_temporal_peg", "init_temporal_attn", self.F)
         self.taps['init'] = x
-        if u.init_resnet_block is not None:
-            x = self._resnet(plan, x, None, u.init_resnet_block, "init_resnet", with_cond=False, f=f)
-        hiddens: List[Act] = []
-        strides = self.lc["temporal_strides"]
-        n_levels = len(self.lc["in_out"])
-        for i, lvl in enumerate(u.downs):
-            pre, init_block, res_blocks, attn_block, peg, tattn, tdown, post = lvl
-            if pre is not None:
-                x = self._downsample(plan, x, pre, f"downs.{i}.0")
-            x = self._resnet(plan, x, None, init_block, f"downs.{i}.1", with_cond=True, f=f)
-            for j, rb in enumerate(res_blocks):
-                x = self._resnet(plan, x, None, rb, f"downs.{i}.2.{j}", with_cond=False, f=f)
-                hiddens.append(x)
-            if isinstance(attn_block, TransformerBlock3dP):
-                x = self._transformer3d(plan, x, attn_block, f"downs.{i}.3", f)
-            if not it:
-                x = self._temporal_peg(plan, x, peg, f"downs.{i}.4", f)
-                x = self._temporal_attn(plan, x, tattn, f"downs.{i}.5", f)
-            hiddens.append(x)
-            self.taps[f'down{i}'] = x
-            if tdown is not None and not it:
-                x = self._temporal_down(plan, x, tdown, f"downs.{i}.6", f)
-                f //= strides[i]
-            if post is not None:
-                x = self._downsample(plan, x, post, f"downs.{i}.7")
+        return x
+
+    def _level_attn(self, plan, x: Act, tb, name: str, f: int) -> Act:
+        return self._transformer3d(plan, x, tb, name, f)
+
+    def _level_temporal(self, plan, x: Act, lvl, idx: dict, name: str, f: int) -> Act:
+        return self._temporal(plan, x, lvl[idx['peg']], lvl[idx['tattn']], f"{name}.{idx['peg']}", f"{name}.{idx['tattn']}", f)
+
+    def _frames_down(self, plan, x: Act, lvl, i: int, f: int) -> tuple:
+        tdown = lvl[self.DOWN['tdown']]
+        if tdown is None or self.ignore_time:
+            return x, f
+        return self._temporal_down(plan, x, tdown, f"downs.{i}.{self.DOWN['tdown']}", f), f // self.lc["temporal_strides"][i]
+
+    def _frames_up(self, plan, x: Act, lvl, i: int, f: int) -> tuple:
+        tup = lvl[self.UP['tup']]
+        if tup is None or self.ignore_time:
+            return x, f
+        return self._temporal_up(plan, x, tup, f"ups.{i}.{self.UP['tup']}", f), f * self.lc["temporal_strides"][len(self.unet.ups) - 1 - i]
+
+    def _mid(self, plan, x: Act, f: int) -> Act:
+        u = self.unet
         self.taps['mid_in'] = x
         x = self._resnet(plan, x, None, u.mid_block1, "mid_block1", with_cond=True, f=f)
         self.taps['mid_block1'] = x
@@ -205,41 +211,11 @@ class UnetEngine3D(UnetEngine):
             y, _ = self._self_attn_out(plan, self._self_attn(plan, tok, u.mid_attn.fn, "mid_attn.fn", with_context=False), tok, u.mid_attn.fn, "mid_attn.fn")
             x = Act(y.t, x.B, x.H, x.W, x.C, x.C, x.H * x.W * x.C)
         self.taps['mid_attn'] = x
-        if not it:
-            x = self._temporal_peg(plan, x, u.mid_temporal_peg, "mid_temporal_peg", f)
-            self.taps['mid_peg'] = x
-            x = self._temporal_attn(plan, x, u.mid_temporal_attn, "mid_temporal_attn", f)
-            self.taps['mid_tattn'] = x
-        x = self._resnet(plan, x, None, u.mid_block2, "mid_block2", with_cond=True, f=f)
-        self.taps['mid'] = x
-        for i, lvl in enumerate(u.ups):
-            init_block, res_blocks, attn_block, peg, tattn, tup, upsample = lvl
-            lv = n_levels - 1 - i
-            if tup is not None and not it:
-                x = self._temporal_up(plan, x, tup, f"ups.{i}.5", f)
-                f *= strides[lv]
-            x = self._resnet(plan, x, hiddens.pop(), init_block, f"ups.{i}.0", with_cond=True, f=f)
-            for j, rb in enumerate(res_blocks):
-                x = self._resnet(plan, x, hiddens.pop(), rb, f"ups.{i}.1.{j}", with_cond=False, f=f)
-            if isinstance(attn_block, TransformerBlock3dP):
-                x = self._transformer3d(plan, x, attn_block, f"ups.{i}.2", f)
-            if not it:
-                x = self._temporal_peg(plan, x, peg, f"ups.{i}.3", f)
-                x = self._temporal_attn(plan, x, tattn, f"ups.{i}.4", f)
-            if isinstance(upsample, PixelShuffleUpsample3dP):
-                x = self._upsample(plan, x, upsample, f"ups.{i}.6")
-            self.taps[f'up{i}'] = x
-        assert not hiddens and f == F
-        if u.final_res_block is not None:
-            x = self._resnet(plan, x, None, u.final_res_block, "final_res_block", with_cond=False, f=f)
-        self._final_conv3d(plan, x)
+        x = self._temporal(plan, x, u.mid_temporal_peg, u.mid_temporal_attn, "mid_temporal_peg", "mid_temporal_attn", f, tap='mid')
+        return self._resnet(plan, x, None, u.mid_block2, "mid_block2", with_cond=True, f=f)
 
-        dyn = Plan("kv-dynamic")
-        self._emit_context_kv(dyn, self.c_time, rows_per_batch=self.ntt, k_row0_self=0, k_row0_cross=1, tag="dyn")
-        plan.ops[self._kv_dynamic_anchor:self._kv_dynamic_anchor] = dyn.ops
-        plan.keep.extend(dyn.keep)
-        plan._arr = None
-        return plan
+    def _head(self, plan, x: Act):
+        self._final_conv3d(plan, x)
 
     # ------------------------------------------------------------------------------------------ convolutions
     def _init_conv3d(self, plan) -> Act:

@@ -3,26 +3,34 @@
 
 STATUS: the parameter surface (this file, modules3d.py) is checked on CPU against the live reference's state_dict; the kernel
 plan is built by engine3d.py and checked on CPU through the plan interpreter against oracle/unet3d_oracle.py; the two kernels the
-video path adds (csrc/temporal.hip) and the whole path have NOT been run on a GPU yet — see DESIGN.md §8 NEXT-2.
+video path adds (csrc/temporal.hip), `forward` and both video samplers run on MI355X in tests/test_video_gpu.py (measurements:
+profiles/r0*_c5*) — see DESIGN.md §8 NEXT-2.
 As for `Unet`, there is no PyTorch fallback: `forward` needs libimagen_hip.so and a CUDA/HIP tensor.
+
+What it shares with `Unet` lives in unet.UnetBase; here are the reference's signature, the scope gates, the video levels (8 modules
+down, 7 up: a temporal PEG, a temporal attention and the temporal resampling behind each level's transformer) and the frame-major `_run`.
 """
 from __future__ import annotations
 
 import functools
 import operator
-from functools import partial
 
 import torch
 from torch import nn
 
-from .modules import Holder, PerceiverResamplerP, SinuPosEmbP
+from .modules import Holder
 from .modules3d import (Attention3dP, CrossEmbed3dP, Parallel3dP, PixelShuffleUpsample3dP, ResidualP, ResnetBlock3dP,
                         TemporalPixelShuffleUpsampleP, TransformerBlock3dP, conv_frames_p, downsample3d_p, temporal_attn_p,
                         temporal_downsample_p, temporal_peg_p)
-from .unet import DEFAULT_TEXT_EMBED_DIM, _cast_tuple, _guided_negative, _unsupported, check_negative_prompt
+from .unet import DEFAULT_TEXT_EMBED_DIM, UnetBase, _cast_tuple, _unsupported, check_negative_prompt
 
 
-class Unet3D(nn.Module):
+class Unet3D(UnetBase):
+    _CrossEmbed, _Conv, _Resnet, _Parallel = CrossEmbed3dP, staticmethod(conv_frames_p), ResnetBlock3dP, Parallel3dP
+    _downsample = staticmethod(downsample3d_p)
+    _PER_LEVEL = UnetBase._PER_LEVEL + ('temporal_strides',)
+    _NO_CPU_PATH = "imagen_pytorch_amd.Unet3D runs on MI355X through libimagen_hip.so only; there is no CPU path"
+
     def __init__(
         self,
         *,
@@ -75,13 +83,7 @@ class Unet3D(nn.Module):
         pixel_shuffle_upsample=True,
         resize_mode='nearest',
     ):
-        super().__init__()
-        assert attn_heads > 1, 'you need to have more than 1 attention head, ideally at least 4 or 8'
-
-        ctor_kwargs = dict(locals())
-        for drop in ('self', '__class__'):
-            ctor_kwargs.pop(drop, None)
-        self._locals = ctor_kwargs                                    # iv.py:1291-1293
+        super().__init__(locals())
 
         for name in ('use_linear_attn', 'use_linear_cross_attn'):
             if any(_cast_tuple(self._locals[name])):
@@ -97,196 +99,56 @@ class Unet3D(nn.Module):
             raise NotImplementedError(f"attn_dim_head = {attn_dim_head}: the attention kernels (temporal attention included) are built for head dims 64 "
                                       "(every README config) and 32 (the reference's Unet3DConfig default, configs.py:61-62)")
 
-        self.self_cond = self_cond
-        self.channels = channels
-        self.channels_out = channels_out if channels_out is not None else channels
-        init_channels = channels * (1 + int(lowres_cond) + int(self_cond))          # iv.py:1302
-        init_dim = init_dim if init_dim is not None else dim
-        self.has_cond_image = cond_images_channels > 0            # iv.py:1307-1310: extra input channels of the init conv
-        self.cond_images_channels = cond_images_channels
-        init_channels += cond_images_channels
-
-        self.init_conv = (CrossEmbed3dP(init_channels, kernel_sizes=init_cross_embed_kernel_sizes, dim_out=init_dim, stride=1)
-                          if init_cross_embed else conv_frames_p(init_channels, init_dim, init_conv_kernel_size, padding=init_conv_kernel_size // 2))
-
-        dims = [init_dim, *[dim * m for m in dim_mults]]
-        in_out = list(zip(dims[:-1], dims[1:]))
-        cond_dim = cond_dim if cond_dim is not None else dim
-        time_cond_dim = dim * 4 * (2 if lowres_cond else 1)
-        self.cond_dim, self.time_cond_dim = cond_dim, time_cond_dim
-
-        def time_nets():                                               # iv.py:1326-1369
-            hiddens = nn.Sequential(SinuPosEmbP(learned_sinu_pos_emb_dim), nn.Linear(learned_sinu_pos_emb_dim + 1, time_cond_dim), nn.SiLU())
-            cond = nn.Sequential(nn.Linear(time_cond_dim, time_cond_dim))
-            tokens = nn.Sequential(nn.Linear(time_cond_dim, cond_dim * num_time_tokens), nn.Identity())
-            return hiddens, cond, tokens
-
-        self.to_time_hiddens, self.to_time_cond, self.to_time_tokens = time_nets()
-        self.num_time_tokens = num_time_tokens
-        self.lowres_cond = lowres_cond
-        if lowres_cond:
-            self.to_lowres_time_hiddens, self.to_lowres_time_cond, self.to_lowres_time_tokens = time_nets()
-        self.norm_cond = nn.LayerNorm(cond_dim)
-
-        self.text_to_cond = None
-        if cond_on_text:
-            assert text_embed_dim is not None, 'text_embed_dim must be given to the unet if cond_on_text is True'
-            self.text_to_cond = nn.Linear(text_embed_dim, cond_dim)
-        self.cond_on_text = cond_on_text
-        self.attn_pool = (PerceiverResamplerP(dim=cond_dim, depth=2, dim_head=attn_dim_head, heads=attn_heads, num_latents=attn_pool_num_latents)
-                          if attn_pool_text else None)
-        self.max_text_len = max_text_len
-        self.null_text_embed = nn.Parameter(torch.randn(1, max_text_len, cond_dim))
-        self.null_text_hidden = nn.Parameter(torch.randn(1, time_cond_dim))
-        self.to_text_non_attn_cond = None
-        if cond_on_text:
-            self.to_text_non_attn_cond = nn.Sequential(nn.LayerNorm(cond_dim), nn.Linear(cond_dim, time_cond_dim), nn.SiLU(),
-                                                       nn.Linear(time_cond_dim, time_cond_dim))
-
-        attn_kwargs = dict(heads=attn_heads, dim_head=attn_dim_head)
-        num_layers = len(in_out)
-        temporal_peg = temporal_peg_p                                   # iv.py:1413-1416
-        temporal_attn = lambda d: temporal_attn_p(d, attn_heads, attn_dim_head, time_causal_attn, time_rel_pos_bias_depth)
         self.time_causal_attn, self.ff_time_token_shift = time_causal_attn, ff_time_token_shift
-
-        num_resnet_blocks = _cast_tuple(num_resnet_blocks, num_layers)
-        resnet = partial(ResnetBlock3dP, **attn_kwargs)
-        layer_attns = _cast_tuple(layer_attns, num_layers)
-        layer_attns_depth = _cast_tuple(layer_attns_depth, num_layers)
-        layer_cross_attns = _cast_tuple(layer_cross_attns, num_layers)
-        temporal_strides = _cast_tuple(temporal_strides, num_layers)
-        self.total_temporal_divisor = functools.reduce(operator.mul, temporal_strides, 1)
-        self._layer_cfg = dict(in_out=in_out, num_resnet_blocks=num_resnet_blocks, layer_attns=layer_attns, layer_attns_depth=layer_attns_depth,
-                               layer_cross_attns=layer_cross_attns, temporal_strides=temporal_strides, memory_efficient=memory_efficient,
-                               attend_at_middle=attend_at_middle, init_dim=init_dim, dim=dim)
-
-        self.init_resnet_block = (resnet(init_dim, init_dim, time_cond_dim=time_cond_dim, use_gca=use_global_context_attn)
-                                  if memory_efficient else None)
-        self.init_temporal_peg = temporal_peg(init_dim)
-        self.init_temporal_attn = temporal_attn(init_dim)
-        self.skip_connect_scale = 1. if not scale_skip_connection else (2 ** -0.5)
-
-        self.downs = nn.ModuleList([])
-        self.ups = nn.ModuleList([])
-        skip_connect_dims = []
-        tb = partial(TransformerBlock3dP, ff_mult=ff_mult, ff_time_token_shift=ff_time_token_shift, context_dim=cond_dim, **attn_kwargs)
-        for ind, ((dim_in, dim_out), n_blocks, l_attn, l_depth, l_cross, t_stride) in enumerate(
-                zip(in_out, num_resnet_blocks, layer_attns, layer_attns_depth, layer_cross_attns, temporal_strides)):   # iv.py:1449-1477
-            is_last = ind >= (num_layers - 1)
-            layer_cond_dim = cond_dim if l_cross else None
-            current_dim = dim_in
-            pre_downsample = None
-            if memory_efficient:
-                pre_downsample = downsample3d_p(dim_in, dim_out)
-                current_dim = dim_out
-            skip_connect_dims.append(current_dim)
-            post_downsample = None
-            if not memory_efficient:
-                post_downsample = downsample3d_p(current_dim, dim_out) if not is_last else Parallel3dP(dim_in, dim_out)
-            self.downs.append(nn.ModuleList([
-                pre_downsample,
-                resnet(current_dim, current_dim, cond_dim=layer_cond_dim, time_cond_dim=time_cond_dim),
-                nn.ModuleList([ResnetBlock3dP(current_dim, current_dim, time_cond_dim=time_cond_dim, use_gca=use_global_context_attn)
-                               for _ in range(n_blocks)]),
-                tb(dim=current_dim, depth=l_depth) if l_attn else nn.Identity(),
-                temporal_peg(current_dim),
-                temporal_attn(current_dim),
-                temporal_downsample_p(current_dim, stride=t_stride) if t_stride > 1 else None,
-                post_downsample,
-            ]))
-
-        mid_dim = dims[-1]                                              # iv.py:1481-1487
-        self.mid_block1 = ResnetBlock3dP(mid_dim, mid_dim, cond_dim=cond_dim, time_cond_dim=time_cond_dim)
-        self.mid_attn = ResidualP(Attention3dP(mid_dim, **attn_kwargs)) if attend_at_middle else None
-        self.mid_temporal_peg = temporal_peg(mid_dim)
-        self.mid_temporal_attn = temporal_attn(mid_dim)
-        self.mid_block2 = ResnetBlock3dP(mid_dim, mid_dim, cond_dim=cond_dim, time_cond_dim=time_cond_dim)
-
-        for ind, ((dim_in, dim_out), n_blocks, l_attn, l_depth, l_cross, t_stride) in enumerate(
-                zip(reversed(in_out), reversed(num_resnet_blocks), reversed(layer_attns), reversed(layer_attns_depth),
-                    reversed(layer_cross_attns), reversed(temporal_strides))):                                           # iv.py:1499-1519
-            is_last = ind == (num_layers - 1)
-            layer_cond_dim = cond_dim if l_cross else None
-            skip_connect_dim = skip_connect_dims.pop()
-            self.ups.append(nn.ModuleList([
-                resnet(dim_out + skip_connect_dim, dim_out, cond_dim=layer_cond_dim, time_cond_dim=time_cond_dim),
-                nn.ModuleList([ResnetBlock3dP(dim_out + skip_connect_dim, dim_out, time_cond_dim=time_cond_dim, use_gca=use_global_context_attn)
-                               for _ in range(n_blocks)]),
-                tb(dim=dim_out, depth=l_depth) if l_attn else nn.Identity(),
-                temporal_peg(dim_out),
-                temporal_attn(dim_out),
-                TemporalPixelShuffleUpsampleP(dim_out, stride=t_stride) if t_stride > 1 else None,
-                PixelShuffleUpsample3dP(dim_out, dim_in) if (not is_last or memory_efficient) else nn.Identity(),
-            ]))
-
+        self._build_front()
+        self.total_temporal_divisor = functools.reduce(operator.mul, self._layer_cfg['temporal_strides'], 1)
+        self.init_temporal_peg = temporal_peg_p(self._layer_cfg['init_dim'])                  # iv.py:1413-1416
+        self.init_temporal_attn = self._temporal_attn(self._layer_cfg['init_dim'])
+        self._build_levels()
         self.upsample_combiner = Holder()
         self.init_conv_to_final_conv_residual = False
-        self.final_res_block = ResnetBlock3dP(dim, dim, time_cond_dim=time_cond_dim, use_gca=True) if final_resnet_block else None
-        final_conv_dim_in = dim + (channels if lowres_cond else 0)
-        self.final_conv = conv_frames_p(final_conv_dim_in, self.channels_out, final_conv_kernel_size, padding=final_conv_kernel_size // 2)
-        nn.init.zeros_(self.final_conv.weight)                          # iv.py:1578
-        nn.init.zeros_(self.final_conv.bias)
-        self.resize_mode = resize_mode
-        self._engines = {}
+        self._build_tail(dim)
 
-    # ---- cascade plumbing (iv.py:1586-1634) -----------------------------------------------------------
-    def cast_model_parameters(self, *, lowres_cond, text_embed_dim, channels, channels_out, cond_on_text):
-        if (lowres_cond == self.lowres_cond and channels == self.channels and cond_on_text == self.cond_on_text
-                and text_embed_dim == self._locals['text_embed_dim'] and channels_out == self.channels_out):
-            return self
-        updated = dict(lowres_cond=lowres_cond, text_embed_dim=text_embed_dim, channels=channels, channels_out=channels_out,
-                       cond_on_text=cond_on_text)
-        return self.__class__(**{**self._locals, **updated})
+    def _temporal_attn(self, dim):
+        kw = self._locals
+        return temporal_attn_p(dim, kw['attn_heads'], kw['attn_dim_head'], kw['time_causal_attn'], kw['time_rel_pos_bias_depth'])
 
-    def to_config_and_state_dict(self):
-        return self._locals, self.state_dict()
+    def _level_modules(self, lvl: dict, dim_in: int, dim_out: int) -> list:
+        """[first block, blocks, transformer, temporal PEG, temporal attention] (iv.py:1471-1475, 1513-1517)."""
+        kw = self._locals
+        return [*self._level_blocks(lvl, dim_in, dim_out, bool(lvl['layer_cross_attns'])),
+                (TransformerBlock3dP(dim=dim_out, depth=lvl['layer_attns_depth'], ff_mult=kw['ff_mult'], ff_time_token_shift=kw['ff_time_token_shift'],
+                                     context_dim=self.cond_dim, **self._attn_kwargs) if lvl['layer_attns'] else nn.Identity()),
+                temporal_peg_p(dim_out),
+                self._temporal_attn(dim_out)]
 
-    @classmethod
-    def from_config_and_state_dict(klass, config, state_dict):
-        unet = klass(**config)
-        unet.load_state_dict(state_dict)
-        return unet
+    def _down_level(self, lvl, dim, pre, post):
+        t_stride = lvl['temporal_strides']
+        return [pre, *self._level_modules(lvl, dim, dim), temporal_downsample_p(dim, stride=t_stride) if t_stride > 1 else None, post]
+
+    def _build_mid(self, dim):                                          # iv.py:1481-1487
+        tcd = self.time_cond_dim
+        self.mid_block1 = ResnetBlock3dP(dim, dim, cond_dim=self.cond_dim, time_cond_dim=tcd)
+        self.mid_attn = ResidualP(Attention3dP(dim, **self._attn_kwargs)) if self._locals['attend_at_middle'] else None
+        self.mid_temporal_peg = temporal_peg_p(dim)
+        self.mid_temporal_attn = self._temporal_attn(dim)
+        self.mid_block2 = ResnetBlock3dP(dim, dim, cond_dim=self.cond_dim, time_cond_dim=tcd)
+
+    def _up_level(self, lvl, dim_cat, dim_out, upsample_to):
+        t_stride = lvl['temporal_strides']
+        return [*self._level_modules(lvl, dim_cat, dim_out),
+                TemporalPixelShuffleUpsampleP(dim_out, stride=t_stride) if t_stride > 1 else None,
+                PixelShuffleUpsample3dP(dim_out, upsample_to) if upsample_to is not None else nn.Identity()]
 
     # ---- execution ------------------------------------------------------------------------------------
     def engine(self, batch_rows: int, src_batch: int, frames: int, image_size: int, device, with_text: bool = True, ignore_time: bool = False,
                pre_frames: int = 0, post_frames: int = 0):
         from .engine3d import UnetEngine3D
 
-        from . import unet as _unet_mod
         device = torch.device(device)
-        if device.type not in _unet_mod._ENGINE_DEVICE_TYPES:       # ('cuda',) in the product; the CPU replay tests widen it
-            raise RuntimeError("imagen_pytorch_amd.Unet3D runs on MI355X through libimagen_hip.so only; there is no CPU path")
         key = (batch_rows, src_batch, frames, image_size, device.index or 0, bool(with_text), bool(ignore_time), pre_frames, post_frames)
-        eng = self._engines.get(key)
-        if eng is None or eng.stale():
-            eng = UnetEngine3D(self, batch_rows, src_batch, frames, image_size, device, with_text=with_text, ignore_time=ignore_time,
-                               pre_frames=pre_frames, post_frames=post_frames)
-            self._engines[key] = eng
-        return eng
-
-    def release_engines(self):
-        self._engines.clear()
-
-    def forward_with_cond_scale(self, *args, cond_scale=1., negative_text_embeds=None, negative_text_masks=None, negative_texts=None, **kwargs):
-        """iv.py:1636-1648 — the cond and null branches run as ONE 2B-row batch through the kernel plan.
-
-        Extension: negative_text_embeds (+ negative_text_masks, default any(embeds != 0, -1)) puts a second prompt on the null branch — the
-        result is neg + (pos - neg) * cond_scale with both branches evaluated at cond_drop_prob = 0.  A batch-1 negative prompt serves the
-        whole batch.  (`negative_texts` needs an encoder: Imagen.sample takes it; a bare unet has none.)
-
-        Prompt and negative prompt share one token axis, the longer one's.  One consequence for a call WITHOUT `text_mask` whose prompt is
-        the shorter of the two: the positions it is padded by are masked, so they become null_text_embed, where the same call without a
-        negative prompt leaves zero tokens from the prompt's end to max_text_len.  It is the result of passing text_mask = all ones over
-        the prompt's own tokens; pass a `text_mask` (Imagen.sample always derives one) and the conditional branch does not depend on
-        the negative prompt at all."""
-        _guided_negative(self, cond_scale, kwargs.get('text_embeds'), negative_texts, negative_text_embeds, negative_text_masks)
-        if cond_scale == 1:
-            return self.forward(*args, **kwargs)
-        kwargs.pop('cond_drop_prob', None)
-        both = self._run(*args, cfg=True, negative_text_embeds=negative_text_embeds, negative_text_mask=negative_text_masks, **kwargs)
-        b = both.shape[0] // 2
-        logits, null_logits = both[:b], both[b:]
-        return null_logits + (logits - null_logits) * cond_scale
+        return self._cached_engine(key, device, lambda: UnetEngine3D(self, batch_rows, src_batch, frames, image_size, device, with_text=with_text,
+                                                                     ignore_time=ignore_time, pre_frames=pre_frames, post_frames=post_frames))
 
     def forward(self, x, time, *, lowres_cond_img=None, lowres_noise_times=None, text_embeds=None, text_mask=None, cond_images=None,
                 cond_video_frames=None, post_cond_video_frames=None, self_cond=None, cond_drop_prob=0., ignore_time=False):
@@ -326,15 +188,7 @@ class Unet3D(nn.Module):
             eng.set_cond_images(cond_images)
         if self.self_cond:                           # None: zeros (iv.py:1674-1676); a unet built without self_cond ignores the argument
             eng.set_self_cond(None if self_cond is None else self_cond.float().permute(0, 2, 1, 3, 4))
-        if cfg:
-            keep = torch.cat((torch.ones(B, dtype=torch.bool), torch.zeros(B, dtype=torch.bool)))
-        elif cond_drop_prob == 0:
-            keep = torch.ones(B, dtype=torch.bool)
-        elif cond_drop_prob == 1:
-            keep = torch.zeros(B, dtype=torch.bool)
-        else:
-            keep = torch.rand(B) < (1 - cond_drop_prob)
-        eng.set_conditioning(text_embeds=text_embeds if with_text else None, text_mask=text_mask, keep=keep,
+        eng.set_conditioning(text_embeds=text_embeds if with_text else None, text_mask=text_mask, keep=self._keep_mask(B, cfg, cond_drop_prob),
                              lowres_noise_times=lowres_noise_times, negative_text_embeds=negative_text_embeds,
                              negative_text_mask=negative_text_mask)
         # the engine's image layout is frame-major (b, f, c, h, w): frames of one clip are consecutive NHWC images
