@@ -123,7 +123,12 @@ OP_STRUCT = {
     ENUMS["IMAGEN_OP_LINCTX"]: STRUCTS["ImagenLinCtxParams"],
     ENUMS["IMAGEN_OP_LINEAR_XATTN"]: STRUCTS["ImagenLinearXattnParams"],
 }
-STRUCT_KIND = {v: k for k, v in OP_STRUCT.items()}
+# The extension range of the header (ImagenExtOpKind): kinds added without an ABI bump.  A library built before one of them still loads — its
+# base range is whole — and `require_ext_op` refuses the kind when a plan first asks for it.
+EXT_OP_STRUCT = {
+    ENUMS["IMAGEN_OP_GUIDE_X0"]: STRUCTS["ImagenGuideX0Params"],
+}
+STRUCT_KIND = {v: k for k, v in {**OP_STRUCT, **EXT_OP_STRUCT}.items()}
 
 EXPORTED_SYMBOLS = [
     "imagen_abi_version", "imagen_last_error", "imagen_sizeof", "imagen_launch", "imagen_plan_run",
@@ -190,6 +195,17 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
             raise ImagenHipError(f"struct size mismatch for op kind {kind}: C {lib.imagen_sizeof(kind)} vs ctypes {ctypes.sizeof(st)}")
     _lib = lib
     return lib
+
+
+def require_ext_op(kind: int, what: str) -> None:
+    """An op kind of the extension range: the loaded library must know it, with the struct of this header."""
+    st = EXT_OP_STRUCT[kind]
+    have = load_library().imagen_sizeof(kind)
+    if have == 0:
+        raise ImagenHipError(f"{what}: {LIB_PATH} was built before op kind {kind} ({st.__name__}) existed; rebuild it "
+                             "(`python -c 'import __graft_entry__ as g; g.build()'`)")
+    if have != ctypes.sizeof(st):
+        raise ImagenHipError(f"{what}: struct size mismatch for op kind {kind}: C {have} vs ctypes {ctypes.sizeof(st)}; rebuild the library")
 
 
 def hip_runtime_copies() -> list:

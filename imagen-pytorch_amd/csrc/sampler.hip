@@ -32,6 +32,154 @@ __global__ __launch_bounds__(256) void cfg_x0_kernel(const ImagenCfgX0Params p) 
   p.absx0[i] = fabsf(x0);
 }
 
+// ---- GUIDE_X0: the guided x0 with per-sample statistics (guidance rescale | adaptive projected guidance), see ImagenGuideX0Params ----
+// Two launches of one kernel: phase 0 reduces each sample to four fp64 sums (a partial per workgroup, stored plainly: no floating-point
+// atomics), phase 1 adds a sample's partials in workgroup order — every workgroup the same order, so the result is bit-identical from run to
+// run — and applies them.  Both passes stream pred (2B n floats) once: memory-bound, the fp64 accumulation rides along for free and keeps the
+// variance (a difference of two sums of ~n terms) from cancelling.  A thread owns groups of 4 consecutive elements of ONE sample (16 bytes a
+// lane where VEC: n % 4 == 0 and 16-byte aligned buffers; else scalar accesses, the tail masked).
+constexpr int kGuideMaxBlocks = IMAGEN_GUIDE_MAX_BLOCKS;
+constexpr int kGuidePerBlock = 8192;   // elements of a sample per workgroup, as the quantile's
+
+__device__ __forceinline__ float guide_x0_of(float x, float eps, float alpha, float sigma, int objective) {   // CFG_X0's expressions
+  if (objective == 0) return (x - sigma * eps) / fmaxf(alpha, 1e-8f);
+  if (objective == 1) return eps;
+  return alpha * x - sigma * eps;
+}
+
+template <bool VEC>
+__device__ __forceinline__ void guide_load4(const float* row, int e0, int n, float v[4]) {
+  if (VEC) {
+    const f32x4 t = *reinterpret_cast<const f32x4*>(row + e0);
+    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = (e0 + e < n) ? row[e0 + e] : 0.f;
+  }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void guide_store4(float* row, int e0, int n, const float v[4]) {
+  if (VEC) {
+    *reinterpret_cast<f32x4*>(row + e0) = f32x4{v[0], v[1], v[2], v[3]};
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (e0 + e < n) row[e0 + e] = v[e];
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void guide_x0_kernel(const ImagenGuideX0Params p, int bps) {
+  __shared__ double s_red[4][256];
+  const int tid = threadIdx.x;
+  const int b = blockIdx.x / bps, blk = blockIdx.x % bps;
+  const int n = p.n_per_sample;
+  const size_t row0 = (size_t)b * n, total = (size_t)p.B * n;
+  const float* cf = p.coef + (size_t)(*p.step_ptr) * kCoefStride;
+  const float alpha = cf[0], sigma = cf[1];
+  const float s = p.cfg == 2 ? cf[7] : p.cond_scale;
+  const float* xr = p.x + row0;
+  const float* cr = p.pred + row0;             // cond rows first
+  const float* ur = p.pred + total + row0;     // null rows behind them
+  float* ar = p.avg ? p.avg + row0 : nullptr;
+  double* part = p.partials + (size_t)b * IMAGEN_GUIDE_PARTIAL_DOUBLES;
+  const bool apg = p.mode == IMAGEN_GUIDE_APG;
+  const bool need_x = apg && p.objective != 1;   // rescale: x enters only the apply pass
+  const float momentum = p.momentum;
+  const int groups = (int)(((size_t)n + 3) >> 2);
+  const int first = blk * 256 + tid, stride = bps * 256;
+
+  if (p.phase == 0) {
+    double a0 = 0., a1 = 0., a2 = 0., a3 = 0.;
+    for (int g = first; g < groups; g += stride) {
+      const int e0 = g * 4;
+      float c[4], u[4], x[4] = {0.f, 0.f, 0.f, 0.f}, av[4] = {0.f, 0.f, 0.f, 0.f};
+      guide_load4<VEC>(cr, e0, n, c);
+      guide_load4<VEC>(ur, e0, n, u);
+      if (need_x) guide_load4<VEC>(xr, e0, n, x);
+      if (apg && ar) guide_load4<VEC>(ar, e0, n, av);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (e0 + e >= n) break;
+        if (apg) {
+          const float dc = guide_x0_of(x[e], c[e], alpha, sigma, p.objective), du = guide_x0_of(x[e], u[e], alpha, sigma, p.objective);
+          float d = dc - du;
+          if (ar) d = d + momentum * av[e];
+          a0 += (double)d * (double)d;
+          a1 += (double)d * (double)dc;
+          a2 += (double)dc * (double)dc;
+        } else {
+          const float gd = u[e] + (c[e] - u[e]) * s;
+          a0 += (double)c[e];
+          a1 += (double)c[e] * (double)c[e];
+          a2 += (double)gd;
+          a3 += (double)gd * (double)gd;
+        }
+      }
+    }
+    s_red[0][tid] = a0; s_red[1][tid] = a1; s_red[2][tid] = a2; s_red[3][tid] = a3;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {   // a fixed tree: the same sum order on every run
+      if (tid < off) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s_red[k][tid] += s_red[k][tid + off];
+      }
+      __syncthreads();
+    }
+    if (tid < 4) part[blk * 4 + tid] = s_red[tid][0];
+    return;
+  }
+
+  // phase 1: the sample's sums, workgroup 0 first (uniform addresses: every thread reads the same few words out of L2)
+  double t0 = 0., t1 = 0., t2 = 0., t3 = 0.;
+  for (int k = 0; k < bps; ++k) {
+    t0 += part[k * 4 + 0]; t1 += part[k * 4 + 1]; t2 += part[k * 4 + 2]; t3 += part[k * 4 + 3];
+  }
+  float f0 = 1.f, f1 = 0.f;   // rescale: f0 = the factor;  APG: f0 = r, f1 = k
+  if (apg) {
+    double r = 1.;
+    if (p.norm_threshold > 0.f) r = fmin(1., (double)p.norm_threshold / sqrt(t0));
+    f0 = (float)r;
+    f1 = t2 > 0. ? (float)(r * t1 / t2) : 0.f;
+  } else {
+    const double dn = (double)n;   // divisions, not a reciprocal: a constant sample of dyadic values then has variance exactly 0
+    const double mc = t0 / dn, mg = t2 / dn;
+    const double vc = fmax(t1 / dn - mc * mc, 0.), vg = fmax(t3 / dn - mg * mg, 0.);
+    f0 = vg > 0. ? (float)sqrt(vc / vg) : 1.f;
+  }
+  const float phi = p.phi, eta = p.eta, sm1 = s - 1.0f;
+  for (int g = first; g < groups; g += stride) {
+    const int e0 = g * 4;
+    float c[4], u[4], x[4] = {0.f, 0.f, 0.f, 0.f}, av[4] = {0.f, 0.f, 0.f, 0.f}, o[4], oa[4];
+    guide_load4<VEC>(cr, e0, n, c);
+    guide_load4<VEC>(ur, e0, n, u);
+    if (p.objective != 1) guide_load4<VEC>(xr, e0, n, x);
+    if (apg && ar) guide_load4<VEC>(ar, e0, n, av);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float x0;
+      if (apg) {
+        const float dc = guide_x0_of(x[e], c[e], alpha, sigma, p.objective), du = guide_x0_of(x[e], u[e], alpha, sigma, p.objective);
+        float d = dc - du;
+        if (ar) d = d + momentum * av[e];
+        av[e] = d;
+        const float dp = f0 * d, par = f1 * dc;
+        x0 = dc + sm1 * ((dp - par) + eta * par);
+      } else {
+        const float gd = u[e] + (c[e] - u[e]) * s;
+        const float eps = phi == 0.0f ? gd : phi * (gd * f0) + (1.0f - phi) * gd;   // (phi == 0: CFG_X0's bits whatever f is)
+        x0 = guide_x0_of(x[e], eps, alpha, sigma, p.objective);
+      }
+      o[e] = x0;
+      oa[e] = fabsf(x0);
+    }
+    guide_store4<VEC>(p.x0 + row0, e0, n, o);
+    guide_store4<VEC>(p.absx0 + row0, e0, n, oa);
+    if (apg && ar) guide_store4<VEC>(ar, e0, n, av);
+  }
+}
+
 // ---- exact quantile: 4 x 8-bit MSB-first radix select on the (non-negative) float bit patterns ------------
 // scratch per sample (uint32): hist[4][256] | cnt_le | min_gt | unused...
 constexpr int kScratch = IMAGEN_QUANTILE_SCRATCH_WORDS;
@@ -313,6 +461,25 @@ int launch_cfg_x0(const ImagenCfgX0Params* p, hipStream_t s) {
   const size_t n = (size_t)p->B * p->n_per_sample;
   hipLaunchKernelGGL(cfg_x0_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, *p);
   return imagen_hip_status("cfg_x0");
+}
+
+int launch_guide_x0(const ImagenGuideX0Params* p, hipStream_t s) {
+  IMAGEN_CHECK(p->x && p->pred && p->coef && p->step_ptr && p->x0 && p->absx0 && p->partials, "guide_x0: x / pred / coef / step_ptr / x0 / absx0 / partials required");
+  IMAGEN_CHECK(p->B > 0 && p->n_per_sample > 0 && p->n_per_sample <= 0x7FFFFFF0, "guide_x0: B > 0, 0 < n_per_sample <= 2^31 - 16");
+  IMAGEN_CHECK(p->cfg == 1 || p->cfg == 2, "guide_x0: cfg is 1 (cond_scale) or 2 (the scale of the step's table row); an unguided step is CFG_X0's");
+  IMAGEN_CHECK(p->objective >= 0 && p->objective <= 2, "guide_x0: objective is 0 (noise), 1 (x_start) or 2 (v)");
+  IMAGEN_CHECK(p->mode == IMAGEN_GUIDE_RESCALE || p->mode == IMAGEN_GUIDE_APG, "guide_x0: mode is 1 (rescale) or 2 (projected guidance)");
+  IMAGEN_CHECK(p->phase == 0 || p->phase == 1, "guide_x0: phase is 0 (reduce) or 1 (apply)");
+  IMAGEN_CHECK(p->mode != IMAGEN_GUIDE_RESCALE || (p->phi >= 0.f && p->phi <= 1.f), "guide_x0: phi outside [0, 1]");
+  IMAGEN_CHECK(p->mode != IMAGEN_GUIDE_APG || p->momentum == 0.f || p->avg, "guide_x0: momentum needs the running average buffer");
+  IMAGEN_CHECK(((uintptr_t)p->partials & 7) == 0, "guide_x0: partials must be 8-byte aligned");
+  int bps = (p->n_per_sample + kGuidePerBlock - 1) / kGuidePerBlock;
+  if (bps > kGuideMaxBlocks) bps = kGuideMaxBlocks;
+  const uintptr_t align = (uintptr_t)p->x | (uintptr_t)p->pred | (uintptr_t)p->x0 | (uintptr_t)p->absx0 | (uintptr_t)p->avg;
+  const bool vec = p->n_per_sample % 4 == 0 && (align & 15) == 0;
+  if (vec) hipLaunchKernelGGL(guide_x0_kernel<true>, dim3((unsigned)(p->B * bps)), dim3(256), 0, s, *p, bps);
+  else hipLaunchKernelGGL(guide_x0_kernel<false>, dim3((unsigned)(p->B * bps)), dim3(256), 0, s, *p, bps);
+  return imagen_hip_status("guide_x0");
 }
 
 int launch_quantile(const ImagenQuantileParams* p, hipStream_t s) {

@@ -45,7 +45,9 @@ def sample_sharded(sample_fn: Callable[..., torch.Tensor], text_embeds: torch.Te
     Returns the full (B, C, H, W) batch on every rank (or the local shard if gather=False).
     A negative prompt (negative_text_embeds / negative_text_masks, or negative_texts: one string for all samples or one per sample) is
     sharded with its rows.  Every other keyword reaches `sample_fn` as given — the solver keywords `sampler=`, `sample_steps=`, `eta=`
-    among them: a stochastic solver's draws are keyed by the global sample index (`sample_offset`), as the ancestral sampler's are.
+    among them: a stochastic solver's draws are keyed by the global sample index (`sample_offset`), as the ancestral sampler's are; and the
+    guidance keywords (`guidance_schedule=`, `guidance_interval=`, `guidance_rescale=`, `guidance_apg=`): rescale and projected guidance take
+    their statistics per sample, so a shard's rows are guided as in the whole batch.
     """
     B = text_embeds.shape[0]
     if negative_texts is not None:

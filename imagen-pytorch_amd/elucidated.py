@@ -318,6 +318,8 @@ class ElucidatedImagen(Imagen):
         eta=None,
         guidance_schedule=None,                       # Imagen.sample's guidance keywords: refused here (ValueError)
         guidance_interval=None,
+        guidance_rescale=None,
+        guidance_apg=None,
     ):
         return self._sample(self._call(**{k: v for k, v in locals().items() if k != 'self'}))   # (the keywords, as given)
 
@@ -338,10 +340,20 @@ class ElucidatedImagen(Imagen):
                              f"guidance schedules and intervals belong to Imagen.sample")
         return None
 
+    def _guide_of(self, guidance_rescale=None, guidance_apg=None):
+        """Imagen._guide_of: refused, as the guidance keywords are.  The running average of projected guidance is a state per denoiser
+        evaluation of a first-order step; this sampler guides with the plain extrapolation at the fixed cond_scale."""
+        given = [k for k, v in (('guidance_rescale', guidance_rescale), ('guidance_apg', guidance_apg)) if v is not None]
+        if given:
+            raise ValueError(f"{', '.join(given)}: ElucidatedImagen evaluates the denoiser twice per step of its second-order sampler; "
+                             f"guidance rescale and projected guidance belong to Imagen.sample")
+        return None
+
     def _call(self, sigma_min=None, sigma_max=None, **kw):
         """Imagen._call; this sampler's two extra keywords become the record's per-unet `sigma_overrides`, which `_build_stage` takes."""
         self._solver_of(kw.get('sampler'), kw.get('sample_steps'), kw.get('eta'))
         self._guidance_of(kw.get('guidance_schedule'), kw.get('guidance_interval'))
+        self._guide_of(kw.get('guidance_rescale'), kw.get('guidance_apg'))
         n_unets = len(self.unets)
         over = None if sigma_min is None and sigma_max is None else dict(sigma_min=_cast_tuple(sigma_min, n_unets),
                                                                          sigma_max=_cast_tuple(sigma_max, n_unets))

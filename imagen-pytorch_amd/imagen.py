@@ -142,6 +142,8 @@ class _Call:
     eta: Any = None                                    # ... 'ddim' only, 0 (None: the same) .. 1
     guidance_schedule: Any = None                      # extension: the guidance scale per step, a callable f(t) | a sequence, one or per unet
     guidance_interval: Any = None                      # ... (t_lo, t_hi), one or per unet: the steps outside it run unguided — Imagen._guidance_of
+    guidance_rescale: Any = None                       # extension: phi of guidance rescale, one or per unet — Imagen._guide_of
+    guidance_apg: Any = None                           # ... dict(eta=, norm_threshold=, momentum=) of projected guidance, one or per unet
     # not public keywords: set by sample_requests, the sample_pipelined workers and ElucidatedImagen._call
     negative_rows: Optional[torch.Tensor] = None       # bool [rows]: the samples the merged negative prompt applies to
     pipelined_stage: bool = False                      # one stage of a cascade whose guidance scales sample_pipelined has checked as a whole
@@ -153,6 +155,7 @@ class _Call:
     neg_rows: Any = None
     solver: Any = None                                 # None (the ancestral sampler), or per unet (sampler, steps, eta)
     guidance: Any = None                               # per unet: None (cond_scale as it stands) | the fp32 [steps] scales of a schedule that varies
+    guide: Any = None                                  # None, or per unet: None | ('rescale', phi) | ('apg', eta, norm_threshold, momentum)
     sizes: Any = None                                  # per unet: image_sizes[i] (int, square), or (H, W) where image_shapes says H != W
     frames: int = 0                                    # video_frames of a video cascade, else 0
     known: Any = None                                  # inpainting: the normalised known image / clip (reference layout) and its mask
@@ -365,10 +368,12 @@ class Imagen(nn.Module):
         Not covered (raise): inpainting, init images, conditioning images / frames, `noise_fn`, `start_image_or_video`.  The solver keywords
         (`sampler=`, `sample_steps=`, `eta=`) are common ones; a stochastic solver (`eta > 0`) is refused: its update (LINCOMB) draws with one
         key per batch, and the deterministic ones draw nothing after the initial image, which carries every request's own key.  The guidance
-        keywords (`guidance_schedule=`, `guidance_interval=`) are common ones too, as `cond_scale=` is: inside a request they are refused."""
+        keywords (`guidance_schedule=`, `guidance_interval=`, `guidance_rescale=`, `guidance_apg=`) are common ones too, as `cond_scale=` is: inside
+        a request they are refused.  (Rescale and projected guidance take their statistics per row, so a merged row is guided as in its own call.)"""
         solver = self._solver_of(common.get('sampler'), common.get('sample_steps'), common.get('eta'))
         self._guidance_of(common.get('guidance_schedule'), common.get('guidance_interval'))
-        for k in ('guidance_schedule', 'guidance_interval'):
+        self._guide_of(common.get('guidance_rescale'), common.get('guidance_apg'))
+        for k in ('guidance_schedule', 'guidance_interval', 'guidance_rescale', 'guidance_apg'):
             if any(k in r for r in requests):
                 raise ValueError(f'sample_requests: {k} inside a request; merged requests run one plan, so it is a common keyword, as cond_scale is')
         if solver is not None and solver[0][2] > 0.:
@@ -435,9 +440,10 @@ class Imagen(nn.Module):
                 kw['seed'] = self._next_seed()
             kw.setdefault('use_tqdm', False)
             solver = self._solver_of(kw.get('sampler'), kw.get('sample_steps'), kw.get('eta'))   # refusals come before a thread starts
-            self._guidance_vectors(self._guidance_of(kw.get('guidance_schedule'), kw.get('guidance_interval')),
-                                   _cast_tuple(kw.get('cond_scale', 1.), n_stages), solver,
-                                   any(kw.get(k) is not None for k in ('inpaint_images', 'inpaint_videos', 'inpaint_masks')), 0, n_stages)
+            inpainting = any(kw.get(k) is not None for k in ('inpaint_images', 'inpaint_videos', 'inpaint_masks'))
+            vectors, scales = self._guidance_vectors(self._guidance_of(kw.get('guidance_schedule'), kw.get('guidance_interval')),
+                                                     _cast_tuple(kw.get('cond_scale', 1.), n_stages), solver, inpainting, 0, n_stages)
+            self._check_guide(self._guide_of(kw.get('guidance_rescale'), kw.get('guidance_apg')), scales, vectors, inpainting, 0, n_stages)
             jobs.append(kw)
         if n_stages == 1 or len(jobs) == 0:
             return [self.sample(**kw) for kw in jobs]
@@ -571,9 +577,10 @@ class Imagen(nn.Module):
         if TIME_TABLE and not R:
             step_plan = eng.enable_time_table(coef, step_ptr) or step_plan
         zeros = lambda: torch.zeros_like(eng.x_in)
-        # (x: the image the sampler steps.  scales / sibling: Imagen's guidance schedules, None for every stage without one, under both samplers)
+        # (x: the image the sampler steps.  scales / sibling: Imagen's guidance schedules, None for every stage without one, under both samplers;
+        # guide / avg / head: Imagen's guidance rescale | projected guidance, its running average and the plan that zeroes it at a run's start)
         return dict(eng=eng, step_plan=step_plan, plan=None, graph=None, coef=coef, **state, x=eng.x_in,
-                    key=key, scales=None, sibling=None,
+                    key=key, scales=None, sibling=None, guide=None, avg=None, head=None,
                     n=n, S=S, R=R, video=video, frames=frames, sample_offset=sample_offset,
                     # inpainting: the known image (video: frame-major clip), normalised, at this stage's size; 1.0 where it is kept
                     known=zeros() if R else None, mask=zeros() if R else None,
@@ -597,7 +604,7 @@ class Imagen(nn.Module):
     def _emit_step(self, plan: Plan, st: dict, idx: int, *, cfg: int, cond_scale: float, inject_noise: bool) -> dict:
         """One sampling step of stage `st`, on the sampler state it holds, into `plan`:
 
-            [inpaint.blend]  eng.step_plan  CFG_X0  [QUANTILE]  update  [dpmpp_2m.history]  [inpaint.renoise]
+            [inpaint.blend]  eng.step_plan  CFG_X0 | GUIDE_X0 (reduce, apply)  [QUANTILE]  update  [dpmpp_2m.history]  [inpaint.renoise]
 
         The update is the DDPM_UPDATE launch, or — st['solver'] = (sampler, steps, eta) — one LINCOMB x = w0 x + w1 thr(x0) + w3 x0_prev
         (+ the noise term of 'ddim' at eta > 0), which also emits thr(x0) (`thr1_out`: the next step's self-conditioning input and, for
@@ -615,8 +622,14 @@ class Imagen(nn.Module):
             ops.lincomb(plan, st['known'], eng.x_in, tables[1], step_ptr, B=B, n_per_sample=n, t1=noise_blend, mask=st['mask'], mask_else=eng.x_in,
                         stream_id=idx | 0x100, sample_offset=st['sample_offset'], seed_ptr=seed_dev, label="inpaint.blend")
         plan.extend(st['step_plan'])
-        ops.cfg_x0(plan, eng.x_in, eng.out, coef, step_ptr, x0, absx0, B=B, n_per_sample=n, cfg=cfg, cond_scale=float(cond_scale),
-                   objective=self.pred_objectives[idx])
+        guide = st['guide'] if cfg else None             # (an unguided step is CFG_X0's, and leaves the running average alone)
+        if guide is None:
+            ops.cfg_x0(plan, eng.x_in, eng.out, coef, step_ptr, x0, absx0, B=B, n_per_sample=n, cfg=cfg, cond_scale=float(cond_scale),
+                       objective=self.pred_objectives[idx])
+        else:
+            kw = dict(phi=guide[1]) if guide[0] == 'rescale' else dict(eta=guide[1], norm_threshold=guide[2], momentum=guide[3], avg=st['avg'])
+            ops.guide_x0(plan, eng.x_in, eng.out, coef, step_ptr, x0, absx0, B=B, n_per_sample=n, cfg=cfg, cond_scale=float(cond_scale),
+                         objective=self.pred_objectives[idx], mode=guide[0], **kw)
         dyn = bool(self.dynamic_thresholding[idx])
         if dyn:
             ops.quantile(plan, absx0, quant, scratch, B=B, n=n, q=float(self.dynamic_thresholding_percentile))
@@ -644,7 +657,7 @@ class Imagen(nn.Module):
 
     def _build_stage(self, idx: int, B: int, device, *, cond_scale: float, with_text: bool, inject_noise: bool, sample_offset: int,
                      resample_times: int = 0, frames: int = 0, prompt_frames: tuple = (0, 0), size=None, solver: Optional[tuple] = None,
-                     guidance: Optional[torch.Tensor] = None):
+                     guidance: Optional[torch.Tensor] = None, guide: Optional[tuple] = None):
         """Build (or fetch) the per-timestep plan + graph of stage `idx` for batch B, at image_sizes[idx] or at `size` (an int, or (H, W)):
         form the key, get or make the stage (`_new_stage`), emit its step (`_emit_step`), file it.
 
@@ -658,11 +671,17 @@ class Imagen(nn.Module):
         guided one (2B rows) with CFG_X0 at cfg = 2, which reads the step's scale from column 7 of the step table; `cond_scale` is not
         used.  Where the schedule has steps at exactly 1 — outside a guidance interval — st['sibling'] is the stage `cond_scale = 1`
         builds (B rows, cfg = 0), made here with share = this stage: it runs on this stage's sampler state (SHARED_STATE and the engine's
-        x / low-res image) and `_run_stage` replays it on those steps."""
+        x / low-res image) and `_run_stage` replays it on those steps.
+
+        guide = ('rescale', phi) | ('apg', eta, norm_threshold, momentum) (Imagen._guide_of): the guided steps launch GUIDE_X0 in place of
+        CFG_X0; the setting ends the stage's key.  Projected guidance with momentum keeps its running average in st['avg'], zeroed by the
+        one-launch plan st['head'] that `_rewind` runs at the start of every run; the unguided sibling neither reads nor writes it."""
         sched = self.noise_schedulers[idx]
         T, R = sched.num_timesteps if solver is None else solver[1], resample_times
         assert solver is None or not R, 'the solvers do not cover inpainting'
         assert guidance is None or (not R and tuple(guidance.shape) == (T,) and guidance.dtype == torch.float32)
+        assert guide is None or (not R and (guidance is not None or cond_scale != 1.)), 'guidance rescale / projected guidance act on guided steps'
+        suffix = () if guide is None else (('guide', guide),)     # (a call without the keywords keeps the key it always had)
         size = self.image_sizes[idx] if size is None else size
         two = solver is not None and solver[0] == 'dpmpp_2m'
         buffers = ('x0_thr',) * bool(two or getattr(self.unets[idx], 'self_cond', False)) + ('x0_prev',) * two
@@ -679,14 +698,17 @@ class Imagen(nn.Module):
                 # ('dpmpp_2m': the first step of a run has no history: its row is first order, wherever skip_steps starts the run — _rewind)
                 st.update(plan=Plan(f"stage{idx}-step"), T=T, solver=solver, scales=scales, weights=st['tables'][1] if solver is not None else None,
                           weights_at=(lambda start: sched.solver_coefficients(*solver, philox=not inject_noise, start=start)[1]) if two else None,
-                          weights_start=0)
+                          weights_start=0, guide=guide if cfg else None)
+                if cfg and guide is not None and guide[0] == 'apg' and guide[3] != 0.:
+                    st['avg'], st['head'] = torch.zeros(B, st['n'], device=device), Plan(f"stage{idx}-head")
+                    ops.memset32(st['head'], st['avg'], 0)
                 st.update(self._emit_step(st['plan'], st, idx, cfg=cfg, cond_scale=scale, inject_noise=inject_noise))
                 self._stages[key] = st
             return st, built
 
         if guidance is None:
-            return stage(key_at(cond_scale), int(cond_scale != 1.), cond_scale)[0]
-        key = key_at(cond_scale) + (('guidance', guidance.numpy().tobytes()),)   # (a call without a schedule keeps the key it always had)
+            return stage(key_at(cond_scale) + suffix, int(cond_scale != 1.), cond_scale)[0]
+        key = key_at(cond_scale) + (('guidance', guidance.numpy().tobytes()),) + suffix   # (a call without a schedule keeps the key it always had)
         st, built = stage(key, 2, cond_scale, scales=[float(v) for v in guidance])
         if built and 1. in st['scales']:
             st['sibling'] = stage(key_at(1.) + (('shares', key),), 0, 1., share=st)[0]
@@ -719,6 +741,8 @@ class Imagen(nn.Module):
         """The sampler state behind the fresh x_T ~ N(0, I), for a run that starts at timestep `skip`."""
         if init_images is not None:
             st['x'].add_(init_images)                   # ip.py:2205-2206
+        if st['head'] is not None:
+            st['head'].run()                            # projected guidance: the running average starts every run at zero
         if st['x0_thr'] is not None:
             st['x0_thr'].zero_()                        # no x0 estimate yet: the first step self-conditions on zeros (ip.py:2210, 1542)
         if st['x0_prev'] is not None:                   # 'dpmpp_2m': no history yet, and the run's first row is first order
@@ -970,6 +994,12 @@ class Imagen(nn.Module):
                                                        #   Every distinct per-step vector is a cached stage of its own (engine, time table, graph;
                                                        #   with unguided steps also the B-row sibling) that is kept, as every stage is: a sweep
                                                        #   over many schedules grows the cache — sample from a fresh Imagen, or clear `_stages`
+        guidance_rescale=None,                         # extension: phi in [0, 1] of guidance rescale (Lin et al. 2023): the guided model output
+                                                       #   brought back to the conditional one's per-sample standard deviation, blended by phi
+        guidance_apg=None,                             # extension: dict(eta=0., norm_threshold=None, momentum=0.) of adaptive projected guidance
+                                                       #   (Sadat et al. 2024), in x0 space; both: one value for every unet, or a tuple with one
+                                                       #   entry (or None) per unet; not both on one unet.  They act on the guided steps (GUIDE_X0
+                                                       #   in place of CFG_X0); a distinct setting is a cached stage of its own
     ):
         return self._sample(self._call(**{k: v for k, v in locals().items() if k != 'self'}))   # (the keywords, as given)
 
@@ -1012,6 +1042,74 @@ class Imagen(nn.Module):
         if self.unconditional:
             raise ValueError(f'{kw}: this model was built with condition_on_text=False, there is no text branch to guide')
         return schedules, intervals
+
+    def _guide_of(self, guidance_rescale=None, guidance_apg=None):
+        """`guidance_rescale` / `guidance_apg` of one call, per unet and checked as far as that goes without the guidance scales: None when
+        neither is given, else one entry per unet — None, ('rescale', phi) or ('apg', eta, norm_threshold, momentum) with norm_threshold 0.
+        for "no cap".  One value serves every unet; a tuple holds one entry (or None) per unet.  Raises ValueError for malformed values,
+        both keywords on one unet, a model trained without conditional dropout or without a text branch."""
+        import math
+
+        if guidance_rescale is None and guidance_apg is None:
+            return None
+        n = len(self.unets)
+        number = lambda v: (isinstance(v, (int, float)) and not isinstance(v, bool)) or (isinstance(v, torch.Tensor) and v.ndim == 0)
+
+        def per_unet(val, kw, one):
+            if val is None or one(val):
+                return (val,) * n
+            if not isinstance(val, (list, tuple)):
+                raise ValueError(f'{kw} = {val!r}: one value, or a tuple with one entry (or None) per unet')
+            if len(val) != n:
+                raise ValueError(f'{kw}: {len(val)} entries for {n} unets (one entry, or None, per unet)')
+            return tuple(val)
+
+        def finite(v, what, none_ok=False):
+            if v is None and none_ok:
+                return 0.
+            if not number(v) or not math.isfinite(float(v)):
+                raise ValueError(f'{what} = {v!r}: a finite number')
+            return float(v)
+
+        out = []
+        for i, (phi, apg) in enumerate(zip(per_unet(guidance_rescale, 'guidance_rescale', number), per_unet(guidance_apg, 'guidance_apg', lambda v: isinstance(v, dict)))):
+            if phi is not None and apg is not None:
+                raise ValueError(f'guidance_rescale and guidance_apg are both given for unet {i + 1}: a stage takes one of them')
+            if phi is not None:
+                phi = finite(phi, f'guidance_rescale[{i}]')
+                if not 0. <= phi <= 1.:
+                    raise ValueError(f'guidance_rescale[{i}] = {phi} is outside [0, 1]')
+                out.append(('rescale', phi))
+            elif apg is not None:
+                if not isinstance(apg, dict) or set(apg) - {'eta', 'norm_threshold', 'momentum'}:
+                    raise ValueError(f'guidance_apg[{i}] = {apg!r}: a dict with the keys eta, norm_threshold, momentum (each optional)')
+                thr = finite(apg.get('norm_threshold'), f'guidance_apg[{i}][norm_threshold]', none_ok=True)
+                out.append(('apg', finite(apg.get('eta', 0.), f'guidance_apg[{i}][eta]'), max(thr, 0.), finite(apg.get('momentum', 0.), f'guidance_apg[{i}][momentum]')))
+            else:
+                out.append(None)
+        kw = 'guidance_rescale' if guidance_rescale is not None else 'guidance_apg'
+        if not self.can_classifier_guidance:
+            raise ValueError(f'{kw}: imagen was not trained with conditional dropout (cond_drop_prob == 0) and cannot do classifier free guidance')
+        if self.unconditional:
+            raise ValueError(f'{kw}: this model was built with condition_on_text=False, there is no text branch to guide')
+        return tuple(out)
+
+    def _check_guide(self, given, cond_scale: tuple, guidance: tuple, inpainting: bool, first: int, last: int, scales: bool = True):
+        """What `_guide_of` returned against the stages [first, last) of one call — their resolved cond_scale and guidance vectors.  Refused:
+        inpainting, a stage whose unet has no text branch, and (scales: not for one stage of a cascade sample_pipelined has checked as a
+        whole) a call none of whose stages with a setting is guided, which would silently ignore the keyword."""
+        if given is None:
+            return None
+        if inpainting:
+            raise ValueError('guidance_rescale / guidance_apg with inpainting: the resample loop (ip.py:2237-2275) runs every table row '
+                             'several times on one captured plan; sample with the plain guidance when inpainting')
+        for idx in range(first, last):
+            if given[idx] is not None and not getattr(self.unets[idx], 'cond_on_text', False):
+                raise ValueError(f'guidance_rescale / guidance_apg: unet {idx + 1} has no text branch (cond_on_text=False), there is nothing to guide')
+        if scales and all(cond_scale[idx] == 1. and guidance[idx] is None for idx in range(first, last) if given[idx] is not None):
+            raise ValueError('guidance_rescale / guidance_apg: no stage of this call that has a setting is guided (cond_scale is 1 and there is '
+                             'no schedule), so the keyword would be silently ignored')
+        return given
 
     def _solver_of(self, sampler=None, sample_steps=None, eta=None):
         """The solver keywords of one call, checked: None for the ancestral sampler ('ddpm', the default: one step per training timestep),
@@ -1223,6 +1321,9 @@ class Imagen(nn.Module):
         c.level = c.lowres_sample_noise_level if c.lowres_sample_noise_level is not None else self.lowres_sample_noise_level
         c.cond_scale = _cast_tuple(c.cond_scale, num_unets)
         c.guidance = self._resolve_guidance(c)
+        c.guide = self._check_guide(self._guide_of(c.guidance_rescale, c.guidance_apg), c.cond_scale, c.guidance,
+                                    c.inpaint_images is not None or c.inpaint_masks is not None, c.start_at_unet_number - 1,
+                                    num_unets if c.stop_at_unet_number is None else c.stop_at_unet_number, scales=not c.pipelined_stage)
         if c.seed is None:
             c.seed = self._next_seed()
         # the negative prompt of this call: resolved and checked here, before any stage is built or anything is launched
@@ -1308,6 +1409,8 @@ class Imagen(nn.Module):
             extra['solver'] = c.solver[idx]
         if c.guidance is not None and c.guidance[idx] is not None:
             extra['guidance'] = c.guidance[idx]
+        if c.guide is not None and c.guide[idx] is not None and (cs != 1. or 'guidance' in extra):     # (an unguided stage has nothing to rescale)
+            extra['guide'] = c.guide[idx]
         st = self._stage(idx, batch_size, device, cond_scale=cs, with_text=with_text, inject_noise=noise_fn is not None,
                          sample_offset=c.sample_offset, resample_times=c.inpaint_resample_times if c.known is not None else 0,
                          frames=c.frames // self.temporal_downsample_factor[idx] if isinstance(unet, Unet3D) else 0,

@@ -1375,6 +1375,49 @@ def cfg_x0(plan: Plan, x, pred, coef, step_ptr, x0, absx0, *, B, n_per_sample, c
     return p
 
 
+GUIDE_MODES = {"rescale": ENUMS["IMAGEN_GUIDE_RESCALE"], "apg": ENUMS["IMAGEN_GUIDE_APG"]}
+
+
+def guide_x0(plan: Plan, x, pred, coef, step_ptr, x0, absx0, *, B, n_per_sample, cfg: int, cond_scale: float, mode: str, objective: str = "noise",
+             phi: float = 0., eta: float = 0., norm_threshold: Optional[float] = None, momentum: float = 0., avg: Optional[torch.Tensor] = None,
+             partials: Optional[torch.Tensor] = None, label: str = ""):
+    """GUIDE_X0 (include/imagen_hip.h): CFG_X0's guided evaluation with guidance rescale (mode 'rescale': phi) or adaptive projected guidance
+    (mode 'apg': eta, norm_threshold — None or <= 0: no cap —, momentum with its running average `avg`, fp32 [B, n]), as TWO launches (reduce,
+    apply).  cfg: 1 guided at `cond_scale`, 2 at column 7 of the current row of `coef`.  partials: fp64 [B * IMAGEN_GUIDE_PARTIAL_DOUBLES] of
+    scratch (allocated here when None).  Returns the two structs."""
+    if mode not in GUIDE_MODES:
+        raise ValueError(f"guide_x0: mode = {mode!r}; {' | '.join(repr(m) for m in GUIDE_MODES)}")
+    if int(cfg) not in (1, 2):
+        raise ValueError(f"guide_x0: cfg = {cfg!r}; 1 (cond_scale) or 2 (the scale in column 7 of the step's table row): an unguided step is cfg_x0's")
+    if int(cfg) == 2 and not (coef.dtype == torch.float32 and coef.ndim == 2 and coef.shape[1] == 8 and coef.is_contiguous()):
+        raise ValueError("guide_x0: cfg = 2 reads the scale from a contiguous fp32 [steps, 8] table")
+    thr = 0. if norm_threshold is None else float(norm_threshold)
+    phi, eta, momentum = float(phi), float(eta), float(momentum)
+    if mode == "rescale" and not 0. <= phi <= 1.:       # (also refuses nan)
+        raise ValueError(f"guide_x0: phi = {phi} is outside [0, 1]")
+    for name, v in (("eta", eta), ("norm_threshold", thr), ("momentum", momentum)):
+        if not math.isfinite(v):
+            raise ValueError(f"guide_x0: {name} = {v} is not finite")
+    if mode == "apg" and momentum != 0. and avg is None:
+        raise ValueError("guide_x0: momentum needs the running average buffer `avg`")
+    _abi.require_ext_op(ENUMS["IMAGEN_OP_GUIDE_X0"], "guide_x0")
+    words = ENUMS["IMAGEN_GUIDE_PARTIAL_DOUBLES"]
+    if partials is None:
+        partials = torch.empty(B * words, dtype=torch.float64, device=x0.device)
+    assert partials.dtype == torch.float64 and partials.numel() >= B * words and partials.is_contiguous()
+    assert avg is None or (avg.dtype == torch.float32 and avg.numel() == B * n_per_sample and avg.is_contiguous())
+    out = []
+    for phase in (0, 1):
+        p = STRUCTS["ImagenGuideX0Params"]()
+        p.x, p.pred, p.coef, p.step_ptr, p.x0, p.absx0 = x.data_ptr(), pred.data_ptr(), coef.data_ptr(), step_ptr.data_ptr(), x0.data_ptr(), absx0.data_ptr()
+        p.avg, p.partials = ptr(avg if mode == "apg" else None), partials.data_ptr()
+        p.B, p.n_per_sample, p.cfg, p.objective, p.mode, p.phase = B, n_per_sample, int(cfg), OBJECTIVES[objective], GUIDE_MODES[mode], phase
+        p.cond_scale, p.phi, p.eta, p.norm_threshold, p.momentum = cond_scale, phi, eta, thr, momentum
+        plan.add(p, (label or "guide_x0") + (".reduce", ".apply")[phase], [x, pred, coef, step_ptr, x0, absx0, avg, partials])
+        out.append(p)
+    return out
+
+
 def quantile(plan: Plan, absx0, out, scratch, *, B, n, q: float, label: str = ""):
     p = STRUCTS["ImagenQuantileParams"]()
     p.absx0, p.out, p.scratch, p.B, p.n, p.q = absx0.data_ptr(), out.data_ptr(), scratch.data_ptr(), B, n, q

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define IMAGEN_ABI_VERSION 15 /* 15: TEMPORAL_ATTENTION takes F <= 128 (clips of 33 .. 128 frames run on a tiled kernel; F <= 32 launches what it launched before; no struct changed), and head_dim 128 is accepted by ATTENTION / QNORM / KV_PREP / LINCTX / LINEAR_XATTN (Unet(attn_dim_head=128); no struct changed, no new op kind);  14: LINCTX, LINEAR_XATTN (LinearCrossAttention: Unet(use_linear_cross_attn=...); no struct of before changed);  13: ImagenLincombParams.thr1_out / thr3_out (LINCOMB writes out the thresholded operands it sums: the self-conditioning input of the ElucidatedImagen sampler; NULL = the launch of before);  12: ImagenTemporalAttentionParams.head_dim (the temporal attention of Imagen-Video at head dim 32, the reference's Unet3DConfig default; 0 = 64: plans of before are unchanged);  11: ImagenDdpmUpdateParams.row_keys (per-row Philox key + sample index: requests merged into one batch draw their own noise);  10: ImagenIgemmParams.pad_x1 (a KH x KW window with its own x padding: the causal temporal conv of Imagen-Video as ONE (3 x 1)-tap launch);  9: LINEAR_F32, SCALE_SHIFT ss_f32;  8: ROWCHAIN, the latency probes;  3: head_dim in the attention / QNORM / KV_PREP params; 4: DDPM_UPDATE x0_thr; 5: GCA_TAIL; 6: ACT_PREP self_stat, STEP_SLICE;
+#define IMAGEN_ABI_VERSION 15 /* 15 (additive, same number): GUIDE_X0, an op kind of the extension range (ImagenExtOpKind below: guidance rescale and projected guidance, Imagen.sample(guidance_rescale=, guidance_apg=)) — no existing struct or kind changed, every plan of before is launched as before; a library built before it answers imagen_sizeof(IMAGEN_OP_GUIDE_X0) == 0 and the host refuses the keyword with a "rebuild" message.  15: TEMPORAL_ATTENTION takes F <= 128 (clips of 33 .. 128 frames run on a tiled kernel; F <= 32 launches what it launched before; no struct changed), and head_dim 128 is accepted by ATTENTION / QNORM / KV_PREP / LINCTX / LINEAR_XATTN (Unet(attn_dim_head=128); no struct changed, no new op kind);  14: LINCTX, LINEAR_XATTN (LinearCrossAttention: Unet(use_linear_cross_attn=...); no struct of before changed);  13: ImagenLincombParams.thr1_out / thr3_out (LINCOMB writes out the thresholded operands it sums: the self-conditioning input of the ElucidatedImagen sampler; NULL = the launch of before);  12: ImagenTemporalAttentionParams.head_dim (the temporal attention of Imagen-Video at head dim 32, the reference's Unet3DConfig default; 0 = 64: plans of before are unchanged);  11: ImagenDdpmUpdateParams.row_keys (per-row Philox key + sample index: requests merged into one batch draw their own noise);  10: ImagenIgemmParams.pad_x1 (a KH x KW window with its own x padding: the causal temporal conv of Imagen-Video as ONE (3 x 1)-tap launch);  9: LINEAR_F32, SCALE_SHIFT ss_f32;  8: ROWCHAIN, the latency probes;  3: head_dim in the attention / QNORM / KV_PREP params; 4: DDPM_UPDATE x0_thr; 5: GCA_TAIL; 6: ACT_PREP self_stat, STEP_SLICE;
                                * 7: every launch carries sizeof(its params struct) (a stale mirror of a struct fails loudly), ImagenIgemmParams.dbg -> launcher_word, kernel families 6 and 7, ImagenAttentionParams.softmax_mode */
 
 typedef void* imagen_stream_t; /* hipStream_t */
@@ -69,7 +69,13 @@ enum ImagenOpKind {
   IMAGEN_OP_LINEAR_F32 = 30,   /* a Linear on per-sample vectors in fp32 end to end (the timestep-conditioning chain: to_time_cond, the ResnetBlocks' time MLPs) */
   IMAGEN_OP_LINCTX = 31,       /* LinearCrossAttention: per (row, head) the column softmax of k over the conditioning tokens and M = k^T v, for every site in ONE launch */
   IMAGEN_OP_LINEAR_XATTN = 32, /* LinearCrossAttention: o = 8 * softmax_d(q) M per (pixel, head), on MFMA */
-  IMAGEN_OP_KIND_COUNT = 33
+  IMAGEN_OP_KIND_COUNT = 33   /* end of the base range 1 .. 32: the kinds every library of this ABI version has (the binding checks each of their structs when it loads the library) */
+};
+/* The extension range: kinds added WITHOUT an ABI bump, numbered on from the base range.  A caller asks imagen_sizeof(kind) before it builds a plan
+ * with one: 0 = this library was built before the kind existed (imagen_launch refuses it as unknown). */
+enum ImagenExtOpKind {
+  IMAGEN_OP_GUIDE_X0 = 33,     /* guided x0 with per-sample statistics: guidance rescale | adaptive projected guidance; two launches (reduce, apply) */
+  IMAGEN_OP_EXT_END = 34
 };
 
 /* ------------------------------------------------------------------------------------------------
@@ -391,6 +397,35 @@ typedef struct ImagenCfgX0Params {
   const float* x; const float* pred; const float* coef; const int32_t* step_ptr; float* x0; float* absx0;
   int32_t B, n_per_sample, cfg, objective; float cond_scale;
 } ImagenCfgX0Params;
+
+/* GUIDE_X0 — the guided evaluation of CFG_X0 with a remedy for the saturation of high guidance scales that needs PER-SAMPLE reductions over the whole
+ * image (the reference has no such lines; the formulas are those of the papers, stated here).  Same inputs as CFG_X0 at cfg 1 | 2 (pred [2B, n], cond
+ * rows first; s = cond_scale | coef[*step_ptr][7]; alpha, sigma = coef[*step_ptr][0 .. 1]), same outputs (x0, |x0|): QUANTILE / DDPM_UPDATE / LINCOMB
+ * follow unchanged.  With X0(e) = (x - sigma*e) / max(alpha, 1e-8) | e | alpha*x - sigma*e (objective 0 | 1 | 2), CFG_X0's expressions:
+ *   mode 1, guidance rescale (Lin et al. 2023, "Common diffusion noise schedules and sample steps are flawed", section 3.4):
+ *       g  = nul + (cond - nul) * s                                  (fp32, CFG_X0's expression)
+ *       f  = sqrt(var(cond) / var(g)) per sample, 1 where var(g) <= 0;   var(v) = max(sum v^2 / n - (sum v / n)^2, 0) over the sample's n elements (fp64)
+ *       x0 = X0(phi * (g * f) + (1 - phi) * g)                         0 <= phi <= 1; phi == 0 gives the bits of CFG_X0
+ *   mode 2, adaptive projected guidance (Sadat et al. 2024, "Eliminating oversaturation and artifacts of high guidance scales in diffusion models"), in x0 space:
+ *       Dc = X0(cond), Du = X0(nul);   D = (Dc - Du) + momentum * avg   (avg == NULL: D = Dc - Du)                                 (fp32)
+ *       r  = norm_threshold > 0 ? min(1, norm_threshold / sqrt(<D, D>)) : 1;   k = <Dc, Dc> > 0 ? r * <D, Dc> / <Dc, Dc> : 0      (per sample, fp64 sums)
+ *       D' = r * D;  P = k * Dc  (the part of D' parallel to Dc);   x0 = Dc + (s - 1) * ((D' - P) + eta * P);   avg = D  (before the cap; avg != NULL)
+ *       eta == 1 without threshold and momentum is plain guidance in x0 space; s == 1 gives the bits of X0(cond).
+ * Two launches of the SAME struct: phase 0 (reduce) writes, per sample and workgroup, four fp64 partial sums to partials[b][workgroup][4]
+ * (rescale: sum cond, sum cond^2, sum g, sum g^2;  APG: <D, D>, <D, Dc>, <Dc, Dc>, 0); phase 1 (apply) adds a sample's partials in workgroup order
+ * (every workgroup the same order: no floating-point atomics, bit-identical from run to run), rounds f | r, k to fp32 and writes x0, |x0| and avg.
+ * Workgroups per sample: ceil(n / 8192), at most IMAGEN_GUIDE_MAX_BLOCKS (as QUANTILE).  n is arbitrary; 16-byte accesses where n % 4 == 0 and the
+ * buffers are 16-byte aligned.  partials: B * IMAGEN_GUIDE_PARTIAL_DOUBLES fp64 of scratch, 8-byte aligned, needs no clearing; avg: fp32 [B, n], the state
+ * of the momentum across steps (the caller zeroes it at the start of a run), required when momentum != 0. */
+#define IMAGEN_GUIDE_MAX_BLOCKS 64
+#define IMAGEN_GUIDE_PARTIAL_DOUBLES (64 * 4)
+enum { IMAGEN_GUIDE_RESCALE = 1, IMAGEN_GUIDE_APG = 2 };
+typedef struct ImagenGuideX0Params {
+  const float* x; const float* pred; const float* coef; const int32_t* step_ptr; float* x0; float* absx0;
+  float* avg; double* partials;
+  int32_t B, n_per_sample, cfg, objective, mode, phase;
+  float cond_scale, phi, eta, norm_threshold, momentum;
+} ImagenGuideX0Params;
 
 /* QUANTILE — torch.quantile(|x0| per sample, q) ip.py:2097-2101 (linear interpolation), exact. */
 typedef struct ImagenQuantileParams {
