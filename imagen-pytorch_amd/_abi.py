@@ -127,6 +127,7 @@ OP_STRUCT = {
 # base range is whole — and `require_ext_op` refuses the kind when a plan first asks for it.
 EXT_OP_STRUCT = {
     ENUMS["IMAGEN_OP_GUIDE_X0"]: STRUCTS["ImagenGuideX0Params"],
+    ENUMS["IMAGEN_OP_COMPOSE_X0"]: STRUCTS["ImagenComposeX0Params"],
 }
 STRUCT_KIND = {v: k for k, v in {**OP_STRUCT, **EXT_OP_STRUCT}.items()}
 

@@ -53,6 +53,7 @@ extern "C" size_t imagen_sizeof(int kind) {
     case IMAGEN_OP_LINCTX: return sizeof(ImagenLinCtxParams);
     case IMAGEN_OP_LINEAR_XATTN: return sizeof(ImagenLinearXattnParams);
     case IMAGEN_OP_GUIDE_X0: return sizeof(ImagenGuideX0Params);
+    case IMAGEN_OP_COMPOSE_X0: return sizeof(ImagenComposeX0Params);
     default: return 0;
   }
 }
@@ -99,6 +100,7 @@ extern "C" int imagen_launch(int kind, const void* params, size_t params_bytes, 
     case IMAGEN_OP_LINCTX: return launch_linctx(static_cast<const ImagenLinCtxParams*>(params), s);
     case IMAGEN_OP_LINEAR_XATTN: return launch_linear_xattn(static_cast<const ImagenLinearXattnParams*>(params), s);
     case IMAGEN_OP_GUIDE_X0: return launch_guide_x0(static_cast<const ImagenGuideX0Params*>(params), s);
+    case IMAGEN_OP_COMPOSE_X0: return launch_compose_x0(static_cast<const ImagenComposeX0Params*>(params), s);
     default: imagen_set_error("imagen_launch: unknown op kind %d", kind); return -1;
   }
 }

@@ -180,6 +180,64 @@ __global__ __launch_bounds__(256) void guide_x0_kernel(const ImagenGuideX0Params
   }
 }
 
+// ---- COMPOSE_X0: K weighted, optionally masked prompts against one null branch, see ImagenComposeX0Params ----
+// One pass over pred ((K + 1) B n floats), x and the masks: memory-bound, every byte read once.  A thread owns 4 consecutive elements of ONE sample
+// (16 bytes a lane where VEC: n % 4 == 0, hw % 4 == 0 — a group then lies inside one channel plane, so its 4 mask values are consecutive too — and
+// 16-byte aligned buffers; else 4-byte accesses, the tail masked).  The weights are K uniform loads per thread out of L2 / the scalar cache.
+template <bool VEC>
+__global__ __launch_bounds__(256) void compose_x0_kernel(const ImagenComposeX0Params p, unsigned groups) {
+  const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const int n = p.n_per_sample, B = p.B, K = p.K, hw = p.hw;
+  if (g >= (size_t)B * groups) return;
+  const int b = (int)(g / groups);
+  const int e0 = (int)(g % groups) * 4;
+  const float* cf = p.coef + (size_t)(*p.step_ptr) * kCoefStride;
+  const float alpha = cf[0], sigma = cf[1];
+  const size_t branch = (size_t)B * n, row0 = (size_t)b * n;
+  float nul[4], acc[4], x[4] = {0.f, 0.f, 0.f, 0.f}, o[4], oa[4];
+  guide_load4<VEC>(p.pred + (size_t)K * branch + row0, e0, n, nul);   // the null rows are the last B
+#pragma unroll
+  for (int e = 0; e < 4; ++e) acc[e] = nul[e];
+  int pix[4];
+  if (!VEC) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) pix[e] = (e0 + e) % hw;
+  }
+#pragma unroll
+  for (int k = 0; k < IMAGEN_COMPOSE_MAX; ++k) {
+    if (k < K) {
+      float c[4], t[4];
+      guide_load4<VEC>(p.pred + (size_t)k * branch + row0, e0, n, c);
+      const float w = p.weights[k * B + b];
+      if (p.masks) {
+        const float* mr = p.masks + ((size_t)k * B + b) * hw;
+        float m[4];
+        if (VEC) {
+          guide_load4<true>(mr, e0 % hw, hw, m);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) m[e] = (e0 + e < n) ? mr[pix[e]] : 0.f;
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) t[e] = w * m[e];
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) t[e] = w;
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[e] = acc[e] + (c[e] - nul[e]) * t[e];   // CFG_X0's expression, the running sum in nul's place
+    }
+  }
+  if (p.objective != 1) guide_load4<VEC>(p.x + row0, e0, n, x);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    o[e] = guide_x0_of(x[e], acc[e], alpha, sigma, p.objective);
+    oa[e] = fabsf(o[e]);
+  }
+  guide_store4<VEC>(p.x0 + row0, e0, n, o);
+  guide_store4<VEC>(p.absx0 + row0, e0, n, oa);
+}
+
 // ---- exact quantile: 4 x 8-bit MSB-first radix select on the (non-negative) float bit patterns ------------
 // scratch per sample (uint32): hist[4][256] | cnt_le | min_gt | unused...
 constexpr int kScratch = IMAGEN_QUANTILE_SCRATCH_WORDS;
@@ -480,6 +538,23 @@ int launch_guide_x0(const ImagenGuideX0Params* p, hipStream_t s) {
   if (vec) hipLaunchKernelGGL(guide_x0_kernel<true>, dim3((unsigned)(p->B * bps)), dim3(256), 0, s, *p, bps);
   else hipLaunchKernelGGL(guide_x0_kernel<false>, dim3((unsigned)(p->B * bps)), dim3(256), 0, s, *p, bps);
   return imagen_hip_status("guide_x0");
+}
+
+int launch_compose_x0(const ImagenComposeX0Params* p, hipStream_t s) {
+  IMAGEN_CHECK(p->x && p->pred && p->coef && p->step_ptr && p->x0 && p->absx0 && p->weights, "compose_x0: x / pred / coef / step_ptr / x0 / absx0 / weights required");
+  IMAGEN_CHECK(p->B > 0 && p->n_per_sample > 0 && p->n_per_sample <= 0x7FFFFFF0, "compose_x0: B > 0, 0 < n_per_sample <= 2^31 - 16");
+  IMAGEN_CHECK(p->K >= 1 && p->K <= IMAGEN_COMPOSE_MAX, "compose_x0: K outside 1 .. IMAGEN_COMPOSE_MAX prompts");
+  IMAGEN_CHECK(p->hw > 0, "compose_x0: hw <= 0 (the pixels of one channel plane)");
+  IMAGEN_CHECK(p->n_per_sample % p->hw == 0, "compose_x0: n_per_sample is no multiple of hw (the state is NCHW: n = C * hw)");
+  IMAGEN_CHECK(p->objective >= 0 && p->objective <= 2, "compose_x0: objective is 0 (noise), 1 (x_start) or 2 (v)");
+  const unsigned groups = (unsigned)(((size_t)p->n_per_sample + 3) >> 2);
+  const size_t blocks = ((size_t)p->B * groups + 255) / 256;
+  IMAGEN_CHECK(blocks <= 0x7FFFFFFFu, "compose_x0: B * n_per_sample too large for one launch");
+  const uintptr_t align = (uintptr_t)p->x | (uintptr_t)p->pred | (uintptr_t)p->x0 | (uintptr_t)p->absx0 | (uintptr_t)p->masks;
+  const bool vec = p->n_per_sample % 4 == 0 && p->hw % 4 == 0 && (align & 15) == 0;
+  if (vec) hipLaunchKernelGGL(compose_x0_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, *p, groups);
+  else hipLaunchKernelGGL(compose_x0_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, *p, groups);
+  return imagen_hip_status("compose_x0");
 }
 
 int launch_quantile(const ImagenQuantileParams* p, hipStream_t s) {

@@ -36,9 +36,33 @@ def shard_negative(lo: int, hi: int, total: int, negative_text_embeds: Optional[
     return dict(negative_text_embeds=cut(negative_text_embeds), negative_text_masks=None if negative_text_masks is None else cut(negative_text_masks))
 
 
+def shard_compose(lo: int, hi: int, total: int, compose=None, compose_mask=None) -> dict:
+    """The composed-prompt keywords (Imagen.sample(compose=, compose_mask=)) of the shard [lo, hi) of `total` samples: whatever has one row per
+    sample — embeddings and text masks of batch `total`, [total] weights, [total, H, W] masks — is sliced with its rows; batch-1 prompts and
+    masks, [H, W] masks, floats, per-unet tuples and `texts` of one string go to every rank as they are (per-sample `texts` are sliced)."""
+    out = {}
+    rows = lambda t, nd: t[lo:hi] if isinstance(t, torch.Tensor) and t.ndim == nd and t.shape[0] == total and total != 1 else t
+    if compose_mask is not None:
+        out['compose_mask'] = rows(compose_mask, 3)
+    if compose is not None:
+        if not isinstance(compose, (list, tuple)) or not all(isinstance(e, dict) for e in compose):
+            return dict(out, compose=compose)            # malformed: `sample_fn` refuses it in its own words
+        entries = []
+        for e in compose:
+            e = dict(e)
+            for k, nd in (('text_embeds', 3), ('text_masks', 2), ('weight', 1), ('mask', 3)):
+                if k in e:
+                    e[k] = rows(e[k], nd)
+            if isinstance(e.get('texts'), (list, tuple)) and len(e['texts']) == total and total != 1:
+                e['texts'] = list(e['texts'][lo:hi])
+            entries.append(e)
+        out['compose'] = entries
+    return out
+
+
 def sample_sharded(sample_fn: Callable[..., torch.Tensor], text_embeds: torch.Tensor, *, text_masks: Optional[torch.Tensor] = None,
                    negative_text_embeds: Optional[torch.Tensor] = None, negative_text_masks: Optional[torch.Tensor] = None,
-                   negative_texts=None, group=None, gather: bool = True, **kwargs) -> torch.Tensor:
+                   negative_texts=None, compose=None, compose_mask=None, group=None, gather: bool = True, **kwargs) -> torch.Tensor:
     """Run `sample_fn(text_embeds=shard, text_masks=shard, sample_offset=lo, **kwargs)` on this rank's shard and all-gather.
 
     `sample_fn` is normally `Imagen.sample`; it must return a (b_local, C, H, W) tensor on the rank's device.
@@ -47,7 +71,8 @@ def sample_sharded(sample_fn: Callable[..., torch.Tensor], text_embeds: torch.Te
     sharded with its rows.  Every other keyword reaches `sample_fn` as given — the solver keywords `sampler=`, `sample_steps=`, `eta=`
     among them: a stochastic solver's draws are keyed by the global sample index (`sample_offset`), as the ancestral sampler's are; and the
     guidance keywords (`guidance_schedule=`, `guidance_interval=`, `guidance_rescale=`, `guidance_apg=`): rescale and projected guidance take
-    their statistics per sample, so a shard's rows are guided as in the whole batch.
+    their statistics per sample, so a shard's rows are guided as in the whole batch.  Composed prompts (`compose=`, `compose_mask=`) are
+    sharded by `shard_compose`: per-sample entries, weights and masks are sliced with the prompts.
     """
     B = text_embeds.shape[0]
     if negative_texts is not None:
@@ -55,8 +80,9 @@ def sample_sharded(sample_fn: Callable[..., torch.Tensor], text_embeds: torch.Te
             raise ValueError('negative_texts and negative_text_embeds are both given: pass one of them')
         if len(negative_texts) not in (1, B):
             raise ValueError(f"negative_texts: {len(negative_texts)} strings, neither 1 nor the prompts' {B}")
-    neg = lambda lo, hi: (shard_negative(lo, hi, B, negative_text_embeds, negative_text_masks) if negative_texts is None else
-                          dict(negative_texts=list(negative_texts) if len(negative_texts) == 1 else list(negative_texts[lo:hi])))
+    neg_of = lambda lo, hi: (shard_negative(lo, hi, B, negative_text_embeds, negative_text_masks) if negative_texts is None else
+                             dict(negative_texts=list(negative_texts) if len(negative_texts) == 1 else list(negative_texts[lo:hi])))
+    neg = lambda lo, hi: {**neg_of(lo, hi), **shard_compose(lo, hi, B, compose, compose_mask)}
     if not dist.is_available() or not dist.is_initialized():
         return sample_fn(text_embeds=text_embeds, text_masks=text_masks, sample_offset=0, **neg(0, B), **kwargs)
     rank, world = dist.get_rank(group), dist.get_world_size(group)

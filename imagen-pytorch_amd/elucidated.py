@@ -320,8 +320,13 @@ class ElucidatedImagen(Imagen):
         guidance_interval=None,
         guidance_rescale=None,
         guidance_apg=None,
+        compose=None,                                 # Imagen.sample's composed prompts: refused here (ValueError)
+        compose_mask=None,
     ):
         return self._sample(self._call(**{k: v for k, v in locals().items() if k != 'self'}))   # (the keywords, as given)
+
+    _compose_refusal = ('ElucidatedImagen evaluates the denoiser twice per step of its second-order sampler on the two-branch plan; composed '
+                        'prompts belong to Imagen.sample')
 
     def _solver_of(self, sampler=None, sample_steps=None, eta=None):
         """Imagen._solver_of: the Karras et al. sampler of this class is the only one it has (num_sample_steps sets its step count)."""
@@ -354,6 +359,8 @@ class ElucidatedImagen(Imagen):
         self._solver_of(kw.get('sampler'), kw.get('sample_steps'), kw.get('eta'))
         self._guidance_of(kw.get('guidance_schedule'), kw.get('guidance_interval'))
         self._guide_of(kw.get('guidance_rescale'), kw.get('guidance_apg'))
+        if kw.get('compose') is not None or kw.get('compose_mask') is not None:
+            raise ValueError(f'compose: {self._compose_refusal}')
         n_unets = len(self.unets)
         over = None if sigma_min is None and sigma_max is None else dict(sigma_min=_cast_tuple(sigma_min, n_unets),
                                                                          sigma_max=_cast_tuple(sigma_max, n_unets))

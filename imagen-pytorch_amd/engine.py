@@ -10,8 +10,9 @@ HIP kernel launches for a fixed (rows, image size — S x S, or H x W): the MI35
   * (sampler ops are appended by imagen.py to form the per-timestep graph).
 
 Row convention: `rows` = B (plain forward) or 2B (classifier-free guidance: rows [0,B) conditional,
-rows [B,2B) with the null text conditioning — ip.py:1510-1522 evaluated as ONE batch).  Row r reads image
-`r % src_batch`.
+rows [B,2B) with the null text conditioning — ip.py:1510-1522 evaluated as ONE batch), or (K + 1) B (composed
+prompts: rows [kB, (k+1)B) conditional on prompt k, the LAST B rows null — set_conditioning(extra_prompts=)).
+Row r reads image `r % src_batch`.
 
 Nothing here computes with torch: torch only owns device buffers.  `dry=True` builds the plan on CPU memory
 without ever launching (host-logic tests).
@@ -1164,21 +1165,24 @@ class UnetEngine:
             ted = u.text_to_cond.weight.shape[1]
             # source rows [0, src_batch): the prompts.  A guided engine stages a second set, [src_batch, 2 src_batch), for a negative prompt:
             # the null rows of a request that has one select those (set_conditioning points src_idx there and sets their keep flag)
-            n_src = 2 * src_batch if R == 2 * src_batch else src_batch
+            # A composed engine (R = (K + 1) src_batch, K > 1: K prompt sets, branch-major, the null rows last) stages K sets of prompt rows,
+            # [0, K src_batch), all projected by the one launch below, and the negative prompt's set behind them.
+            n_prompt = self.n_prompt_rows
+            n_src = n_prompt + src_batch if R >= 2 * src_batch else src_batch
             te16 = torch.zeros(n_src, n_tok, ted, dtype=torch.float16, device=self.dev)
             mask_u8 = torch.ones(n_src, L, dtype=torch.uint8, device=self.dev)
             tok = self.new(n_src, 1, L, cd, zero=True)              # rows >= n_tok stay zero (F.pad, ip.py:1617)
-            te = Act(te16, src_batch, 1, n_tok, ted, ted, n_tok * ted)
-            tok_head = Act(tok.t, src_batch, 1, n_tok, cd, cd, L * cd)
+            te = Act(te16, n_prompt, 1, n_tok, ted, ted, n_tok * ted)
+            tok_head = Act(tok.t, n_prompt, 1, n_tok, cd, cd, L * cd)
             ops.igemm(plan, te, W.conv("text_to_cond", u.text_to_cond, split=SPLIT_STATIC), tok_head, label="text_to_cond")
-            if n_src > src_batch:
+            if n_src > n_prompt:
                 # the negative prompts' projection: the same launch on the second set of source rows, in a plan of its own that runs ahead of
                 # this one only when a request brings a negative prompt (without one nothing reads those rows, and the launches are the
                 # same as before)
                 neg_plan = Plan("unet-static-negative")
-                ops.igemm(neg_plan, Act(te16, src_batch, 1, n_tok, ted, ted, n_tok * ted, src_batch * n_tok * ted),
+                ops.igemm(neg_plan, Act(te16, src_batch, 1, n_tok, ted, ted, n_tok * ted, n_prompt * n_tok * ted),
                           W.conv("text_to_cond", u.text_to_cond, split=SPLIT_STATIC),
-                          Act(tok.t, src_batch, 1, n_tok, cd, cd, L * cd, src_batch * L * cd), label="text_to_cond(negative)")
+                          Act(tok.t, src_batch, 1, n_tok, cd, cd, L * cd, n_prompt * L * cd), label="text_to_cond(negative)")
             xt = self.new(R, 1, L, cd)
             ops.select_rows(plan, tok.t, W.f16("null_text_embed", lambda: u.null_text_embed[0]), mask_u8, self.src_idx, self.keep_u8, xt.t,
                             R=R, L=L, C=cd, label="text_keep_select")
@@ -1281,8 +1285,17 @@ class UnetEngine:
         return lat
 
     # ------------------------------------------------------------------------------------------ run-time API
+    @property
+    def n_prompts(self) -> int:
+        """K: the prompt sets of this engine's rows — R = (K + 1) src_batch with the null rows last; 1 for an unguided engine (R = src_batch)."""
+        return max(1, self.R // self.src_batch - 1)
+
+    @property
+    def n_prompt_rows(self) -> int:
+        return self.n_prompts * self.src_batch
+
     def set_conditioning(self, *, text_embeds, text_mask, keep, lowres_noise_times, negative_text_embeds=None, negative_text_mask=None,
-                         negative_rows=None):
+                         negative_rows=None, extra_prompts=None):
         """Stage the timestep-invariant inputs and run the static plan.  `keep`: bool [R] (True = conditional row).
 
         negative_text_embeds [src_batch | 1, n, text_embed_dim] (+ negative_text_mask, default any(embeds != 0, -1)): a second prompt for the
@@ -1290,18 +1303,32 @@ class UnetEngine:
         null_text_embed, Perceiver pooling, the text hiddens' MLP, their K/V rows) instead of the learned null conditioning: the guided
         output is neg + (pos - neg) * cond_scale.  A batch-1 negative prompt is repeated over the batch.  `negative_rows`: bool [src_batch],
         the samples that have one (merged requests); the others keep the learned null rows.  Prompt and negative prompt share the static
-        plan of the longer one's token count: the shorter is zero-padded and its padded positions are masked."""
+        plan of the longer one's token count: the shorter is zero-padded and its padded positions are masked.
+
+        extra_prompts: the prompts 1 .. K - 1 of a composed engine (R = (K + 1) src_batch, K > 1), a list of K - 1 (embeds [src_batch | 1, n,
+        text_embed_dim], mask or None).  Rows [k src_batch, (k + 1) src_batch) run the conditional path on prompt k (prompt 0 = text_embeds),
+        the last src_batch rows are the null rows (or the negative prompt's).  All prompts share the static plan of the longest one."""
         R, u, src_batch = self.R, self.unet, self.src_batch
         n_tok = n_pos = n_neg = 0
         neg = negative_text_embeds
+        K, n_prompt = self.n_prompts, self.n_prompt_rows
+        extra = []
         if self.has_text:
             assert text_embeds is not None, "this engine was planned with text conditioning"
             text_embeds = text_embeds[:, : u.max_text_len]
             n_tok = n_pos = text_embeds.shape[1]
             assert text_embeds.shape[0] == src_batch
+        assert len(extra_prompts or ()) == (K - 1 if self.has_text else 0), \
+            f"extra_prompts: {len(extra_prompts or ())} given, this engine's {R} rows over a batch of {src_batch} hold {K} prompt sets"
+        for emb, mask in (extra_prompts or ()):
+            assert emb.ndim == 3 and emb.shape[0] in (1, src_batch), f"extra_prompts: batch {emb.shape[0]} is neither 1 nor the prompts' {src_batch}"
+            assert emb.shape[-1] == text_embeds.shape[-1], f"extra_prompts: embedding width {emb.shape[-1]}, the prompts have {text_embeds.shape[-1]}"
+            emb = emb[:, : u.max_text_len]
+            extra.append((emb, torch.any(emb != 0., dim=-1) if mask is None else mask))
+            n_tok = n_pos = max(n_pos, emb.shape[1])
         if neg is not None:
             assert self.has_text, "negative_text_embeds: this engine was planned without text conditioning"
-            assert R == 2 * src_batch, "negative_text_embeds: only a guided engine (rows = 2 * batch) has null rows to put a prompt on"
+            assert R >= 2 * src_batch, "negative_text_embeds: only a guided engine (rows = (K + 1) * batch) has null rows to put a prompt on"
             assert neg.ndim == 3 and neg.shape[0] in (1, src_batch), \
                 f"negative_text_embeds: batch {neg.shape[0]} is neither 1 nor the prompts' {src_batch}"
             assert neg.shape[-1] == text_embeds.shape[-1], \
@@ -1314,15 +1341,17 @@ class UnetEngine:
         if n_tok not in self._static_plans:
             self._static_plans[n_tok] = self._build_static_plan(n_tok)
         plan, te16, mask_u8, neg_plan = self._static_plans[n_tok]
+        # row r of prompt set k reads source row k src_batch + r % src_batch = r; the null rows read (and, kept out, ignore) the main prompt's
+        src_idx = torch.arange(R, dtype=torch.int32)
+        src_idx[n_prompt:] %= src_batch
         if neg is None:
             self.keep_u8.copy_(keep.to(torch.uint8))
-            self.src_idx.copy_(torch.arange(R, dtype=torch.int32) % src_batch)
+            self.src_idx.copy_(src_idx)
         else:
             keep_u8 = keep.to(torch.uint8).cpu().clone()
-            src_idx = torch.arange(R, dtype=torch.int32) % src_batch
             has = torch.ones(src_batch, dtype=torch.bool) if negative_rows is None else negative_rows.to(torch.bool).cpu().reshape(src_batch)
-            keep_u8[src_batch:][has] = 1
-            src_idx[src_batch:][has] += src_batch            # < 2 * src_batch: the rows te16 / mask_u8 / tok were allocated with
+            keep_u8[n_prompt:][has] = 1
+            src_idx[n_prompt:][has] += n_prompt              # < n_prompt + src_batch: the rows te16 / mask_u8 / tok were allocated with
             self.keep_u8.copy_(keep_u8)
             self.src_idx.copy_(src_idx)
         if self.lowres:
@@ -1351,8 +1380,10 @@ class UnetEngine:
                 mask_u8[row0:row0 + src_batch].copy_(m)
 
             stage(0, text_embeds, text_mask)
+            for k, (emb, mask) in enumerate(extra):
+                stage((k + 1) * src_batch, emb, mask)
             if neg is not None:
-                stage(src_batch, neg, negative_text_mask)
+                stage(n_prompt, neg, negative_text_mask)
         self._last_static = [neg_plan, plan] if neg is not None else [plan]
         if not self.dry:
             for pl in self._last_static:

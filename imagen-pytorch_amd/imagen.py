@@ -144,6 +144,8 @@ class _Call:
     guidance_interval: Any = None                      # ... (t_lo, t_hi), one or per unet: the steps outside it run unguided — Imagen._guidance_of
     guidance_rescale: Any = None                       # extension: phi of guidance rescale, one or per unet — Imagen._guide_of
     guidance_apg: Any = None                           # ... dict(eta=, norm_threshold=, momentum=) of projected guidance, one or per unet
+    compose: Any = None                                # extension: further prompts, [dict(text_embeds= | texts=, text_masks=, weight=, mask=), ...] — Imagen._compose_of
+    compose_mask: Any = None                           # ... the main prompt's mask, [B | 1, H, W] or [H, W] in [0, 1]
     # not public keywords: set by sample_requests, the sample_pipelined workers and ElucidatedImagen._call
     negative_rows: Optional[torch.Tensor] = None       # bool [rows]: the samples the merged negative prompt applies to
     pipelined_stage: bool = False                      # one stage of a cascade whose guidance scales sample_pipelined has checked as a whole
@@ -156,6 +158,7 @@ class _Call:
     solver: Any = None                                 # None (the ancestral sampler), or per unet (sampler, steps, eta)
     guidance: Any = None                               # per unet: None (cond_scale as it stands) | the fp32 [steps] scales of a schedule that varies
     guide: Any = None                                  # None, or per unet: None | ('rescale', phi) | ('apg', eta, norm_threshold, momentum)
+    composed: Any = None                               # None, or dict(K, prompts [(embeds, masks)] of the prompts 1 .. K - 1, weights per unet fp32 [K, B], masks None | K x (None | fp32 [B | 1, H, W]))
     sizes: Any = None                                  # per unet: image_sizes[i] (int, square), or (H, W) where image_shapes says H != W
     frames: int = 0                                    # video_frames of a video cascade, else 0
     known: Any = None                                  # inpainting: the normalised known image / clip (reference layout) and its mask
@@ -373,6 +376,9 @@ class Imagen(nn.Module):
         solver = self._solver_of(common.get('sampler'), common.get('sample_steps'), common.get('eta'))
         self._guidance_of(common.get('guidance_schedule'), common.get('guidance_interval'))
         self._guide_of(common.get('guidance_rescale'), common.get('guidance_apg'))
+        if common.get('compose') is not None or common.get('compose_mask') is not None or any('compose' in r or 'compose_mask' in r for r in requests):
+            raise ValueError('sample_requests: compose / compose_mask inside or beside merged requests; the merged rows share one stage of 2 rows '
+                             'per sample, composed prompts run K + 1: sample composed prompts with sample() or sample_pipelined()')
         for k in ('guidance_schedule', 'guidance_interval', 'guidance_rescale', 'guidance_apg'):
             if any(k in r for r in requests):
                 raise ValueError(f'sample_requests: {k} inside a request; merged requests run one plan, so it is a common keyword, as cond_scale is')
@@ -444,6 +450,8 @@ class Imagen(nn.Module):
             vectors, scales = self._guidance_vectors(self._guidance_of(kw.get('guidance_schedule'), kw.get('guidance_interval')),
                                                      _cast_tuple(kw.get('cond_scale', 1.), n_stages), solver, inpainting, 0, n_stages)
             self._check_guide(self._guide_of(kw.get('guidance_rescale'), kw.get('guidance_apg')), scales, vectors, inpainting, 0, n_stages)
+            if kw.get('compose') is not None or kw.get('compose_mask') is not None:
+                self._resolve(self._call(**kw))          # composed prompts: every refusal of the whole cascade, before a thread starts (no launch)
             jobs.append(kw)
         if n_stages == 1 or len(jobs) == 0:
             return [self.sample(**kw) for kw in jobs]
@@ -530,20 +538,22 @@ class Imagen(nn.Module):
 
     def _new_stage(self, key: tuple, idx: int, B: int, device, *, cfg: bool, with_text: bool, inject_noise: bool, sample_offset: int,
                    resample_times: int, frames: int, prompt_frames: tuple, tables: Callable, size=None, buffers: tuple = (),
-                   share: Optional[dict] = None):
+                   share: Optional[dict] = None, prompts: int = 1):
         """What both samplers' `_build_stage` do first.  Returns (the cached stage of `key`, False) while its engine is not stale; else
         (a new stage dict, True): the engine (image or video), the sampler state (SHARED_STATE), the engine bound to the step counter and to
         `coef` = tables[0], the per-request time table where it applies, the buffers of inpainting.  EVERY key the run side reads is present
         (None where unused); the sampler adds its plan(s) and files the stage.  tables: () -> the sampler's device tables, [rows, 8] each,
         the per-evaluation one first; called only on a cache miss.  buffers: which of the optional [B, n] state buffers ('x0_thr',
-        'x0_prev') the step needs.  share: the stage whose sampler state this one runs on (the unguided sibling of a stage with a guidance
+        'x0_prev') the step needs.  prompts: K, the prompt sets of a guided stage — (K + 1) B denoiser rows, the null rows last; 1 is plain
+        guidance's 2 B.  share: the stage whose sampler state this one runs on (the unguided sibling of a stage with a guidance
         schedule): the very objects of `share` are this stage's own, and its engine reads that stage's `x_in` / low-res image."""
         st = self._stages.get(key)
         if st is not None and not st['eng'].stale():
             return st, False
         unet, S, R = self.unets[idx], self.image_sizes[idx] if size is None else size, resample_times
-        rows = 2 * B if cfg else B
+        rows = (prompts + 1) * B if cfg else B
         video = isinstance(unet, Unet3D)
+        assert prompts == 1 or (cfg and not video), 'composed prompts run on the guided image engine'
         if video:
             # Imagen-Video stage: the sampler state is the engine's frame-major clip (b, f, c, h, w); every sampler kernel is
             # elementwise per sample (the dynamic threshold is one quantile over the whole clip, ip.py:1921, 2097-2101), so only
@@ -578,9 +588,10 @@ class Imagen(nn.Module):
             step_plan = eng.enable_time_table(coef, step_ptr) or step_plan
         zeros = lambda: torch.zeros_like(eng.x_in)
         # (x: the image the sampler steps.  scales / sibling: Imagen's guidance schedules, None for every stage without one, under both samplers;
-        # guide / avg / head: Imagen's guidance rescale | projected guidance, its running average and the plan that zeroes it at a run's start)
+        # guide / avg / head: Imagen's guidance rescale | projected guidance, its running average and the plan that zeroes it at a run's start;
+        # compose: Imagen's composed prompts, the per-call weights [K, B] and masks [K, B, hw] | None that COMPOSE_X0 reads)
         return dict(eng=eng, step_plan=step_plan, plan=None, graph=None, coef=coef, **state, x=eng.x_in,
-                    key=key, scales=None, sibling=None, guide=None, avg=None, head=None,
+                    key=key, scales=None, sibling=None, guide=None, avg=None, head=None, compose=None,
                     n=n, S=S, R=R, video=video, frames=frames, sample_offset=sample_offset,
                     # inpainting: the known image (video: frame-major clip), normalised, at this stage's size; 1.0 where it is kept
                     known=zeros() if R else None, mask=zeros() if R else None,
@@ -604,7 +615,7 @@ class Imagen(nn.Module):
     def _emit_step(self, plan: Plan, st: dict, idx: int, *, cfg: int, cond_scale: float, inject_noise: bool) -> dict:
         """One sampling step of stage `st`, on the sampler state it holds, into `plan`:
 
-            [inpaint.blend]  eng.step_plan  CFG_X0 | GUIDE_X0 (reduce, apply)  [QUANTILE]  update  [dpmpp_2m.history]  [inpaint.renoise]
+            [inpaint.blend]  eng.step_plan  CFG_X0 | GUIDE_X0 (reduce, apply) | COMPOSE_X0  [QUANTILE]  update  [dpmpp_2m.history]  [inpaint.renoise]
 
         The update is the DDPM_UPDATE launch, or — st['solver'] = (sampler, steps, eta) — one LINCOMB x = w0 x + w1 thr(x0) + w3 x0_prev
         (+ the noise term of 'ddim' at eta > 0), which also emits thr(x0) (`thr1_out`: the next step's self-conditioning input and, for
@@ -623,7 +634,11 @@ class Imagen(nn.Module):
                         stream_id=idx | 0x100, sample_offset=st['sample_offset'], seed_ptr=seed_dev, label="inpaint.blend")
         plan.extend(st['step_plan'])
         guide = st['guide'] if cfg else None             # (an unguided step is CFG_X0's, and leaves the running average alone)
-        if guide is None:
+        if st['compose'] is not None:
+            H, Wd = eng.x_in.shape[-2:]
+            ops.compose_x0(plan, eng.x_in, eng.out, coef, step_ptr, x0, absx0, B=B, n_per_sample=n, hw=H * Wd, weights=st['compose']['weights'],
+                           masks=st['compose']['masks'], objective=self.pred_objectives[idx])
+        elif guide is None:
             ops.cfg_x0(plan, eng.x_in, eng.out, coef, step_ptr, x0, absx0, B=B, n_per_sample=n, cfg=cfg, cond_scale=float(cond_scale),
                        objective=self.pred_objectives[idx])
         else:
@@ -657,7 +672,7 @@ class Imagen(nn.Module):
 
     def _build_stage(self, idx: int, B: int, device, *, cond_scale: float, with_text: bool, inject_noise: bool, sample_offset: int,
                      resample_times: int = 0, frames: int = 0, prompt_frames: tuple = (0, 0), size=None, solver: Optional[tuple] = None,
-                     guidance: Optional[torch.Tensor] = None, guide: Optional[tuple] = None):
+                     guidance: Optional[torch.Tensor] = None, guide: Optional[tuple] = None, compose: Optional[tuple] = None):
         """Build (or fetch) the per-timestep plan + graph of stage `idx` for batch B, at image_sizes[idx] or at `size` (an int, or (H, W)):
         form the key, get or make the stage (`_new_stage`), emit its step (`_emit_step`), file it.
 
@@ -675,7 +690,11 @@ class Imagen(nn.Module):
 
         guide = ('rescale', phi) | ('apg', eta, norm_threshold, momentum) (Imagen._guide_of): the guided steps launch GUIDE_X0 in place of
         CFG_X0; the setting ends the stage's key.  Projected guidance with momentum keeps its running average in st['avg'], zeroed by the
-        one-launch plan st['head'] that `_rewind` runs at the start of every run; the unguided sibling neither reads nor writes it."""
+        one-launch plan st['head'] that `_rewind` runs at the start of every run; the unguided sibling neither reads nor writes it.
+
+        compose = (K, masks present) (Imagen._compose_of): the stage runs (K + 1) B denoiser rows and COMPOSE_X0 in place of CFG_X0, whatever
+        `cond_scale` is — the main prompt's weight like every other lives in st['compose']['weights'] (device memory, filled per call by
+        `_prepare_stage`, as the masks are), so the key holds no scale and ends with (K, masks present)."""
         sched = self.noise_schedulers[idx]
         T, R = sched.num_timesteps if solver is None else solver[1], resample_times
         assert solver is None or not R, 'the solvers do not cover inpainting'
@@ -689,8 +708,8 @@ class Imagen(nn.Module):
                                 self.pred_objectives[idx], self.dynamic_thresholding_percentile, resample_times, frames, prompt_frames,
                                 self._lane, solver)
 
-        def stage(key, cfg, scale, scales=None, share=None):
-            st, built = self._new_stage(key, idx, B, device, cfg=bool(cfg), with_text=with_text, inject_noise=inject_noise, sample_offset=sample_offset,
+        def stage(key, cfg, scale, scales=None, share=None, prompts=1):
+            st, built = self._new_stage(key, idx, B, device, cfg=bool(cfg), prompts=prompts, with_text=with_text, inject_noise=inject_noise, sample_offset=sample_offset,
                                         resample_times=R, frames=frames, prompt_frames=prompt_frames, size=size, buffers=buffers, share=share,
                                         tables=functools.partial(self._step_tables, idx, device, solver=solver, R=R, inject_noise=inject_noise,
                                                                  guidance=guidance))
@@ -702,10 +721,17 @@ class Imagen(nn.Module):
                 if cfg and guide is not None and guide[0] == 'apg' and guide[3] != 0.:
                     st['avg'], st['head'] = torch.zeros(B, st['n'], device=device), Plan(f"stage{idx}-head")
                     ops.memset32(st['head'], st['avg'], 0)
+                if compose is not None:
+                    H, Wd = st['eng'].x_in.shape[-2:]
+                    st['compose'] = dict(K=compose[0], weights=torch.zeros(compose[0], B, device=device),
+                                         masks=torch.ones(compose[0], B, H * Wd, device=device) if compose[1] else None)
                 st.update(self._emit_step(st['plan'], st, idx, cfg=cfg, cond_scale=scale, inject_noise=inject_noise))
                 self._stages[key] = st
             return st, built
 
+        if compose is not None:
+            assert guidance is None and guide is None and not R, 'composed prompts take the plain guided step'
+            return stage(key_at(0.) + ('compose', (int(compose[0]), bool(compose[1]))), 1, cond_scale, prompts=int(compose[0]))[0]
         if guidance is None:
             return stage(key_at(cond_scale) + suffix, int(cond_scale != 1.), cond_scale)[0]
         key = key_at(cond_scale) + (('guidance', guidance.numpy().tobytes()),) + suffix   # (a call without a schedule keeps the key it always had)
@@ -1000,6 +1026,13 @@ class Imagen(nn.Module):
                                                        #   (Sadat et al. 2024), in x0 space; both: one value for every unet, or a tuple with one
                                                        #   entry (or None) per unet; not both on one unet.  They act on the guided steps (GUIDE_X0
                                                        #   in place of CFG_X0); a distinct setting is a cached stage of its own
+        compose=None,                                  # extension: composed prompts (Liu et al. 2022).  A list of up to 3 dicts, each one more prompt:
+                                                       #   dict(text_embeds= | texts=, text_masks=, weight=, mask=).  The call's own prompt is prompt 0 at
+                                                       #   weight cond_scale; the guided output is nul + sum_k w_k m_k (cond_k - nul) (COMPOSE_X0 in place
+                                                       #   of CFG_X0, (K + 1) B denoiser rows).  weight: a float, a per-unet tuple or a [B] tensor, negative =
+                                                       #   negation; mask: [B | 1, H, W] or [H, W] in [0, 1], resized to every stage (nearest): regional
+                                                       #   prompts.  Weights and masks are per-call state: every call of one K shares the stage and its graph
+        compose_mask=None,                             #   ... the mask of the call's own prompt
     ):
         return self._sample(self._call(**{k: v for k, v in locals().items() if k != 'self'}))   # (the keywords, as given)
 
@@ -1110,6 +1143,104 @@ class Imagen(nn.Module):
             raise ValueError('guidance_rescale / guidance_apg: no stage of this call that has a setting is guided (cond_scale is 1 and there is '
                              'no schedule), so the keyword would be silently ignored')
         return given
+
+    _compose_refusal = None         # ElucidatedImagen: why `compose=` is not its keyword
+
+    def _compose_of(self, c: _Call):
+        """`compose=` / `compose_mask=` of one call whose text, batch, sizes, cond_scale and guidance are resolved: None without the keyword,
+        else dict(K, prompts, weights, masks) — prompts: the (embeds, masks) of the prompts 1 .. K - 1 on the device, batch 1 or B; weights:
+        per unet an fp32 [K, B] tensor (row 0 the main prompt's cond_scale); masks: None when no prompt has one, else K entries None | fp32
+        [B | 1, H, W].  Every refusal is a ValueError; nothing is built or launched."""
+        if c.compose is None and c.compose_mask is None:
+            return None
+        n, B, kmax = len(self.unets), c.batch_size, ops.ENUMS["IMAGEN_COMPOSE_MAX"]
+        if self._compose_refusal is not None:
+            raise ValueError(f'compose: {self._compose_refusal}')
+        if not isinstance(c.compose, (list, tuple)) or not c.compose or not all(isinstance(e, dict) for e in c.compose):
+            raise ValueError('compose: a non-empty list of dicts(text_embeds= | texts=, text_masks=, weight=, mask=), one per further prompt '
+                             '(compose_mask alone composes nothing)')
+        if len(c.compose) + 1 > kmax:
+            raise ValueError(f'compose: {len(c.compose)} entries + the call\'s own prompt are {len(c.compose) + 1} prompts, at most {kmax} are composed')
+        given = [k for k in ('guidance_schedule', 'guidance_interval', 'guidance_rescale', 'guidance_apg') if getattr(c, k) is not None]
+        if given:
+            raise ValueError(f"compose with {', '.join(given)}: those act on the one scale of plain guidance (CFG_X0 / GUIDE_X0); composed prompts "
+                             f"carry a weight per prompt at a fixed value")
+        if c.inpaint_images is not None or c.inpaint_masks is not None:
+            raise ValueError('compose with inpainting: the resample loop (ip.py:2237-2275) is planned on the two-branch step; inpaint with one prompt')
+        if c.conditioning is not None:
+            raise ValueError('compose with a `conditioning` handle: a handle stages one prompt per sample; pass text_embeds / texts with compose')
+        if isinstance(c.seed, (list, tuple)) or c.negative_rows is not None:
+            raise ValueError('compose inside merged requests (sample_requests): not covered')
+        if any(isinstance(u, Unet3D) for u in self.unets):
+            raise ValueError('compose: this cascade has a Unet3D stage; composed prompts run on the image engine (UnetEngine) only')
+        if not self.can_classifier_guidance:
+            raise ValueError('compose: imagen was not trained with conditional dropout (cond_drop_prob == 0) and has no null branch to compose against')
+        if self.unconditional or c.text_embeds is None:
+            raise ValueError('compose: this model was built with condition_on_text=False, there is no text branch to compose prompts on')
+        first, last = c.start_at_unet_number - 1, n if c.stop_at_unet_number is None else c.stop_at_unet_number
+        for idx in range(first, last):
+            if not getattr(self.unets[idx], 'cond_on_text', False):
+                raise ValueError(f'compose: unet {idx + 1} has no text branch (cond_on_text=False), there is nothing to compose')
+
+        def weight_of(v, what):
+            """-> per unet an fp32 [B] tensor"""
+            if isinstance(v, torch.Tensor) and v.ndim == 1:
+                if v.shape[0] != B:
+                    raise ValueError(f'{what}: a [B] tensor of {v.shape[0]} weights, the batch is {B}')
+                per = (v.detach().float().cpu(),) * n
+            else:
+                number = lambda x: (isinstance(x, (int, float)) and not isinstance(x, bool)) or (isinstance(x, torch.Tensor) and x.ndim == 0)
+                if isinstance(v, (list, tuple)):
+                    if len(v) != n or not all(number(x) for x in v):
+                        raise ValueError(f'{what} = {v!r}: a float, a tuple of one float per unet ({n}), or a [B] tensor')
+                elif not number(v):
+                    raise ValueError(f'{what} = {v!r}: a float, a tuple of one float per unet ({n}), or a [B] tensor')
+                else:
+                    v = (v,) * n
+                per = tuple(torch.full((B,), float(x), dtype=torch.float32) for x in v)
+            if not all(bool(torch.isfinite(w).all()) for w in per):
+                raise ValueError(f'{what}: weights must be finite')
+            return per
+
+        def mask_of(m, what):
+            if m is None:
+                return None
+            if not isinstance(m, torch.Tensor) or m.ndim not in (2, 3) or (m.ndim == 3 and m.shape[0] not in (1, B)) or 0 in m.shape:
+                raise ValueError(f'{what}: a [B | 1, H, W] or [H, W] tensor (B = {B})' + (f', got {tuple(m.shape)}' if isinstance(m, torch.Tensor) else ''))
+            m = m.detach().float().cpu()
+            if not bool(((m >= 0.) & (m <= 1.)).all()):          # (also refuses nan)
+                raise ValueError(f'{what}: values outside [0, 1]')
+            return m[None] if m.ndim == 2 else m
+
+        prompts, weights, masks = [], [weight_of(tuple(c.cond_scale), 'cond_scale')], [mask_of(c.compose_mask, 'compose_mask')]
+        for i, e in enumerate(c.compose):
+            unknown = set(e) - {'text_embeds', 'texts', 'text_masks', 'weight', 'mask'}
+            if unknown:
+                raise ValueError(f'compose[{i}]: unknown keys {sorted(unknown)}; text_embeds | texts, text_masks, weight, mask')
+            texts, emb, tm = e.get('texts'), e.get('text_embeds'), e.get('text_masks')
+            if (texts is None) == (emb is None):
+                raise ValueError(f'compose[{i}]: one of text_embeds and texts')
+            if texts is not None:
+                texts = [texts] if isinstance(texts, str) else list(texts)
+                if not all(map(len, texts)):
+                    raise ValueError(f'compose[{i}].texts: text cannot be empty')
+                emb, tm = self.encode_text(texts, return_attn_mask=True)
+            kw = f'compose[{i}].text_embeds' if texts is None else f'compose[{i}].texts'
+            if not isinstance(emb, torch.Tensor) or emb.ndim != 3 or emb.shape[-1] != self.text_embed_dim:
+                raise ValueError(f"{kw}: invalid text embedding shape {tuple(emb.shape) if isinstance(emb, torch.Tensor) else emb!r} "
+                                 f"(should be (b, n, {self.text_embed_dim}))")
+            if emb.shape[0] not in (1, B):
+                raise ValueError(f"{kw}: batch {emb.shape[0]} is neither 1 nor the prompts' {B}")
+            if tm is not None and tuple(tm.shape) != tuple(emb.shape[:2]):
+                raise ValueError(f"compose[{i}].text_masks: shape {tuple(tm.shape)} does not match the prompt's {tuple(emb.shape[:2])}")
+            emb = emb.to(c.device)
+            prompts.append((emb, tm.to(c.device) if tm is not None else torch.any(emb != 0., dim=-1)))
+            weights.append(weight_of(e.get('weight', 1.), f'compose[{i}].weight'))
+            masks.append(mask_of(e.get('mask'), f'compose[{i}].mask'))
+        per_unet = [torch.stack([w[idx] for w in weights]) for idx in range(n)]
+        if not c.pipelined_stage and all(c.cond_scale[idx] == 1. and not bool(per_unet[idx][1:].any()) for idx in range(first, last)):
+            raise ValueError('compose: cond_scale is 1 and every further weight is 0 on every stage of this call, so the keyword would be silently ignored')
+        return dict(K=len(prompts) + 1, prompts=prompts, weights=per_unet, masks=masks if any(m is not None for m in masks) else None)
 
     def _solver_of(self, sampler=None, sample_steps=None, eta=None):
         """The solver keywords of one call, checked: None for the ancestral sampler ('ddpm', the default: one step per training timestep),
@@ -1324,13 +1455,14 @@ class Imagen(nn.Module):
         c.guide = self._check_guide(self._guide_of(c.guidance_rescale, c.guidance_apg), c.cond_scale, c.guidance,
                                     c.inpaint_images is not None or c.inpaint_masks is not None, c.start_at_unet_number - 1,
                                     num_unets if c.stop_at_unet_number is None else c.stop_at_unet_number, scales=not c.pipelined_stage)
+        c.composed = self._compose_of(c)
         if c.seed is None:
             c.seed = self._next_seed()
         # the negative prompt of this call: resolved and checked here, before any stage is built or anything is launched
         if c.negative is not None:
             last = num_unets if c.stop_at_unet_number is None else c.stop_at_unet_number
             scales = [cs if g is None else None for cs, g in zip(c.cond_scale, c.guidance)]      # (None: a schedule that varies, so not 1)
-            scales = None if c.pipelined_stage else scales[c.start_at_unet_number - 1:last]
+            scales = None if c.pipelined_stage or c.composed is not None else scales[c.start_at_unet_number - 1:last]   # (a composed stage has null rows at any cond_scale)
             c.neg_embeds, c.neg_masks, c.neg_rows = self._check_negative(c.negative, c.batch_size, scales, device)
 
         if c.start_at_unet_number > 1:
@@ -1411,6 +1543,9 @@ class Imagen(nn.Module):
             extra['guidance'] = c.guidance[idx]
         if c.guide is not None and c.guide[idx] is not None and (cs != 1. or 'guidance' in extra):     # (an unguided stage has nothing to rescale)
             extra['guide'] = c.guide[idx]
+        comp = c.composed if with_text else None
+        if comp is not None:
+            extra['compose'] = (comp['K'], comp['masks'] is not None)
         st = self._stage(idx, batch_size, device, cond_scale=cs, with_text=with_text, inject_noise=noise_fn is not None,
                          sample_offset=c.sample_offset, resample_times=c.inpaint_resample_times if c.known is not None else 0,
                          frames=c.frames // self.temporal_downsample_factor[idx] if isinstance(unet, Unet3D) else 0,
@@ -1462,17 +1597,29 @@ class Imagen(nn.Module):
             ops.lowres_prep(prep, as_images(src), as_images(aug), as_images(eng.lowres_in), alpha=a, sigma=s)
             prep.keep += [src, aug, eng.lowres_in]
             prep.run()
+        if comp is not None:                         # the call's weights and masks, into the buffers COMPOSE_X0 reads: no launch list changes
+            st['compose']['weights'].copy_(comp['weights'][idx])
+            if comp['masks'] is not None:
+                H, Wd = eng.x_in.shape[-2:]
+                for k, m in enumerate(comp['masks']):
+                    if m is None:
+                        st['compose']['masks'][k].fill_(1.)
+                    else:                             # nearest, as the cascade resizes its images (nearest_indices), once per stage and call
+                        m = m[:, nearest_indices(m.shape[1], H)][:, :, nearest_indices(m.shape[2], Wd)]
+                        st['compose']['masks'][k].copy_(m.expand(batch_size, -1, -1).reshape(batch_size, H * Wd))
         cond = c.conditioning
         stamp = None if cond is None else (cond.token, None if lowres_logsnr is None else float(lowres_logsnr[0]))
         for eng in engines:
             rows = eng.R
             keep = torch.ones(rows, dtype=torch.bool)
-            if rows == 2 * batch_size:
-                keep[batch_size:] = False            # second half = null-conditioned CFG branch (cond_drop_prob = 1, ip.py:1521)
+            if rows > batch_size:
+                keep[rows - batch_size:] = False     # the last B rows = null-conditioned CFG branch (cond_drop_prob = 1, ip.py:1521)
             if stamp is None or getattr(eng, '_cond_stamp', None) != stamp:
                 neg_kw = {}
-                if c.neg_embeds is not None and with_text and rows == 2 * batch_size:     # (a stage at cond_scale 1 has no null rows)
+                if c.neg_embeds is not None and with_text and rows > batch_size:          # (a stage at cond_scale 1 has no null rows)
                     neg_kw = dict(negative_text_embeds=c.neg_embeds, negative_text_mask=c.neg_masks, negative_rows=c.neg_rows)
+                if comp is not None:
+                    neg_kw['extra_prompts'] = comp['prompts']
                 eng.set_conditioning(text_embeds=c.text_embeds if with_text else None, text_mask=c.text_masks if with_text else None,
                                      keep=keep, lowres_noise_times=lowres_logsnr, **neg_kw)
                 eng.static_runs = getattr(eng, 'static_runs', 0) + 1

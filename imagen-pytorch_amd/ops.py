@@ -1418,6 +1418,35 @@ def guide_x0(plan: Plan, x, pred, coef, step_ptr, x0, absx0, *, B, n_per_sample,
     return out
 
 
+def compose_x0(plan: Plan, x, pred, coef, step_ptr, x0, absx0, *, B, n_per_sample, hw, weights, masks=None, objective: str = "noise", label: str = ""):
+    """COMPOSE_X0 (include/imagen_hip.h): K weighted, optionally masked prompts against one null branch, then CFG_X0's x0.  pred fp32
+    [(K + 1) B, n] branch-major, the null rows last; weights fp32 [K, B] on the device (read at every launch: refill them between runs of one
+    captured plan); masks fp32 [K, B, hw] or None.  K comes from `weights`.  Returns the struct."""
+    if not (isinstance(weights, torch.Tensor) and weights.dtype == torch.float32 and weights.ndim == 2 and weights.is_contiguous()):
+        raise ValueError("compose_x0: weights is a contiguous fp32 [K, B] tensor")
+    K = int(weights.shape[0])
+    if not 1 <= K <= ENUMS["IMAGEN_COMPOSE_MAX"]:
+        raise ValueError(f"compose_x0: K = {K} prompts; 1 .. {ENUMS['IMAGEN_COMPOSE_MAX']}")
+    if int(weights.shape[1]) != int(B):
+        raise ValueError(f"compose_x0: weights is [K, {weights.shape[1]}], the batch is {B}")
+    if int(hw) <= 0 or int(n_per_sample) <= 0 or int(n_per_sample) % int(hw) != 0:
+        raise ValueError(f"compose_x0: n_per_sample = {n_per_sample} is no positive multiple of hw = {hw} (the state is NCHW: n = C * hw)")
+    if masks is not None and not (isinstance(masks, torch.Tensor) and masks.dtype == torch.float32 and masks.is_contiguous()
+                                  and tuple(masks.shape) == (K, int(B), int(hw))):
+        raise ValueError(f"compose_x0: masks is a contiguous fp32 [K, B, hw] = [{K}, {B}, {hw}] tensor or None")
+    if objective not in OBJECTIVES:
+        raise ValueError(f"compose_x0: objective = {objective!r}; {' | '.join(repr(o) for o in OBJECTIVES)}")
+    if pred.numel() < (K + 1) * int(B) * int(n_per_sample):
+        raise ValueError(f"compose_x0: pred holds {pred.numel()} elements, (K + 1) B n = {(K + 1) * int(B) * int(n_per_sample)} are read")
+    _abi.require_ext_op(ENUMS["IMAGEN_OP_COMPOSE_X0"], "compose_x0")
+    p = STRUCTS["ImagenComposeX0Params"]()
+    p.x, p.pred, p.coef, p.step_ptr, p.x0, p.absx0 = x.data_ptr(), pred.data_ptr(), coef.data_ptr(), step_ptr.data_ptr(), x0.data_ptr(), absx0.data_ptr()
+    p.weights, p.masks = weights.data_ptr(), ptr(masks)
+    p.B, p.n_per_sample, p.hw, p.K, p.objective = int(B), int(n_per_sample), int(hw), K, OBJECTIVES[objective]
+    plan.add(p, label or "compose_x0", [x, pred, coef, step_ptr, x0, absx0, weights, masks])
+    return p
+
+
 def quantile(plan: Plan, absx0, out, scratch, *, B, n, q: float, label: str = ""):
     p = STRUCTS["ImagenQuantileParams"]()
     p.absx0, p.out, p.scratch, p.B, p.n, p.q = absx0.data_ptr(), out.data_ptr(), scratch.data_ptr(), B, n, q

@@ -425,7 +425,7 @@ class Unet(UnetBase):
             raise ValueError(f"{what} of {H} x {W}: both sides must be positive multiples of {d} (what the downsamples of this unet divide by)")
 
     def engine(self, batch_rows: int, src_batch: int, image_size, device, with_text: bool = True) -> "UnetEngine":  # noqa: F821
-        """Compiled kernel plan for `batch_rows` denoiser rows (= src_batch, or 2*src_batch with CFG) at image_size^2, or at H x W for
+        """Compiled kernel plan for `batch_rows` denoiser rows (= src_batch, 2*src_batch with CFG, or (K + 1)*src_batch for K composed prompt sets) at image_size^2, or at H x W for
         image_size = (H, W); (S, S) is the engine of S."""
         from .engine import UnetEngine
 

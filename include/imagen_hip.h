@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define IMAGEN_ABI_VERSION 15 /* 15 (additive, same number): GUIDE_X0, an op kind of the extension range (ImagenExtOpKind below: guidance rescale and projected guidance, Imagen.sample(guidance_rescale=, guidance_apg=)) — no existing struct or kind changed, every plan of before is launched as before; a library built before it answers imagen_sizeof(IMAGEN_OP_GUIDE_X0) == 0 and the host refuses the keyword with a "rebuild" message.  15: TEMPORAL_ATTENTION takes F <= 128 (clips of 33 .. 128 frames run on a tiled kernel; F <= 32 launches what it launched before; no struct changed), and head_dim 128 is accepted by ATTENTION / QNORM / KV_PREP / LINCTX / LINEAR_XATTN (Unet(attn_dim_head=128); no struct changed, no new op kind);  14: LINCTX, LINEAR_XATTN (LinearCrossAttention: Unet(use_linear_cross_attn=...); no struct of before changed);  13: ImagenLincombParams.thr1_out / thr3_out (LINCOMB writes out the thresholded operands it sums: the self-conditioning input of the ElucidatedImagen sampler; NULL = the launch of before);  12: ImagenTemporalAttentionParams.head_dim (the temporal attention of Imagen-Video at head dim 32, the reference's Unet3DConfig default; 0 = 64: plans of before are unchanged);  11: ImagenDdpmUpdateParams.row_keys (per-row Philox key + sample index: requests merged into one batch draw their own noise);  10: ImagenIgemmParams.pad_x1 (a KH x KW window with its own x padding: the causal temporal conv of Imagen-Video as ONE (3 x 1)-tap launch);  9: LINEAR_F32, SCALE_SHIFT ss_f32;  8: ROWCHAIN, the latency probes;  3: head_dim in the attention / QNORM / KV_PREP params; 4: DDPM_UPDATE x0_thr; 5: GCA_TAIL; 6: ACT_PREP self_stat, STEP_SLICE;
+#define IMAGEN_ABI_VERSION 15 /* 15 (additive, same number): COMPOSE_X0, a second kind of the extension range (composed prompts, Imagen.sample(compose=[...])), added as GUIDE_X0 was: imagen_sizeof(IMAGEN_OP_COMPOSE_X0) == 0 on a library from before it.  15 (additive, same number): GUIDE_X0, an op kind of the extension range (ImagenExtOpKind below: guidance rescale and projected guidance, Imagen.sample(guidance_rescale=, guidance_apg=)) — no existing struct or kind changed, every plan of before is launched as before; a library built before it answers imagen_sizeof(IMAGEN_OP_GUIDE_X0) == 0 and the host refuses the keyword with a "rebuild" message.  15: TEMPORAL_ATTENTION takes F <= 128 (clips of 33 .. 128 frames run on a tiled kernel; F <= 32 launches what it launched before; no struct changed), and head_dim 128 is accepted by ATTENTION / QNORM / KV_PREP / LINCTX / LINEAR_XATTN (Unet(attn_dim_head=128); no struct changed, no new op kind);  14: LINCTX, LINEAR_XATTN (LinearCrossAttention: Unet(use_linear_cross_attn=...); no struct of before changed);  13: ImagenLincombParams.thr1_out / thr3_out (LINCOMB writes out the thresholded operands it sums: the self-conditioning input of the ElucidatedImagen sampler; NULL = the launch of before);  12: ImagenTemporalAttentionParams.head_dim (the temporal attention of Imagen-Video at head dim 32, the reference's Unet3DConfig default; 0 = 64: plans of before are unchanged);  11: ImagenDdpmUpdateParams.row_keys (per-row Philox key + sample index: requests merged into one batch draw their own noise);  10: ImagenIgemmParams.pad_x1 (a KH x KW window with its own x padding: the causal temporal conv of Imagen-Video as ONE (3 x 1)-tap launch);  9: LINEAR_F32, SCALE_SHIFT ss_f32;  8: ROWCHAIN, the latency probes;  3: head_dim in the attention / QNORM / KV_PREP params; 4: DDPM_UPDATE x0_thr; 5: GCA_TAIL; 6: ACT_PREP self_stat, STEP_SLICE;
                                * 7: every launch carries sizeof(its params struct) (a stale mirror of a struct fails loudly), ImagenIgemmParams.dbg -> launcher_word, kernel families 6 and 7, ImagenAttentionParams.softmax_mode */
 
 typedef void* imagen_stream_t; /* hipStream_t */
@@ -75,7 +75,8 @@ enum ImagenOpKind {
  * with one: 0 = this library was built before the kind existed (imagen_launch refuses it as unknown). */
 enum ImagenExtOpKind {
   IMAGEN_OP_GUIDE_X0 = 33,     /* guided x0 with per-sample statistics: guidance rescale | adaptive projected guidance; two launches (reduce, apply) */
-  IMAGEN_OP_EXT_END = 34
+  IMAGEN_OP_COMPOSE_X0 = 34,   /* composed guidance: K weighted, optionally masked prompts against one null branch, then CFG_X0's x0; one launch */
+  IMAGEN_OP_EXT_END = 35
 };
 
 /* ------------------------------------------------------------------------------------------------
@@ -426,6 +427,26 @@ typedef struct ImagenGuideX0Params {
   int32_t B, n_per_sample, cfg, objective, mode, phase;
   float cond_scale, phi, eta, norm_threshold, momentum;
 } ImagenGuideX0Params;
+
+/* COMPOSE_X0 — composed guidance (Liu et al. 2022, "Compositional Visual Generation with Composable Diffusion Models": conjunction with positive
+ * weights, negation with negative ones), with an optional mask per prompt (regional prompting); the reference has no such lines.  x, coef, step_ptr,
+ * objective as for CFG_X0 (alpha, sigma = coef[*step_ptr][0 .. 1]); same outputs (x0, |x0|): QUANTILE / DDPM_UPDATE / LINCOMB follow unchanged.
+ *   pred    fp32 [(K + 1) * B, n], branch-major: rows [k B, (k + 1) B) are prompt k's, the LAST B rows the null branch's (at K = 1: CFG_X0's layout).
+ *   weights fp32 [K, B] in device memory, read by every launch: one captured graph serves any weights.  Any finite value; negative = negation.
+ *   masks   fp32 [K, B, hw] or NULL: element e of a sample reads pixel e % hw (the state is NCHW, so n % hw == 0: a mask is shared by the channels).
+ * Per element, in fp32, k ascending — one fixed order, so the result is bit-identical from run to run:
+ *       t_k = weights[k][b] * masks[k][b][e % hw]          (masks == NULL: t_k = weights[k][b])
+ *       out_0 = nul + (cond_0 - nul) * t_0;   out_k = out_{k-1} + (cond_k - nul) * t_k;   x0 = X0(out_{K-1})  (GUIDE_X0's X0: CFG_X0's expressions)
+ * Every step is CFG_X0's `nul + (cond - nul) * s` with the running sum in nul's place (and contracted as the compiler contracts that one), so K = 1
+ * without masks and weights[0][b] = s gives the bits of CFG_X0 at cfg = 1, cond_scale = s; a mask of ones gives the bits of no mask.
+ * 1 <= K <= IMAGEN_COMPOSE_MAX.  n is arbitrary; 16-byte accesses where n % 4 == 0, hw % 4 == 0 and x, pred, x0, absx0, masks are 16-byte aligned,
+ * else 4-byte accesses.  One launch, no LDS, no atomics.  Refused: K out of range, hw <= 0, n % hw != 0. */
+#define IMAGEN_COMPOSE_MAX 4
+typedef struct ImagenComposeX0Params {
+  const float* x; const float* pred; const float* coef; const int32_t* step_ptr; float* x0; float* absx0;
+  const float* weights; const float* masks;
+  int32_t B, n_per_sample, hw, K, objective;
+} ImagenComposeX0Params;
 
 /* QUANTILE — torch.quantile(|x0| per sample, q) ip.py:2097-2101 (linear interpolation), exact. */
 typedef struct ImagenQuantileParams {
