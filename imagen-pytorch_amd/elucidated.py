@@ -325,42 +325,21 @@ class ElucidatedImagen(Imagen):
     ):
         return self._sample(self._call(**{k: v for k, v in locals().items() if k != 'self'}))   # (the keywords, as given)
 
-    _compose_refusal = ('ElucidatedImagen evaluates the denoiser twice per step of its second-order sampler on the two-branch plan; composed '
-                        'prompts belong to Imagen.sample')
-
-    def _solver_of(self, sampler=None, sample_steps=None, eta=None):
-        """Imagen._solver_of: the Karras et al. sampler of this class is the only one it has (num_sample_steps sets its step count)."""
-        given = [k for k, v in (('sampler', sampler), ('sample_steps', sample_steps), ('eta', eta)) if v is not None]
-        if given:
-            raise ValueError(f"{', '.join(given)}: ElucidatedImagen samples with its own second-order sampler (num_sample_steps); "
-                             f"the solver keywords belong to Imagen.sample")
-        return None
-
-    def _guidance_of(self, guidance_schedule=None, guidance_interval=None):
-        """Imagen._guidance_of: refused.  A Heun step evaluates the denoiser twice per table row, so a per-row scale and a per-step choice
-        of plan are not what Imagen's are; this sampler guides with the fixed cond_scale."""
-        given = [k for k, v in (('guidance_schedule', guidance_schedule), ('guidance_interval', guidance_interval)) if v is not None]
-        if given:
-            raise ValueError(f"{', '.join(given)}: ElucidatedImagen evaluates the denoiser twice per step of its second-order sampler; "
-                             f"guidance schedules and intervals belong to Imagen.sample")
-        return None
-
-    def _guide_of(self, guidance_rescale=None, guidance_apg=None):
-        """Imagen._guide_of: refused, as the guidance keywords are.  The running average of projected guidance is a state per denoiser
-        evaluation of a first-order step; this sampler guides with the plain extrapolation at the fixed cond_scale."""
-        given = [k for k, v in (('guidance_rescale', guidance_rescale), ('guidance_apg', guidance_apg)) if v is not None]
-        if given:
-            raise ValueError(f"{', '.join(given)}: ElucidatedImagen evaluates the denoiser twice per step of its second-order sampler; "
-                             f"guidance rescale and projected guidance belong to Imagen.sample")
-        return None
+    # Imagen.sample's keywords that are not this sampler's (SampleCall._preflight).  A Heun step evaluates the denoiser twice per table row, so
+    # a per-row scale, a per-step choice of plan and the running average of projected guidance — a state per evaluation of a first-order
+    # step — are not what Imagen's are; this sampler guides with the plain extrapolation at the fixed cond_scale.
+    _twice = 'ElucidatedImagen evaluates the denoiser twice per step of its second-order sampler'
+    _refused_keywords = (
+        (('sampler', 'sample_steps', 'eta'), 'ElucidatedImagen samples with its own second-order sampler (num_sample_steps); the solver keywords belong to Imagen.sample'),
+        (('guidance_schedule', 'guidance_interval'), _twice + '; guidance schedules and intervals belong to Imagen.sample'),
+        (('guidance_rescale', 'guidance_apg'), _twice + '; guidance rescale and projected guidance belong to Imagen.sample'),
+        (('compose', 'compose_mask'), _twice + ' on the two-branch plan; composed prompts belong to Imagen.sample', 'compose'),
+    )
 
     def _call(self, sigma_min=None, sigma_max=None, **kw):
-        """Imagen._call; this sampler's two extra keywords become the record's per-unet `sigma_overrides`, which `_build_stage` takes."""
-        self._solver_of(kw.get('sampler'), kw.get('sample_steps'), kw.get('eta'))
-        self._guidance_of(kw.get('guidance_schedule'), kw.get('guidance_interval'))
-        self._guide_of(kw.get('guidance_rescale'), kw.get('guidance_apg'))
-        if kw.get('compose') is not None or kw.get('compose_mask') is not None:
-            raise ValueError(f'compose: {self._compose_refusal}')
+        """Imagen._call behind the pre-flight (the refused keywords never make a record); this sampler's two extra keywords become the
+        record's per-unet `sigma_overrides`, which `_build_stage` takes."""
+        self._preflight(**kw)
         n_unets = len(self.unets)
         over = None if sigma_min is None and sigma_max is None else dict(sigma_min=_cast_tuple(sigma_min, n_unets),
                                                                          sigma_max=_cast_tuple(sigma_max, n_unets))

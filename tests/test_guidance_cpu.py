@@ -356,3 +356,28 @@ def test_pipelined_sharded_requests_negative_prompt_and_lanes(cpu_backend):
     # stage 2 alone from stage 1's image
     outs = model.sample(text_embeds=te, return_all_unet_outputs=True, **kw)
     assert torch.equal(model.sample(text_embeds=te, start_at_unet_number=2, start_image_or_video=outs[0], **kw), outs[1])
+
+
+def test_sample_and_sample_pipelined_agree_on_a_negative_prompt_beside_a_schedule(cpu_backend):
+    """Both entries check a negative prompt against the scales the schedule resolves to, through the one `_resolve`: a schedule that guides
+    (varying, or constant and not 1) beside cond_scale = 1 is sampled, bit-equal; a schedule of ones beside cond_scale = 3 is refused by both,
+    and so is cond_scale = 1 with no schedule."""
+    g = fs.cascade_fixture()
+    model = fs.cascade_model()
+    te = g["text_embeds"]
+    T = g["timesteps"]
+    neg = dict(negative_text_embeds=torch.randn(1, 6, 32, generator=torch.Generator().manual_seed(5)))
+    ramp = [3.0 - i / T for i in range(T)]
+    for sched in (ramp, [3.0] * T):
+        kw = dict(cond_scale=1.0, guidance_schedule=sched, device="cpu", **neg)
+        batch = dict(text_embeds=te, noise_fn=fs.memo_noise(31))
+        seq = model.sample(use_tqdm=False, **kw, **batch)
+        assert torch.equal(model.sample_pipelined([batch], **kw)[0], seq)
+        assert not torch.equal(seq, model.sample(use_tqdm=False, **{k: v for k, v in kw.items() if k not in neg}, **batch))
+    stages = len(model._stages)
+    for kw in (dict(cond_scale=3.0, guidance_schedule=[1.0] * T), dict(cond_scale=1.0)):
+        with pytest.raises(ValueError, match="cond_scale is 1 on every stage"):
+            model.sample(text_embeds=te, use_tqdm=False, device="cpu", **kw, **neg)
+        with pytest.raises(ValueError, match="cond_scale is 1 on every stage"):
+            model.sample_pipelined([dict(text_embeds=te)], device="cpu", **kw, **neg)
+    assert len(model._stages) == stages

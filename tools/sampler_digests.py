@@ -5,11 +5,14 @@ warm-up included.  A refactor of the driver must leave both equal; there is no t
     python tools/sampler_digests.py --mode cpu --out profiles/sampler_stage_bits_head_cpu.json
     python tools/sampler_digests.py --mode gpu --tree ../parent --out profiles/sampler_stage_bits_parent_gpu.json
     python tools/sampler_digests.py --compare profiles/sampler_stage_bits_parent_cpu.json profiles/sampler_stage_bits_head_cpu.json
+    python tools/sampler_digests.py --mode refusals --out profiles/sample_call_refusals_head.json
 
 --tree: the checkout whose `imagen_pytorch_amd` is sampled (default: this one); the tool, the fixtures and the interpreter are this tree's, and
 the sampled tree is used through `sample()`, `sample_requests()` and `sample_pipelined()` alone.
 --mode cpu: injected noise (`noise_fn`, drawn from the tag) through the plan interpreter, with the patches of tests/cpu_replay.py; the
 interpreter has no in-kernel noise, so `sample_requests` is left to the other mode.  --mode gpu: the in-kernel Philox path with a fixed seed.
+--mode refusals: no digests — the fixed list of malformed and out-of-scope calls of tools/sampler_refusals.py, per call the exception type and its
+full message; nothing is built or launched.  --compare takes these files too; --expect names the cases an intended change makes differ.
 """
 from __future__ import annotations
 
@@ -53,6 +56,9 @@ def cases(mode: str):
     paint = dict(inpaint_images=_rand(1, B, 3, s1, s1), inpaint_masks=_rand(2, B, s1, s1) > 0.5, inpaint_resample_times=2)
     video = dict(text_embeds=vte, video_frames=vid["frames"])
     D, K, kw = ("image", False), ("image", True), dict(text_embeds=te, cond_scale=3.0)
+    left = (torch.arange(s0) < s0 // 2).float().expand(s0, s0)                       # the left half of the image, [H, W]
+    compose = [dict(text_embeds=te.flip(0) * 0.75, weight=(1.5, -0.5), mask=left[None]), dict(text_embeds=te[:1] * 1.25, weight=0.5)]
+    batches = lambda: [dict(text_embeds=te * (1.0 + 0.1 * i)) for i in range(2)]
     out = [
         ("ddpm.guided", D, "sample", dict(kw, return_all_unet_outputs=True)),
         ("ddpm.unguided", D, "sample", dict(kw, cond_scale=1.0)),
@@ -81,10 +87,20 @@ def cases(mode: str):
         ("ddpm.pipelined", D, "sample_pipelined", ([dict(text_embeds=te * (1.0 + 0.1 * i)) for i in range(3)],), dict(cond_scale=3.0)),
         ("ddpm.eager", D, "sample", dict(kw, use_graph=False)),
         ("karras.eager", K, "sample", dict(kw, use_graph=False)),
+        # guidance rescale, projected guidance and composed prompts, through sample() and through the sample_pipelined pre-flight
+        ("ddpm.rescale", D, "sample", dict(kw, guidance_rescale=0.7)),
+        ("ddpm.apg_momentum", D, "sample", dict(kw, guidance_apg=dict(eta=0.5, norm_threshold=2.0, momentum=-0.5))),
+        ("ddpm.apg_interval", D, "sample", dict(kw, guidance_apg=dict(momentum=-0.25), guidance_interval=(0.3, 0.8))),
+        ("ddpm.compose", D, "sample", dict(kw, compose=compose, compose_mask=1.0 - left)),
+        ("ddpm.negative_schedule", D, "sample", dict(kw, cond_scale=1.0, guidance_schedule=[3.0, 2.5, 2.0, 1.5], **neg)),
+        ("ddpm.pipelined.negative", D, "sample_pipelined", (batches(),), dict(cond_scale=3.0, **neg)),
+        ("ddpm.pipelined.rescale", D, "sample_pipelined", (batches(),), dict(cond_scale=3.0, guidance_rescale=(0.7, 0.3))),
+        ("ddpm.pipelined.compose", D, "sample_pipelined", (batches(),), dict(cond_scale=3.0, compose=compose, compose_mask=1.0 - left)),
     ]
     if mode == "gpu":
-        out.insert(-2, ("ddpm.requests", D, "sample_requests", ([dict(text_embeds=te[:1], seed=SEED + 1), dict(text_embeds=te[1:], seed=SEED + 2, **{
-            k: v[1:] for k, v in neg.items()})],), dict(cond_scale=3.0)))
+        requests = lambda: [dict(text_embeds=te[:1], seed=SEED + 1), dict(text_embeds=te[1:], seed=SEED + 2, **{k: v[1:] for k, v in neg.items()})]
+        out.insert(-10, ("ddpm.requests", D, "sample_requests", (requests(),), dict(cond_scale=3.0)))
+        out.append(("ddpm.requests.rescale_negative", D, "sample_requests", (requests(),), dict(cond_scale=3.0, guidance_rescale=0.7)))
     return [c if len(c) == 5 else (*c[:3], (), c[3]) for c in out]
 
 
@@ -104,16 +120,20 @@ def _digests(out) -> list:
 
 
 @contextlib.contextmanager
-def _run_log(log: dict):
-    """Every Plan.run and Graph.launch appends (plan name, number of ops) to the list of the calling thread."""
+def _run_log(log: dict, one_at_a_time: bool = False):
+    """Every Plan.run and Graph.launch appends (plan name, number of ops) to the list of the calling thread.  one_at_a_time: the plan
+    interpreter keeps one table of the storages it has seen, so the stage workers of sample_pipelined take turns at it."""
     from imagen_pytorch_amd import ops
 
     run, launch = ops.Plan.run, ops.Graph.launch
     note = lambda plan: log.setdefault(threading.get_ident(), []).append([plan.name, len(plan.ops)])
 
+    turn = threading.Lock() if one_at_a_time else contextlib.nullcontext()
+
     def logged_run(self, stream=None):
         note(self)
-        return run(self, stream)
+        with turn:
+            return run(self, stream)
 
     def logged_launch(self):
         note(self.plan)
@@ -148,7 +168,7 @@ def collect(mode: str) -> dict:
         elif method == "sample":
             kw["seed"] = SEED
         log = {}
-        with _run_log(log):
+        with _run_log(log, one_at_a_time=mode == "cpu"):
             out = getattr(models[mkey], method)(*args, **kw)
         if mode == "gpu":
             torch.cuda.synchronize()
@@ -159,25 +179,35 @@ def collect(mode: str) -> dict:
     return result
 
 
-def compare(a_path: str, b_path: str) -> int:
+def compare(a_path: str, b_path: str, expect=()) -> int:
+    """Equal but for the cases of `expect`, which must differ: those are printed with both outcomes."""
     a, b = (json.load(open(p))["cases"] for p in (a_path, b_path))
-    bad = [n for n in sorted(set(a) | set(b)) if a.get(n) != b.get(n)]
-    for n in bad:
-        what = "missing" if n not in a or n not in b else "digests" if a[n]["digests"] != b[n]["digests"] else "run log"
-        print(f"{n}: {what} differ")
-    print(f"{len(a)} / {len(b)} cases, " + (f"{len(bad)} differ" if bad else "every digest and every run log equal"))
+    differ = [n for n in sorted(set(a) | set(b)) if a.get(n) != b.get(n)]
+    bad = sorted(set(differ) ^ set(expect))
+    for n in differ:
+        if n in expect:
+            print(f"{n}: differs as expected\n    {json.dumps(a.get(n))}\n    {json.dumps(b.get(n))}")
+        else:
+            what = "missing" if n not in a or n not in b else "outcome" if "digests" not in a[n] else \
+                "digests" if a[n]["digests"] != b[n]["digests"] else "run log"
+            print(f"{n}: {what} differ")
+    for n in set(expect) - set(differ):
+        print(f"{n}: expected to differ, is equal")
+    everything = "every outcome equal" if a and "digests" not in next(iter(a.values())) else "every digest and every run log equal"
+    print(f"{len(a)} / {len(b)} cases, " + (f"{len(bad)} differ unexpectedly" if bad else everything + (f" but the {len(expect)} expected" if expect else "")))
     return 1 if bad else 0
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--mode", choices=("cpu", "gpu"))
+    ap.add_argument("--mode", choices=("cpu", "gpu", "refusals"))
     ap.add_argument("--tree", default=ROOT, help="the checkout whose package is sampled")
     ap.add_argument("--out")
     ap.add_argument("--compare", nargs=2, metavar=("A", "B"))
+    ap.add_argument("--expect", nargs="*", default=(), metavar="CASE", help="with --compare: the cases that are to differ (an intended change)")
     args = ap.parse_args()
     if args.compare:
-        return compare(*args.compare)
+        return compare(*args.compare, expect=args.expect)
     assert args.mode and args.out, "--mode and --out"
     tree = os.path.abspath(args.tree)
     for p in (os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools"), tree):      # (the sampled tree first on the path)
@@ -187,10 +217,16 @@ def main():
     assert os.path.abspath(imagen_pytorch_amd.__file__).startswith(tree + os.sep), imagen_pytorch_amd.__file__
     if args.mode == "cpu":
         import cpu_replay
-        from plan_interp_guidance import GuidanceInterpreter      # (the interpreter that also knows CFG_X0 at cfg == 2)
+        from plan_interp_compose import ComposeInterpreter        # (the superset interpreter: CFG_X0 at cfg == 2, GUIDE_X0, COMPOSE_X0)
 
-        with cpu_replay.cpu_backend(GuidanceInterpreter()):
+        with cpu_replay.cpu_backend(ComposeInterpreter()):
             result = collect("cpu")
+    elif args.mode == "refusals":
+        import cpu_replay
+        import sampler_refusals
+
+        with cpu_replay.cpu_backend(sampler_refusals.NoLaunch()):
+            result = sampler_refusals.collect()
     else:
         result = collect("gpu")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
