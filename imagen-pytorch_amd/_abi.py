@@ -128,6 +128,7 @@ OP_STRUCT = {
 EXT_OP_STRUCT = {
     ENUMS["IMAGEN_OP_GUIDE_X0"]: STRUCTS["ImagenGuideX0Params"],
     ENUMS["IMAGEN_OP_COMPOSE_X0"]: STRUCTS["ImagenComposeX0Params"],
+    ENUMS["IMAGEN_OP_TILES"]: STRUCTS["ImagenTilesParams"],             # (ImagenExtOpKind2: the range goes on past IMAGEN_OP_EXT_END)
 }
 STRUCT_KIND = {v: k for k, v in {**OP_STRUCT, **EXT_OP_STRUCT}.items()}
 

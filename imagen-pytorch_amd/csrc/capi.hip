@@ -54,6 +54,7 @@ extern "C" size_t imagen_sizeof(int kind) {
     case IMAGEN_OP_LINEAR_XATTN: return sizeof(ImagenLinearXattnParams);
     case IMAGEN_OP_GUIDE_X0: return sizeof(ImagenGuideX0Params);
     case IMAGEN_OP_COMPOSE_X0: return sizeof(ImagenComposeX0Params);
+    case IMAGEN_OP_TILES: return sizeof(ImagenTilesParams);
     default: return 0;
   }
 }
@@ -101,6 +102,7 @@ extern "C" int imagen_launch(int kind, const void* params, size_t params_bytes, 
     case IMAGEN_OP_LINEAR_XATTN: return launch_linear_xattn(static_cast<const ImagenLinearXattnParams*>(params), s);
     case IMAGEN_OP_GUIDE_X0: return launch_guide_x0(static_cast<const ImagenGuideX0Params*>(params), s);
     case IMAGEN_OP_COMPOSE_X0: return launch_compose_x0(static_cast<const ImagenComposeX0Params*>(params), s);
+    case IMAGEN_OP_TILES: return launch_tiles(static_cast<const ImagenTilesParams*>(params), s);
     default: imagen_set_error("imagen_launch: unknown op kind %d", kind); return -1;
   }
 }

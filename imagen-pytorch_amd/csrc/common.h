@@ -121,6 +121,7 @@ int launch_pack_image(const ImagenPackImageParams* p, hipStream_t s);
 int launch_cfg_x0(const ImagenCfgX0Params* p, hipStream_t s);
 int launch_guide_x0(const ImagenGuideX0Params* p, hipStream_t s);
 int launch_compose_x0(const ImagenComposeX0Params* p, hipStream_t s);
+int launch_tiles(const ImagenTilesParams* p, hipStream_t s);
 int launch_quantile(const ImagenQuantileParams* p, hipStream_t s);
 int launch_ddpm_update(const ImagenDdpmUpdateParams* p, hipStream_t s);
 int launch_rows_copy(const ImagenRowsCopyParams* p, hipStream_t s);

@@ -322,6 +322,9 @@ class ElucidatedImagen(Imagen):
         guidance_apg=None,
         compose=None,                                 # Imagen.sample's composed prompts: refused here (ValueError)
         compose_mask=None,
+        tile_shapes=None,                             # Imagen.sample's tiled sampling: refused here (ValueError)
+        tile_overlap=None,
+        tile_blend=None,
     ):
         return self._sample(self._call(**{k: v for k, v in locals().items() if k != 'self'}))   # (the keywords, as given)
 
@@ -334,6 +337,7 @@ class ElucidatedImagen(Imagen):
         (('guidance_schedule', 'guidance_interval'), _twice + '; guidance schedules and intervals belong to Imagen.sample'),
         (('guidance_rescale', 'guidance_apg'), _twice + '; guidance rescale and projected guidance belong to Imagen.sample'),
         (('compose', 'compose_mask'), _twice + ' on the two-branch plan; composed prompts belong to Imagen.sample', 'compose'),
+        (('tile_shapes', 'tile_overlap', 'tile_blend'), _twice + ', each on the whole canvas; tiled sampling belongs to Imagen.sample', 'tile_shapes'),
     )
 
     def _call(self, sigma_min=None, sigma_max=None, **kw):

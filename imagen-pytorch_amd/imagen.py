@@ -271,6 +271,10 @@ class Imagen(SampleCall, nn.Module):
         if common.get('compose') is not None or common.get('compose_mask') is not None or any('compose' in r or 'compose_mask' in r for r in requests):
             raise ValueError('sample_requests: compose / compose_mask inside or beside merged requests; the merged rows share one stage of 2 rows '
                              'per sample, composed prompts run K + 1: sample composed prompts with sample() or sample_pipelined()')
+        tile_keys = ('tile_shapes', 'tile_overlap', 'tile_blend')
+        if any(common.get(k) is not None for k in tile_keys) or any(k in r for r in requests for k in tile_keys):
+            raise ValueError('sample_requests: tile_shapes / tile_overlap / tile_blend inside or beside merged requests; the merged rows share one stage of '
+                             'one row per sample, a tiled stage runs T: sample tiled with sample() or sample_pipelined()')
         for k in GUIDANCE_KEYWORDS:
             if any(k in r for r in requests):
                 raise ValueError(f'sample_requests: {k} inside a request; merged requests run one plan, so it is a common keyword, as cond_scale is')
@@ -414,7 +418,7 @@ class Imagen(SampleCall, nn.Module):
 
     def _new_stage(self, key: tuple, idx: int, B: int, device, *, cfg: bool, with_text: bool, inject_noise: bool, sample_offset: int,
                    resample_times: int, frames: int, prompt_frames: tuple, tables: Callable, size=None, buffers: tuple = (),
-                   share: Optional[dict] = None, prompts: int = 1):
+                   share: Optional[dict] = None, prompts: int = 1, tile: Optional[dict] = None):
         """What both samplers' `_build_stage` do first.  Returns (the cached stage of `key`, False) while its engine is not stale; else
         (a new stage dict, True): the engine (image or video), the sampler state (SHARED_STATE), the engine bound to the step counter and to
         `coef` = tables[0], the per-request time table where it applies, the buffers of inpainting.  EVERY key the run side reads is present
@@ -422,14 +426,18 @@ class Imagen(SampleCall, nn.Module):
         the per-evaluation one first; called only on a cache miss.  buffers: which of the optional [B, n] state buffers ('x0_thr',
         'x0_prev') the step needs.  prompts: K, the prompt sets of a guided stage — (K + 1) B denoiser rows, the null rows last; 1 is plain
         guidance's 2 B.  share: the stage whose sampler state this one runs on (the unguided sibling of a stage with a guidance
-        schedule): the very objects of `share` are this stage's own, and its engine reads that stage's `x_in` / low-res image."""
+        schedule): the very objects of `share` are this stage's own, and its engine reads that stage's `x_in` / low-res image.  tile: the
+        tile_geometry of a tiled stage (sample_call.tile_geometry) — the engine is built at the tile's size for T B samples (src_batch = T B,
+        tile-major), the sampler state at the canvas's `size`: st['x'] is a canvas of its own that TILES gathers into the engine's `x_in`."""
         st = self._stages.get(key)
         if st is not None and not st['eng'].stale():
             return st, False
         unet, S, R = self.unets[idx], self.image_sizes[idx] if size is None else size, resample_times
-        rows = (prompts + 1) * B if cfg else B
+        EB = B if tile is None else tile['T'] * B       # the engine's samples
+        rows = (prompts + 1) * EB if cfg else EB
         video = isinstance(unet, Unet3D)
         assert prompts == 1 or (cfg and not video), 'composed prompts run on the guided image engine'
+        assert tile is None or (prompts == 1 and not video and not R and share is None), 'a tiled stage is a plain image stage'
         if video:
             # Imagen-Video stage: the sampler state is the engine's frame-major clip (b, f, c, h, w); every sampler kernel is
             # elementwise per sample (the dynamic threshold is one quantile over the whole clip, ip.py:1921, 2097-2101), so only
@@ -440,8 +448,13 @@ class Imagen(SampleCall, nn.Module):
                                         post_frames=prompt_frames[1])
         else:
             from . import engine
-            eng = engine.UnetEngine(unet, rows, B, S, device, with_text=with_text)
-        n = eng.x_in[0].numel()
+            eng = engine.UnetEngine(unet, rows, EB, S if tile is None else (tile['h'], tile['w']), device, with_text=with_text)
+        canvas = None
+        if tile is not None:
+            H, Wd = (S, S) if isinstance(S, int) else S
+            canvas = torch.zeros(B, unet.channels, H, Wd, device=device)
+        x_state = eng.x_in if canvas is None else canvas
+        n = x_state[0].numel()
         if share is not None:
             assert not R, 'a shared sampler state does not cover the inpainting plan'
             eng.share_sampler_state(share['eng'])
@@ -451,7 +464,7 @@ class Imagen(SampleCall, nn.Module):
             state = dict(step_ptr=torch.zeros(1, dtype=torch.int32, device=device), seed_dev=torch.zeros(2, dtype=torch.int32, device=device),
                          # (Philox key lo, hi, global sample index, 0) of every row: _run_stage fills it per call
                          row_keys=torch.zeros(B, 4, dtype=torch.int32, device=device) if self._per_row_noise_keys else None,
-                         noise=torch.empty_like(eng.x_in) if inject_noise else None, final=torch.empty_like(eng.x_in),
+                         noise=torch.empty_like(x_state) if inject_noise else None, final=torch.empty_like(x_state),
                          x0_thr=per_sample('x0_thr'), x0_prev=per_sample('x0_prev'), tables=tables())
             assert tuple(state) == self.SHARED_STATE
         coef, step_ptr = state['tables'][0], state['step_ptr']
@@ -466,8 +479,12 @@ class Imagen(SampleCall, nn.Module):
         # (x: the image the sampler steps.  scales / sibling: Imagen's guidance schedules, None for every stage without one, under both samplers;
         # guide / avg / head: Imagen's guidance rescale | projected guidance, its running average and the plan that zeroes it at a run's start;
         # compose: Imagen's composed prompts, the per-call weights [K, B] and masks [K, B, hw] | None that COMPOSE_X0 reads)
-        return dict(eng=eng, step_plan=step_plan, plan=None, graph=None, coef=coef, **state, x=eng.x_in,
-                    key=key, scales=None, sibling=None, guide=None, avg=None, head=None, compose=None,
+        # tile: Imagen's tiled sampling — the geometry with the origins and window weights on the device, and the canvas the low-res image is
+        # augmented on before TILES gathers it into the engine's
+        if tile is not None:
+            tile = dict(tile, origins=tile['origins'].to(device), nw=tile['nw'].to(device), lowres=torch.zeros_like(canvas) if unet.lowres_cond else None)
+        return dict(eng=eng, step_plan=step_plan, plan=None, graph=None, coef=coef, **state, x=eng.x_in if canvas is None else canvas, B=B,   # (eng.x_in: after share_sampler_state)
+                    key=key, scales=None, sibling=None, guide=None, avg=None, head=None, compose=None, tile=tile,
                     n=n, S=S, R=R, video=video, frames=frames, sample_offset=sample_offset,
                     # inpainting: the known image (video: frame-major clip), normalised, at this stage's size; 1.0 where it is kept
                     known=zeros() if R else None, mask=zeros() if R else None,
@@ -499,7 +516,7 @@ class Imagen(SampleCall, nn.Module):
         'dpmpp_2m' hands thr(x0) to `x0_prev` with a second LINCOMB used as a copy — LINCOMB forbids thr1_out aliasing an input of its own
         launch — so that ONE captured graph serves every step.  Allocates only the scratch of these launches, private to the plan."""
         eng, n, R, solver, tables, coef, step_ptr, seed_dev = (st[k] for k in ('eng', 'n', 'R', 'solver', 'tables', 'coef', 'step_ptr', 'seed_dev'))
-        B, device = eng.src_batch, coef.device
+        B, device, x, tile = st['B'], coef.device, st['x'], st['tile']
         x0, absx0 = (torch.empty(B, n, device=device) for _ in range(2))
         quant = torch.empty(B, device=device)
         scratch = torch.empty(B * ops.ENUMS["IMAGEN_QUANTILE_SCRATCH_WORDS"], dtype=torch.int32, device=device)
@@ -508,9 +525,19 @@ class Imagen(SampleCall, nn.Module):
             noise_blend = torch.zeros_like(eng.x_in) if inject_noise else None
             ops.lincomb(plan, st['known'], eng.x_in, tables[1], step_ptr, B=B, n_per_sample=n, t1=noise_blend, mask=st['mask'], mask_else=eng.x_in,
                         stream_id=idx | 0x100, sample_offset=st['sample_offset'], seed_ptr=seed_dev, label="inpaint.blend")
+        if tile is not None:                             # the canvas x_t -> the engine's tile rows
+            geo = dict(B=B, C=x.shape[1], H=x.shape[2], W=x.shape[3], h=tile['h'], w=tile['w'])
+            ops.tiles(plan, x, eng.x_in, tile['origins'], mode='gather', **geo)
         plan.extend(st['step_plan'])
         guide = st['guide'] if cfg else None             # (an unguided step is CFG_X0's, and leaves the running average alone)
-        if st['compose'] is not None:
+        if tile is not None:
+            # CFG_X0 on the tile rows against the gathered x: the tiles' x0 (its |x0| goes to a scratch nobody reads), blended into the canvas's
+            EB, tn = eng.src_batch, eng.x_in[0].numel()
+            tx0, tabs = (torch.empty(EB, tn, device=device) for _ in range(2))
+            ops.cfg_x0(plan, eng.x_in, eng.out, coef, step_ptr, tx0, tabs, B=EB, n_per_sample=tn, cfg=cfg, cond_scale=float(cond_scale),
+                       objective=self.pred_objectives[idx])
+            ops.tiles(plan, tx0, x0, tile['origins'], mode='blend', nw=tile['nw'], absdst=absx0, **geo)
+        elif st['compose'] is not None:
             H, Wd = eng.x_in.shape[-2:]
             ops.compose_x0(plan, eng.x_in, eng.out, coef, step_ptr, x0, absx0, B=B, n_per_sample=n, hw=H * Wd, weights=st['compose']['weights'],
                            masks=st['compose']['masks'], objective=self.pred_objectives[idx])
@@ -530,7 +557,7 @@ class Imagen(SampleCall, nn.Module):
             sampler, _, eta = solver
             # 'dpmpp_2m', the history: x0_prev enters the update as t3 (already thresholded: thr(.) with no quantile is the identity on
             # [-1, 1]), and receives this step's thr(x0) from a copy launch (weights (1, 0, ...) of row 0 of a table of its own)
-            ops.lincomb(plan, eng.x_in, eng.x_in, tables[1], step_ptr, B=B, n_per_sample=n, t1=x0, q1=quant if dyn else None,
+            ops.lincomb(plan, x, x, tables[1], step_ptr, B=B, n_per_sample=n, t1=x0, q1=quant if dyn else None,
                         t2=st['noise'] if eta > 0. else None, t3=st['x0_prev'], thr_mode=1 if dyn else 2, thr1_out=st['x0_thr'], final=True,
                         final_out=st['final'], advance=True, stream_id=idx, sample_offset=st['sample_offset'], seed_ptr=seed_dev,
                         label=f"{sampler}.update")
@@ -538,17 +565,17 @@ class Imagen(SampleCall, nn.Module):
                 zero_ptr = torch.zeros(1, dtype=torch.int32, device=device)
                 ops.lincomb(plan, st['x0_thr'], st['x0_prev'], tables[2], zero_ptr, B=B, n_per_sample=n, label="dpmpp_2m.history")
         else:
-            ops.ddpm_update(plan, eng.x_in, x0, quant if dyn else None, coef, st['noise'], st['final'], step_ptr, B=B, n_per_sample=n,
+            ops.ddpm_update(plan, x, x0, quant if dyn else None, coef, st['noise'], st['final'], step_ptr, B=B, n_per_sample=n,
                             dynamic_threshold=dyn, total_steps=st['T'] * max(R, 1), seed=0, stream_id=idx, sample_offset=st['sample_offset'],
                             seed_ptr=seed_dev, advance=not R, x0_thr=st['x0_thr'], row_keys=None if inject_noise else st['row_keys'])
         if R:
-            ops.lincomb(plan, eng.x_in, eng.x_in, tables[2], step_ptr, B=B, n_per_sample=n, t1=st['noise_renoise'], advance=True,
+            ops.lincomb(plan, x, x, tables[2], step_ptr, B=B, n_per_sample=n, t1=st['noise_renoise'], advance=True,
                         stream_id=idx | 0x200, sample_offset=st['sample_offset'], seed_ptr=seed_dev, label="inpaint.renoise")
         return dict(quant=quant, x0=x0, noise_blend=noise_blend)
 
     def _build_stage(self, idx: int, B: int, device, *, cond_scale: float, with_text: bool, inject_noise: bool, sample_offset: int,
                      resample_times: int = 0, frames: int = 0, prompt_frames: tuple = (0, 0), size=None, solver: Optional[tuple] = None,
-                     guidance: Optional[torch.Tensor] = None, guide: Optional[tuple] = None, compose: Optional[tuple] = None):
+                     guidance: Optional[torch.Tensor] = None, guide: Optional[tuple] = None, compose: Optional[tuple] = None, tile: Optional[dict] = None):
         """Build (or fetch) the per-timestep plan + graph of stage `idx` for batch B, at image_sizes[idx] or at `size` (an int, or (H, W)):
         form the key, get or make the stage (`_new_stage`), emit its step (`_emit_step`), file it.
 
@@ -570,13 +597,20 @@ class Imagen(SampleCall, nn.Module):
 
         compose = (K, masks present) (SampleCall._compose_of): the stage runs (K + 1) B denoiser rows and COMPOSE_X0 in place of CFG_X0, whatever
         `cond_scale` is — the main prompt's weight like every other lives in st['compose']['weights'] (device memory, filled per call by
-        `_prepare_stage`, as the masks are), so the key holds no scale and ends with (K, masks present)."""
+        `_prepare_stage`, as the masks are), so the key holds no scale and ends with (K, masks present).
+
+        tile = the tile_geometry of a tiled stage (SampleCall._tiles_of): `size` stays the canvas's, the engine runs T B (2 T B) rows at the
+        tile's size, and the step is TILES gather, the denoiser, CFG_X0 on the tile rows, TILES blend, then the canvas's threshold and update.
+        The geometry is a function of (canvas, tile shape, overlap, blend): the key ends with ('tile', (tile shape, overlap, blend))."""
         sched = self.noise_schedulers[idx]
         T, R = sched.num_timesteps if solver is None else solver[1], resample_times
         assert solver is None or not R, 'the solvers do not cover inpainting'
         assert guidance is None or (not R and tuple(guidance.shape) == (T,) and guidance.dtype == torch.float32)
         assert guide is None or (not R and (guidance is not None or cond_scale != 1.)), 'guidance rescale / projected guidance act on guided steps'
         suffix = () if guide is None else (('guide', guide),)     # (a call without the keywords keeps the key it always had)
+        if tile is not None:
+            assert guide is None and compose is None and not R, 'a tiled stage takes the plain guided step'
+            suffix += (('tile', ((tile['h'], tile['w']), (tile['oy'], tile['ox']), tile['blend'])),)
         size = self.image_sizes[idx] if size is None else size
         two = solver is not None and solver[0] == 'dpmpp_2m'
         buffers = ('x0_thr',) * bool(two or getattr(self.unets[idx], 'self_cond', False)) + ('x0_prev',) * two
@@ -586,7 +620,7 @@ class Imagen(SampleCall, nn.Module):
 
         def stage(key, cfg, scale, scales=None, share=None, prompts=1):
             st, built = self._new_stage(key, idx, B, device, cfg=bool(cfg), prompts=prompts, with_text=with_text, inject_noise=inject_noise, sample_offset=sample_offset,
-                                        resample_times=R, frames=frames, prompt_frames=prompt_frames, size=size, buffers=buffers, share=share,
+                                        resample_times=R, frames=frames, prompt_frames=prompt_frames, size=size, buffers=buffers, share=share, tile=tile,
                                         tables=functools.partial(self._step_tables, idx, device, solver=solver, R=R, inject_noise=inject_noise,
                                                                  guidance=guidance))
             if built:
@@ -686,7 +720,7 @@ class Imagen(SampleCall, nn.Module):
         on (each run `inpaint_resample_times` times when st is an inpainting stage), clamp + unnormalise (done by the last step's kernel)
         and the final paste of the known pixels.  What the samplers differ in: `_rewind` (the state at the start of a run),
         `_plans_of_steps` (which captured plan a step replays), `_capture` (warm-up and capture), `_draw_step_noise` (the injected draws)."""
-        x, T, R, B = st['x'], st['T'], st['R'], st['eng'].src_batch
+        x, T, R, B = st['x'], st['T'], st['R'], st['B']
         stream = torch.cuda.current_stream()
         skip = skip_steps or 0
         assert 0 <= skip < T, f'skip_steps must leave at least one {self._step_noun}'
@@ -909,6 +943,12 @@ class Imagen(SampleCall, nn.Module):
                                                        #   negation; mask: [B | 1, H, W] or [H, W] in [0, 1], resized to every stage (nearest): regional
                                                        #   prompts.  Weights and masks are per-call state: every call of one K shares the stage and its graph
         compose_mask=None,                             #   ... the mask of the call's own prompt
+        tile_shapes=None,                              # extension: tiled sampling (MultiDiffusion, Bar-Tal et al. 2023).  One (h, w), an int or None, or a
+                                                       #   tuple of one per unet (a pair of ints is ONE shape): every step runs the denoiser on overlapping
+                                                       #   h x w windows of the stage's canvas (image_shapes / image_sizes) — T B rows, 2 T B under guidance —
+                                                       #   and blends their x0 into one canvas x0 (TILES); threshold, solver and noise act on the canvas
+        tile_overlap=None,                             #   ... an int or (oy, ox), one or per unet; None: a quarter of the tile side
+        tile_blend='ramp',                             #   ... the window of the blend: 'ramp' (linear over the overlap) | 'uniform'
     ):
         return self._sample(self._call(**{k: v for k, v in locals().items() if k != 'self'}))   # (the keywords, as given)
 
@@ -964,6 +1004,9 @@ class Imagen(SampleCall, nn.Module):
         comp = c.composed if with_text else None
         if comp is not None:
             extra['compose'] = (comp['K'], comp['masks'] is not None)
+        tile = None if c.tiles is None else c.tiles[idx]
+        if tile is not None:
+            extra['tile'] = tile
         st = self._stage(idx, batch_size, device, cond_scale=cs, with_text=with_text, inject_noise=noise_fn is not None,
                          sample_offset=c.sample_offset, resample_times=c.inpaint_resample_times if c.known is not None else 0,
                          frames=c.frames // self.temporal_downsample_factor[idx] if isinstance(unet, Unet3D) else 0,
@@ -992,8 +1035,10 @@ class Imagen(SampleCall, nn.Module):
             a, s, lsnr = self.lowres_noise_schedule.q_sample_coefficients(c.level)
             # Imagen conditions on the log-SNR of the augmentation level (ip.py:2081); ElucidatedImagen.sample passes the
             # raw level (elucidated_imagen.py:700, 728): `_lowres_time_raw`
-            lowres_logsnr = torch.full((batch_size,), c.level if self._lowres_time_raw else lsnr, dtype=torch.float32)
-            aug = torch.empty_like(eng.lowres_in)
+            lowres_logsnr = torch.full((eng.src_batch,), c.level if self._lowres_time_raw else lsnr, dtype=torch.float32)
+            # (a tiled stage: the low-res image is resized and augmented once, on the canvas; one TILES gather then fills the engine's tile rows)
+            lowres_out = eng.lowres_in if tile is None else st['tile']['lowres']
+            aug = torch.empty_like(lowres_out)
             if noise_fn is not None:
                 aug.copy_(self._draw(st, noise_fn, ("lowres", idx), aug))
             prep = Plan("lowres-prep")
@@ -1005,15 +1050,18 @@ class Imagen(SampleCall, nn.Module):
                 # a stage sampled at a lower frame rate feeds this one: nearest over the frame axis (resize_video_to,
                 # iv.py:134-156); once per stage
                 src = src[:, nearest_indices(src.shape[1], aug.shape[1]).to(src.device)]
-            if self.resize_mode != 'nearest' and tuple(src.shape[-2:]) != tuple(eng.lowres_in.shape[-2:]):
+            if self.resize_mode != 'nearest' and tuple(src.shape[-2:]) != tuple(lowres_out.shape[-2:]):
                 # LOWRES_PREP resizes with nearest in-kernel; any other mode is resized here, once per stage, and the kernel's
                 # own resize becomes the identity.  The resize acts on the [0, 1] image as in ip.py:2444-2446 (normalisation after).
                 src = self._resize(img, S) if self.auto_normalize_img else (self._resize(img, S) + 1) * 0.5
             src = src.contiguous()
             # frames are independent images for the nearest resize (resize_video_to with unchanged frame count, iv.py:134-156)
             as_images = lambda t: t.reshape(-1, *t.shape[-3:])
-            ops.lowres_prep(prep, as_images(src), as_images(aug), as_images(eng.lowres_in), alpha=a, sigma=s)
-            prep.keep += [src, aug, eng.lowres_in]
+            ops.lowres_prep(prep, as_images(src), as_images(aug), as_images(lowres_out), alpha=a, sigma=s)
+            if tile is not None:
+                ops.tiles(prep, lowres_out, eng.lowres_in, st['tile']['origins'], mode='gather', B=batch_size, C=lowres_out.shape[1],
+                          H=lowres_out.shape[2], W=lowres_out.shape[3], h=tile['h'], w=tile['w'])
+            prep.keep += [src, aug, lowres_out]
             prep.run()
         if comp is not None:                         # the call's weights and masks, into the buffers COMPOSE_X0 reads: no launch list changes
             st['compose']['weights'].copy_(comp['weights'][idx])
@@ -1027,18 +1075,27 @@ class Imagen(SampleCall, nn.Module):
                         st['compose']['masks'][k].copy_(m.expand(batch_size, -1, -1).reshape(batch_size, H * Wd))
         cond = c.conditioning
         stamp = None if cond is None else (cond.token, None if lowres_logsnr is None else float(lowres_logsnr[0]))
+        # (a tiled stage: engine row t B + b is tile t of sample b, so the prompts — and the negative prompt's rows — repeat per tile)
+
+        def per_tile(t, keep_one=False):
+            """A per-sample conditioning tensor for the engine's T B samples; keep_one: a batch-1 tensor stays batch 1 (the negative prompt, which
+            the engine repeats over its samples itself)."""
+            if tile is None or t is None or (keep_one and t.shape[0] == 1):
+                return t
+            return t.repeat(tile['T'], *((1,) * (t.ndim - 1)))
+
         for eng in engines:
-            rows = eng.R
+            rows, eb = eng.R, eng.src_batch
             keep = torch.ones(rows, dtype=torch.bool)
-            if rows > batch_size:
-                keep[rows - batch_size:] = False     # the last B rows = null-conditioned CFG branch (cond_drop_prob = 1, ip.py:1521)
+            if rows > eb:
+                keep[rows - eb:] = False             # the last B rows = null-conditioned CFG branch (cond_drop_prob = 1, ip.py:1521)
             if stamp is None or getattr(eng, '_cond_stamp', None) != stamp:
                 neg_kw = {}
-                if c.neg_embeds is not None and with_text and rows > batch_size:          # (a stage at cond_scale 1 has no null rows)
-                    neg_kw = dict(negative_text_embeds=c.neg_embeds, negative_text_mask=c.neg_masks, negative_rows=c.neg_rows)
+                if c.neg_embeds is not None and with_text and rows > eb:                  # (a stage at cond_scale 1 has no null rows)
+                    neg_kw = dict(negative_text_embeds=per_tile(c.neg_embeds, True), negative_text_mask=per_tile(c.neg_masks, True), negative_rows=c.neg_rows)
                 if comp is not None:
                     neg_kw['extra_prompts'] = comp['prompts']
-                eng.set_conditioning(text_embeds=c.text_embeds if with_text else None, text_mask=c.text_masks if with_text else None,
+                eng.set_conditioning(text_embeds=per_tile(c.text_embeds) if with_text else None, text_mask=per_tile(c.text_masks) if with_text else None,
                                      keep=keep, lowres_noise_times=lowres_logsnr, **neg_kw)
                 eng.static_runs = getattr(eng, 'static_runs', 0) + 1
             eng._cond_stamp = stamp

@@ -1447,6 +1447,33 @@ def compose_x0(plan: Plan, x, pred, coef, step_ptr, x0, absx0, *, B, n_per_sampl
     return p
 
 
+def tiles(plan: Plan, src, dst, origins, *, B, C, H, W, h, w, mode: str, nw=None, absdst=None, label: str = ""):
+    """TILES (include/imagen_hip.h): mode 'gather' copies the T windows of the fp32 canvas `src` [B, C, H, W] into the tile rows `dst`
+    [T, B, C, h, w] (tile-major); mode 'blend' sums the tile rows `src` into the canvas `dst` (and |.| into `absdst`) with the normalised window
+    weights `nw` fp32 [T, h * w].  origins int32 [T, 2] = (y0, x0) on the device; T comes from it.  Returns the struct."""
+    if mode not in ("gather", "blend"):
+        raise ValueError(f"tiles: mode = {mode!r}; 'gather' | 'blend'")
+    if not (isinstance(origins, torch.Tensor) and origins.dtype == torch.int32 and origins.ndim == 2 and origins.shape[1] == 2 and origins.is_contiguous()):
+        raise ValueError("tiles: origins is a contiguous int32 [T, 2] tensor of (y0, x0)")
+    T = int(origins.shape[0])
+    B, C, H, W, h, w = (int(v) for v in (B, C, H, W, h, w))
+    if not 1 <= T <= ENUMS["IMAGEN_TILE_MAX"]:
+        raise ValueError(f"tiles: T = {T} tiles; 1 .. {ENUMS['IMAGEN_TILE_MAX']}")
+    if min(B, C, H, W, h, w) <= 0 or h > H or w > W:
+        raise ValueError(f"tiles: B, C = {B}, {C}, canvas {H} x {W}, tile {h} x {w}: positive dimensions, the tile no larger than the canvas")
+    canvas, rows = (src, dst) if mode == "gather" else (dst, src)
+    if canvas.numel() < B * C * H * W or rows.numel() < T * B * C * h * w or (absdst is not None and absdst.numel() < B * C * H * W):
+        raise ValueError(f"tiles: the canvas holds {canvas.numel()} elements (B C H W = {B * C * H * W}), the tile rows {rows.numel()} (T B C h w = {T * B * C * h * w})")
+    if mode == "blend" and not (isinstance(nw, torch.Tensor) and nw.dtype == torch.float32 and nw.is_contiguous() and nw.numel() == T * h * w):
+        raise ValueError(f"tiles: the blend reads nw, a contiguous fp32 [T, h * w] = [{T}, {h * w}] tensor")
+    _abi.require_ext_op(ENUMS["IMAGEN_OP_TILES"], "tiles")
+    p = STRUCTS["ImagenTilesParams"]()
+    p.src, p.dst, p.absdst, p.origins, p.nw = src.data_ptr(), dst.data_ptr(), ptr(absdst if mode == "blend" else None), origins.data_ptr(), ptr(nw if mode == "blend" else None)
+    p.B, p.C, p.H, p.W, p.h, p.w, p.T, p.mode = B, C, H, W, h, w, T, int(mode == "blend")
+    plan.add(p, label or f"tiles.{mode}", [src, dst, absdst, origins, nw])
+    return p
+
+
 def quantile(plan: Plan, absx0, out, scratch, *, B, n, q: float, label: str = ""):
     p = STRUCTS["ImagenQuantileParams"]()
     p.absx0, p.out, p.scratch, p.B, p.n, p.q = absx0.data_ptr(), out.data_ptr(), scratch.data_ptr(), B, n, q

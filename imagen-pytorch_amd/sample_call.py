@@ -6,7 +6,8 @@ record, `_resolve` fills it:
     text or draws a seed, `ElucidatedImagen._call` before it makes the record; `sample_pipelined` checks a batch by `_resolve` of the
     whole-cascade call, so every entry refuses what `sample()` refuses;
   * then, in an order the refusals of a call with several faults depend on: sizes, device, text and batch, inpainting inputs, the per-unet tuples,
-    the guidance vectors, `_check_guide`, composed prompts, the seed, the negative prompt, the start image.
+    the guidance vectors, `_check_guide`, composed prompts, tiled sampling (`_tiles_of`; its geometry and window weights are `tile_origins`,
+    `tile_window`, `tile_geometry` below), the seed, the negative prompt, the start image.
 What the resolvers share exists once: `per_unet`, `is_number`, `stage_range`, `_cannot_guide`, `_needs_text_branch`, `_refuse_inpainting`.
 """
 from __future__ import annotations
@@ -98,6 +99,9 @@ class _Call:
     guidance_apg: Any = None                           # ... dict(eta=, norm_threshold=, momentum=) of projected guidance, one or per unet
     compose: Any = None                                # extension: further prompts, [dict(text_embeds= | texts=, text_masks=, weight=, mask=), ...] — SampleCall._compose_of
     compose_mask: Any = None                           # ... the main prompt's mask, [B | 1, H, W] or [H, W] in [0, 1]
+    tile_shapes: Any = None                            # extension: tiled sampling, the (h, w) window of the denoiser, one or per unet (None: untiled) — SampleCall._tiles_of
+    tile_overlap: Any = None                           # ... an int or (oy, ox), one or per unet (None: a quarter of the tile side)
+    tile_blend: Any = None                             # ... the window: 'ramp' (None: the same) | 'uniform'
     # not public keywords: set by sample_requests, the sample_pipelined workers and ElucidatedImagen._call
     negative_rows: Optional[torch.Tensor] = None       # bool [rows]: the samples the merged negative prompt applies to
     pipelined_stage: bool = False                      # one stage of a cascade whose guidance scales sample_pipelined has checked as a whole
@@ -111,6 +115,7 @@ class _Call:
     guidance: Any = None                               # per unet: None (cond_scale as it stands) | the fp32 [steps] scales of a schedule that varies
     guide: Any = None                                  # None, or per unet: None | ('rescale', phi) | ('apg', eta, norm_threshold, momentum)
     composed: Any = None                               # None, or dict(K, prompts [(embeds, masks)] of the prompts 1 .. K - 1, weights per unet fp32 [K, B], masks None | K x (None | fp32 [B | 1, H, W]))
+    tiles: Any = None                                  # None, or per unet: None | tile_geometry(...) of the stage's canvas
     sizes: Any = None                                  # per unet: image_sizes[i] (int, square), or (H, W) where image_shapes says H != W
     frames: int = 0                                    # video_frames of a video cascade, else 0
     known: Any = None                                  # inpainting: the normalised known image / clip (reference layout) and its mask
@@ -130,6 +135,45 @@ def _seed_spans(seed, batch: int, sample_offset: int = 0):
         assert r0 == batch, f'merged requests cover {r0} rows, the batch has {batch}'
         return spans
     return [(int(seed), 0, batch, sample_offset)]
+
+
+# ---- tiled sampling: the geometry and the window weights of one stage (host code; the kernel side is TILES, include/imagen_hip.h) ----
+TILE_BLENDS = ('ramp', 'uniform')
+
+
+def tile_origins(N: int, L: int, o: int) -> list:
+    """The tile origins along one axis of length N for tiles of length L at overlap o (0 <= o < L), stride s = L - o: 0, s, 2 s, ... while
+    < N - L, then N - L — the last tile is clamped to the canvas, so its overlap may be larger.  N == L: one tile."""
+    if N < L:
+        raise ValueError(f'a tile side of {L} is larger than the canvas side of {N}')
+    if not 0 <= o < L:
+        raise ValueError(f'an overlap of {o} is outside [0, {L}) (the tile side)')
+    return [*range(0, N - L, L - o), N - L]
+
+
+def tile_window(L: int, o: int, blend: str) -> torch.Tensor:
+    """The fp64 window of one axis: 'uniform' 1; 'ramp' min(i + 1, L - i, o + 1) / (o + 1) — linear over the overlap at both ends, 1 between."""
+    if blend == 'uniform':
+        return torch.ones(L, dtype=torch.float64)
+    i = torch.arange(L, dtype=torch.float64)
+    return torch.minimum(torch.minimum(i + 1, L - i), torch.tensor(o + 1., dtype=torch.float64)) / (o + 1)
+
+
+def tile_geometry(H: int, W: int, h: int, w: int, oy: int, ox: int, blend: str = 'ramp') -> dict:
+    """The tiles of an H x W canvas: dict(h, w, oy, ox, blend, Ty, Tx, T, origins int32 [T, 2] = (y0, x0) in row-major tile order (y outer), nw
+    fp32 [T, h * w]).  nw[t][p] = w_t(p) / sum_s w_s(p) with the separable window w_y(i) w_x(j), computed in fp64 and rounded to fp32: exactly
+    1.0 where one tile covers the pixel.  Raises ValueError as tile_origins does."""
+    if blend not in TILE_BLENDS:
+        raise ValueError(f"tile_blend = {blend!r}: {' | '.join(repr(b) for b in TILE_BLENDS)}")
+    ys, xs = tile_origins(H, h, oy), tile_origins(W, w, ox)
+    win = tile_window(h, oy, blend)[:, None] * tile_window(w, ox, blend)[None, :]
+    origins = [(y0, x0) for y0 in ys for x0 in xs]
+    total = torch.zeros(H, W, dtype=torch.float64)
+    for y0, x0 in origins:
+        total[y0:y0 + h, x0:x0 + w] += win
+    nw = torch.stack([win / total[y0:y0 + h, x0:x0 + w] for y0, x0 in origins]).to(torch.float32)
+    return dict(h=h, w=w, oy=oy, ox=ox, blend=blend, Ty=len(ys), Tx=len(xs), T=len(origins),
+                origins=torch.tensor(origins, dtype=torch.int32), nw=nw.reshape(len(origins), h * w).contiguous())
 
 
 # ---- what every resolver shares ---------------------------------------------------------------------------------------------------
@@ -416,6 +460,79 @@ class SampleCall:
             raise ValueError('compose: cond_scale is 1 and every further weight is 0 on every stage of this call, so the keyword would be silently ignored')
         return dict(K=len(prompts) + 1, prompts=prompts, weights=by_unet, masks=masks if any(m is not None for m in masks) else None)
 
+    def _tiles_of(self, c: _Call):
+        """`tile_shapes=` / `tile_overlap=` / `tile_blend=` of one call whose sizes, batch, cond_scale and guidance are resolved: None without
+        `tile_shapes` (or with None for every stage the call runs), else per unet None | tile_geometry(...) of that stage's canvas (c.sizes).  One
+        (h, w) — a pair of ints is ONE tile shape, never two stages' square sides —, an int or None serves every unet; a tuple of pairs / ints /
+        None holds one entry per unet; the overlap likewise.  Every refusal is a ValueError; nothing is built or launched."""
+        if c.tile_shapes is None:
+            if c.tile_overlap is not None or c.tile_blend not in (None, 'ramp'):
+                raise ValueError('tile_overlap / tile_blend without tile_shapes: there is no tile to overlap or blend')
+            return None
+        n = len(self.unets)
+        pair = lambda v: isinstance(v, (tuple, list, torch.Size)) and len(v) == 2 and all(isinstance(e, int) and not isinstance(e, bool) for e in v)
+        one = lambda v: (isinstance(v, int) and not isinstance(v, bool)) or pair(v)
+        shapes = per_unet(c.tile_shapes, 'tile_shapes', n, one, entry='one (h, w), int or None')
+        overlaps = per_unet(c.tile_overlap, 'tile_overlap', n, one, entry='one int, (oy, ox) or None')
+        blend = 'ramp' if c.tile_blend is None else c.tile_blend
+        if blend not in TILE_BLENDS:
+            raise ValueError(f"tile_blend = {blend!r}: {' | '.join(repr(b) for b in TILE_BLENDS)}")
+        first, last = stage_range(c, n)
+        if all(shapes[idx] is None for idx in range(first, last)):
+            return None
+        if any(isinstance(u, Unet3D) for u in self.unets):
+            raise ValueError('tile_shapes: this cascade has a Unet3D stage; tiled sampling runs on the image engine (UnetEngine) only')
+        self._refuse_inpainting(c, 'tile_shapes', 'pastes the known pixels on the whole image; inpaint untiled')
+        if c.compose is not None or c.compose_mask is not None:
+            raise ValueError('tile_shapes with compose / compose_mask: COMPOSE_X0 reads its masks per engine row, which would be per tile; not covered')
+        if c.guidance_rescale is not None or c.guidance_apg is not None:
+            raise ValueError('tile_shapes with guidance_rescale / guidance_apg: their per-sample sums (GUIDE_X0) would be per-tile sums')
+        if c.guidance_interval is not None:
+            raise ValueError('tile_shapes with guidance_interval: the unguided steps run a sibling plan on the stage\'s state, which a tiled stage does not build')
+        if any(g is not None and bool((g == 1.).any()) for g in c.guidance):
+            raise ValueError('tile_shapes with a guidance_schedule that has unguided steps (scale 1): those run a sibling plan, which a tiled stage does not build')
+        if c.conditioning is not None:
+            raise ValueError('tile_shapes with a `conditioning` handle: a handle stamps the engine of one prompt row per sample; pass text_embeds / texts')
+        if isinstance(c.seed, (list, tuple)) or c.negative_rows is not None:
+            raise ValueError('tile_shapes inside merged requests (sample_requests): not covered')
+        if c.cond_images is not None:
+            raise ValueError('tile_shapes with cond_images: the conditioning image is staged per engine row, which would be per tile; not covered')
+        out, tmax = [None] * n, ops.ENUMS['IMAGEN_TILE_MAX']
+        for idx in range(first, last):
+            s, o, unet = shapes[idx], overlaps[idx], self.unets[idx]
+            if s is None:
+                continue
+            what = f'tile_shapes[{idx}]'
+            if not one(s):
+                raise ValueError(f'{what} = {s!r}: an (h, w) pair of ints, an int or None')
+            if o is not None and not one(o):
+                raise ValueError(f'tile_overlap[{idx}] = {o!r}: an int, an (oy, ox) pair of ints or None')
+            if getattr(unet, 'self_cond', False):
+                raise ValueError(f'{what}: unet {idx + 1} self-conditions on the previous x0 per engine row, which would be the unblended tile; not covered')
+            if getattr(unet, 'has_cond_image', False):
+                raise ValueError(f'{what}: unet {idx + 1} takes cond_images (cond_images_channels), staged per engine row; not covered')
+            h, w = (int(s), int(s)) if isinstance(s, int) else (int(s[0]), int(s[1]))
+            oy, ox = (h // 4, w // 4) if o is None else (int(o), int(o)) if isinstance(o, int) else (int(o[0]), int(o[1]))
+            if min(h, w) <= 0:
+                raise ValueError(f'{what} = {s!r}: positive sides')
+            unet.check_image_size(h, w, what=what)
+            H, W = (c.sizes[idx],) * 2 if isinstance(c.sizes[idx], int) else c.sizes[idx]
+            if h > H or w > W:
+                raise ValueError(f'{what} = {h} x {w} is larger than the canvas of unet {idx + 1}, {H} x {W}')
+            for L, ov, ax in ((h, oy, 'y'), (w, ox, 'x')):
+                if not 0 <= ov < L:
+                    raise ValueError(f'tile_overlap[{idx}]: {ov} along {ax} is outside [0, {L}) (the tile side)')
+            ty, tx = len(tile_origins(H, h, oy)), len(tile_origins(W, w, ox))
+            if ty * tx > tmax:
+                raise ValueError(f'{what}: {ty} x {tx} = {ty * tx} tiles on a canvas of {H} x {W}, at most {tmax} are blended (IMAGEN_TILE_MAX)')
+            rows = ty * tx * c.batch_size * (1 if c.cond_scale[idx] == 1. and c.guidance[idx] is None else 2)
+            heads = unet._attn_kwargs['heads']
+            if rows * heads > 65535:
+                raise ValueError(f'{what}: {ty * tx} tiles of a batch of {c.batch_size} are {rows} engine rows; rows x {heads} attention heads exceed '
+                                 f'the 65535 workgroups of a launch axis, which the engine refuses')
+            out[idx] = tile_geometry(H, W, h, w, oy, ox, blend)
+        return tuple(out)
+
     # ---- the negative prompt: as given, encoded, checked
     def _negative_of_call(self, conditioning, negative_texts, negative_text_embeds, negative_text_masks, negative_rows=None):
         """The negative prompt of one sample() call as given — by keyword, or on the conditioning handle — for _resolve, which resolves and
@@ -578,6 +695,7 @@ class SampleCall:
         c.guidance = self._resolve_guidance(c, guidance)
         c.guide = self._check_guide(c, guide)
         c.composed = self._compose_of(c)
+        c.tiles = self._tiles_of(c)
         if c.seed is None:
             c.seed = self._next_seed()
         # the negative prompt of this call: resolved and checked here, before any stage is built or anything is launched

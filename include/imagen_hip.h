@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define IMAGEN_ABI_VERSION 15 /* 15 (additive, same number): COMPOSE_X0, a second kind of the extension range (composed prompts, Imagen.sample(compose=[...])), added as GUIDE_X0 was: imagen_sizeof(IMAGEN_OP_COMPOSE_X0) == 0 on a library from before it.  15 (additive, same number): GUIDE_X0, an op kind of the extension range (ImagenExtOpKind below: guidance rescale and projected guidance, Imagen.sample(guidance_rescale=, guidance_apg=)) — no existing struct or kind changed, every plan of before is launched as before; a library built before it answers imagen_sizeof(IMAGEN_OP_GUIDE_X0) == 0 and the host refuses the keyword with a "rebuild" message.  15: TEMPORAL_ATTENTION takes F <= 128 (clips of 33 .. 128 frames run on a tiled kernel; F <= 32 launches what it launched before; no struct changed), and head_dim 128 is accepted by ATTENTION / QNORM / KV_PREP / LINCTX / LINEAR_XATTN (Unet(attn_dim_head=128); no struct changed, no new op kind);  14: LINCTX, LINEAR_XATTN (LinearCrossAttention: Unet(use_linear_cross_attn=...); no struct of before changed);  13: ImagenLincombParams.thr1_out / thr3_out (LINCOMB writes out the thresholded operands it sums: the self-conditioning input of the ElucidatedImagen sampler; NULL = the launch of before);  12: ImagenTemporalAttentionParams.head_dim (the temporal attention of Imagen-Video at head dim 32, the reference's Unet3DConfig default; 0 = 64: plans of before are unchanged);  11: ImagenDdpmUpdateParams.row_keys (per-row Philox key + sample index: requests merged into one batch draw their own noise);  10: ImagenIgemmParams.pad_x1 (a KH x KW window with its own x padding: the causal temporal conv of Imagen-Video as ONE (3 x 1)-tap launch);  9: LINEAR_F32, SCALE_SHIFT ss_f32;  8: ROWCHAIN, the latency probes;  3: head_dim in the attention / QNORM / KV_PREP params; 4: DDPM_UPDATE x0_thr; 5: GCA_TAIL; 6: ACT_PREP self_stat, STEP_SLICE;
+#define IMAGEN_ABI_VERSION 15 /* 15 (additive, same number): TILES, kind 35 in a further block of the extension range (ImagenExtOpKind2; tiled sampling, Imagen.sample(tile_shapes=)), added as GUIDE_X0 and COMPOSE_X0 were: imagen_sizeof(IMAGEN_OP_TILES) == 0 on a library from before it.  15 (additive, same number): COMPOSE_X0, a second kind of the extension range (composed prompts, Imagen.sample(compose=[...])), added as GUIDE_X0 was: imagen_sizeof(IMAGEN_OP_COMPOSE_X0) == 0 on a library from before it.  15 (additive, same number): GUIDE_X0, an op kind of the extension range (ImagenExtOpKind below: guidance rescale and projected guidance, Imagen.sample(guidance_rescale=, guidance_apg=)) — no existing struct or kind changed, every plan of before is launched as before; a library built before it answers imagen_sizeof(IMAGEN_OP_GUIDE_X0) == 0 and the host refuses the keyword with a "rebuild" message.  15: TEMPORAL_ATTENTION takes F <= 128 (clips of 33 .. 128 frames run on a tiled kernel; F <= 32 launches what it launched before; no struct changed), and head_dim 128 is accepted by ATTENTION / QNORM / KV_PREP / LINCTX / LINEAR_XATTN (Unet(attn_dim_head=128); no struct changed, no new op kind);  14: LINCTX, LINEAR_XATTN (LinearCrossAttention: Unet(use_linear_cross_attn=...); no struct of before changed);  13: ImagenLincombParams.thr1_out / thr3_out (LINCOMB writes out the thresholded operands it sums: the self-conditioning input of the ElucidatedImagen sampler; NULL = the launch of before);  12: ImagenTemporalAttentionParams.head_dim (the temporal attention of Imagen-Video at head dim 32, the reference's Unet3DConfig default; 0 = 64: plans of before are unchanged);  11: ImagenDdpmUpdateParams.row_keys (per-row Philox key + sample index: requests merged into one batch draw their own noise);  10: ImagenIgemmParams.pad_x1 (a KH x KW window with its own x padding: the causal temporal conv of Imagen-Video as ONE (3 x 1)-tap launch);  9: LINEAR_F32, SCALE_SHIFT ss_f32;  8: ROWCHAIN, the latency probes;  3: head_dim in the attention / QNORM / KV_PREP params; 4: DDPM_UPDATE x0_thr; 5: GCA_TAIL; 6: ACT_PREP self_stat, STEP_SLICE;
                                * 7: every launch carries sizeof(its params struct) (a stale mirror of a struct fails loudly), ImagenIgemmParams.dbg -> launcher_word, kernel families 6 and 7, ImagenAttentionParams.softmax_mode */
 
 typedef void* imagen_stream_t; /* hipStream_t */
@@ -77,6 +77,11 @@ enum ImagenExtOpKind {
   IMAGEN_OP_GUIDE_X0 = 33,     /* guided x0 with per-sample statistics: guidance rescale | adaptive projected guidance; two launches (reduce, apply) */
   IMAGEN_OP_COMPOSE_X0 = 34,   /* composed guidance: K weighted, optionally masked prompts against one null branch, then CFG_X0's x0; one launch */
   IMAGEN_OP_EXT_END = 35
+};
+/* The extension range goes on in a block of its own (IMAGEN_OP_EXT_END stays the end of the block above, which callers have pinned). */
+enum ImagenExtOpKind2 {
+  IMAGEN_OP_TILES = 35,        /* tiled sampling: gather overlapping windows of a canvas into tile rows | blend tile rows into the canvas; one launch */
+  IMAGEN_OP_EXT2_END = 36
 };
 
 /* ------------------------------------------------------------------------------------------------
@@ -447,6 +452,31 @@ typedef struct ImagenComposeX0Params {
   const float* weights; const float* masks;
   int32_t B, n_per_sample, hw, K, objective;
 } ImagenComposeX0Params;
+
+/* TILES — tiled sampling (Bar-Tal et al. 2023, "MultiDiffusion"): the denoiser runs on T overlapping h x w windows of an H x W canvas, and the
+ * windows' x0 predictions are blended into one canvas x0; the reference has no such lines.  The canvas is fp32 NCHW [B, C, H, W], the tiles are
+ * fp32 [T, B, C, h, w], tile-major: row t * B + b is tile t of sample b (the engine's rows, branch-major around them).
+ *   origins int32 [T][2] = (y0, x0) in device memory, tiles in row-major order of the grid (y outer).  The kernel clamps every origin into
+ *           [0, H - h] x [0, W - w] before use, so no table can address outside the buffers.
+ *   nw      fp32 [T][h * w] in device memory (blend only): the normalised window weights, sum over the covering tiles == 1 at every canvas pixel,
+ *           exactly 1.0f where one tile covers it.  Shared by the samples and the channels.
+ * mode 0, gather: src = canvas, dst = tiles;  dst[t][b][c][y][x] = src[b][c][y0_t + y][x0_t + x], a pure copy.  absdst, nw unused.
+ * mode 1, blend:  src = tiles, dst = canvas.  Per canvas element, in fp32, over the tiles that cover it in ascending t — one fixed order, no
+ *           atomics, no LDS, bit-identical from run to run:
+ *               acc = nw_t * v_t (the first covering tile);   acc = acc + nw_t * v_t (the rest, contracted as the compiler contracts it)
+ *           dst = acc, and absdst = |acc| where absdst != NULL.  A pixel one tile covers with nw == 1.0f receives the bits of v (1.0f * v == v;
+ *           only a signalling NaN is quietened); a pixel no tile covers receives 0 (the host's geometry leaves none).
+ * One launch over the output, 4 consecutive x per thread: 16-byte accesses where W % 4 == 0, w % 4 == 0 and src, dst, absdst, nw are 16-byte
+ * aligned, else 4-byte accesses; the tile side of a tile whose clamped x0_t % 4 != 0 is read 4 bytes at a time (the kernel tests the entry it reads,
+ * tile by tile: the table lives in device memory).
+ * Refused: T outside 1 .. IMAGEN_TILE_MAX, h > H or w > W, a non-positive dimension, an unknown mode, nw == NULL in mode 1. */
+#define IMAGEN_TILE_MAX 64
+typedef struct ImagenTilesParams {
+  const float* src; float* dst; float* absdst;
+  const int32_t* origins;
+  const float* nw;
+  int32_t B, C, H, W, h, w, T, mode;
+} ImagenTilesParams;
 
 /* QUANTILE — torch.quantile(|x0| per sample, q) ip.py:2097-2101 (linear interpolation), exact. */
 typedef struct ImagenQuantileParams {
